@@ -4,7 +4,12 @@
 Metric (BASELINE.json): 3-D FFT GFLOP/s + fraction of the HBM roofline, 1024^3
 double-complex, forward transform (offt_3d_execute), data resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--dtype f64|f32] [--n 1024]
+  python bench.py --gpus N --steps K --warmup W [--dtype f64|f32] [--n 1024] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs or
+work of its own: the CPU baseline at N = 1, and at N > 1 the pipelined figure and the extras below.
+--dump-outputs DIR writes the array the last timed step left to its caller as DIR/*.npy (see
+dump_outputs); the input is the same seeded fill at every run, so two builds compare output for output.
 
 One process per GPU.  Either the caller starts the ranks (torch.distributed.run sets RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_*), or -- when WORLD_SIZE is unset and N > 1 -- this script is the
@@ -18,7 +23,7 @@ A "step" is one synchronous offt_3d_execute of the whole grid, at every N (the r
 times one call per repetition between barriers, run-fft.c:374-395).  flops = 5 E log2 E,
 algorithmic bytes = 6 * S * E / P per GPU per transform (S = 16 B double-complex, 8 B
 single-complex).  Rank 0 prints ONE JSON line.  For N > 1 the headline is the 1 x N
-mesh (one exchange over all N - 1 xGMI links) in that same synchronous mode; the line also carries
+mesh (one exchange over all N - 1 xGMI links) in that same synchronous mode; with --full the line also carries
 the pipelined figure (`ms_per_step_pipelined`: the K steps enqueued back to back, one wait), the
 reference-default mesh (2 x 4 at N = 8), an exchange-only and a compute-only time of the headline
 schedule, the per-link rate against 153 GB/s, an xGMI link probe and the number of ranks that
@@ -48,9 +53,11 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"], help="f64: double-complex (headline); f32: single-complex (configs[4])")
     ap.add_argument("--p1", type=int, default=-1, help="mesh rows of the headline; default 1 (one exchange over all xGMI links)")
     ap.add_argument("--layout", default="zyx", choices=["zyx", "xyz"], help="output layout: reference default z-y-x, or S=1 x-y-z")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline (N = 1), the pipelined figure and the extras (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-n", type=int, default=0, help="grid side of the CPU baseline (0: 1024 if the host has >= 64 GiB free, else 512)")
-    ap.add_argument("--no-extras", action="store_true", help="N > 1: headline only (no pencil mesh, split timings, link probe)")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N > 1: no pencil mesh, split timings, link probe")
     ap.add_argument("--launch-timeout", type=float, default=900.0, help="wall-clock limit of the whole run in seconds")
     ap.add_argument("--launch-selftest", action="store_true", help="rehearse the launcher on CPU: ranks rendezvous over gloo, no GPU work")
     return ap.parse_args(argv)
@@ -265,6 +272,37 @@ def xgmi_block(group, esz, E, world, t_exchange_step):
             "frac_of_link_bidirectional": round(2 * link_bytes / t_exchange_step / XGMI_LINK, 4)}
 
 
+DUMP_BYTES = 32 << 20  # all ranks' files together
+
+
+def dump_outputs(dirname, data, osize, ostride, rank, world, seed=20261016):
+    """--dump-outputs: the rank's output block as its caller reads it (element (i, j, k), i < osize[0] ..., at
+    i*ostride[0] + j*ostride[1] + k*ostride[2] complex elements into `data`, run-fft.c:477-478), as (real, imag) rows in the
+    precision of `data`: output[_rank<r>].npy.  A block larger than its share of DUMP_BYTES is sampled at fixed seeded
+    positions (the same at every run with the same arguments); their flat indices (i, j, k row-major) go to
+    output[_rank<r>]_index.npy as float64.  Returns the paths written."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    m = osize[0] * osize[1] * osize[2]
+    row = 2 * data.element_size()
+    share = DUMP_BYTES // world
+    sampled = m * row > share
+    idx = np.unique(np.random.default_rng(seed + rank).integers(0, m, share // (row + 8))) if sampled else np.arange(m)
+    i, j, k = np.unravel_index(idx, osize)
+    off = i * ostride[0] + j * ostride[1] + k * ostride[2]
+    if m and not 0 <= off.min() <= off.max() < data.numel() // 2:
+        raise ValueError(f"output block {osize} / {ostride} does not fit the {data.numel() // 2} elements of the array")
+    rows = data.view(-1, 2)[torch.from_numpy(off).to(data.device)].cpu().numpy()
+    paths = [os.path.join(dirname, f"output{tag}.npy")]
+    np.save(paths[0], rows)
+    if sampled:
+        paths.append(os.path.join(dirname, f"output{tag}_index.npy"))
+        np.save(paths[1], idx.astype(np.float64))
+    return paths
+
+
 # ------------------------------------------------------------------------------------------------
 # one rank
 # ------------------------------------------------------------------------------------------------
@@ -406,6 +444,8 @@ def rank_main(args):
     c = api.comm_dict(po)
     # the SAME mode at every N: one synchronous offt_3d_execute per step between two barriers (run-fft.c:374-395)
     dt, pass_s, dev_s = timed(po, data, args.steps, args.warmup, enqueue_only=False)
+    if args.dump_outputs:  # in place: `data` holds what the last timed step handed back, before anything else runs on it
+        dump_outputs(args.dump_outputs, data, c["osize"], c["ostride"], rank, world)
     steps = args.steps
     ms = dt / steps * 1e3
     value = flops * steps / dt / 1e9
@@ -431,7 +471,7 @@ def rank_main(args):
                       "grid": [n, n, n], "mesh": f"{c['p1']}x{c['p2']}", "output_layout": args.layout,
                       "steps_enqueued": "one synchronous call per step"},
            "roofline": roof}
-    if multi:
+    if multi and args.full:
         # second figure, NOT the headline: the K steps enqueued back to back with one wait, as a caller that transforms a
         # series of fields would do (no host round trip between steps)
         try:
@@ -447,9 +487,10 @@ def rank_main(args):
     # DIAGNOSTICS build (tools/liboffthip_diag.so, `make`), never in the product library the headline was measured with.
     # The product's world is closed, the diagnostics build gets a world of its own, and the headline plan is made again there.
     diag_path = os.path.join(ROOT, "tools", "liboffthip_diag.so")
-    if multi and not args.no_extras and not os.path.exists(diag_path):
+    extras = multi and args.full and not args.no_extras
+    if extras and not os.path.exists(diag_path):
         out["multi_gpu"] = {"n_ranks_seen": int(L.offt_hip_world_count()), "note": "tools/liboffthip_diag.so not built: no split timings"}
-    elif multi and not args.no_extras:
+    elif extras:
         extra = {"library": "tools/liboffthip_diag.so (product + offt_hip_set_debug_skip); the headline above used offt_amd/liboffthip.so"}
         try:
             extra["n_ranks_seen"] = int(L.offt_hip_world_count())
@@ -520,7 +561,7 @@ def rank_main(args):
         api.offt_3d_fin(po)
 
     if rank == 0:
-        if world == 1 and not multi and not args.no_cpu_baseline:
+        if world == 1 and not multi and args.full and not args.no_cpu_baseline:
             try:
                 cores = len(os.sched_getaffinity(0))
                 big = mem_available_gib() >= 64.0

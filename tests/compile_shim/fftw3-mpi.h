@@ -1,5 +1,5 @@
 /* TEST SCAFFOLDING, declarations only (see fftw3.h next to this file): the four fftw_mpi_* calls of the reference
- * harness's `-a 1` comparison path (run-fft.c:324-334, 424), for a -fsyntax-only check. */
+ * harness's `-a 1` comparison path (run-fft.c:324-334, 424), for the reference's offt.h to compile. */
 #ifndef OFFT_TEST_SHIM_FFTW3_MPI_H
 #define OFFT_TEST_SHIM_FFTW3_MPI_H
 #include <stddef.h>

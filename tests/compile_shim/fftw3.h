@@ -1,7 +1,7 @@
 /* TEST SCAFFOLDING, declarations only -- not FFTW, not a reference build.
- * tests/test_boundary_pin.py runs `gcc -fsyntax-only` on the reference's own caller (run-fft.c, read from its mounted
- * location) against include/offt.h, and compares struct layouts with the reference's offt.h; both need the FFTW type and
- * function NAMES those files mention to exist.  Nothing here is compiled into an object, linked, or shipped. */
+ * tests/golden/make_fixtures.py compiles the reference's offt.h (from a reference checkout) to record the struct layouts
+ * tests/test_boundary_pin.py compares ours with; that header needs the FFTW type and function NAMES it mentions to exist.
+ * Nothing here is linked into the project or shipped. */
 #ifndef OFFT_TEST_SHIM_FFTW3_H
 #define OFFT_TEST_SHIM_FFTW3_H
 typedef double fftw_complex[2];

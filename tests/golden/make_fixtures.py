@@ -18,11 +18,21 @@ corroboration only; the numerics are pinned by numpy (item 3) and the closed-for
    run-fft -v spot values at 128^3 on 2 ranks, and the default P1 choices.
 3. numpy_fftn_*.npz -- independent second oracle: numpy.fft.fftn (pocketfft) of
    the seeded hash field for 8^3, 16^3 and 20^3.
+4. reference_boundary.json -- only with a reference checkout and the directory of an
+   MPI's mpi.h given as arguments (`make_fixtures.py <checkout> <mpi include dir>`): what tests/test_boundary_pin.py pins our header
+   against, as data -- the names of offt.h its run-fft.c uses, the offsets, sizes
+   and macro values of its offt.h compiled with the Hopper flags (stand-in FFTW
+   names from tests/compile_shim/, an MPI header), and SHA-256 hashes of its five
+   entry points' prototypes.  No reference text is stored.
 """
 import glob
+import hashlib
 import json
 import os
+import re
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -68,7 +78,34 @@ def numpy_goldens():
         np.savez_compressed(os.path.join(HERE, f"numpy_fftn_hash_{n}.npz"), F=np.fft.fftn(f))
 
 
+def reference_boundary(ref, mpi_inc):
+    import pathlib
+    import test_boundary_pin as B
+    hop = ["-DA2AV", "-DSTRIDE", "-DSHSONG_HOPPER", "-DSHSONG_MPICH"]
+    header = os.path.join(ref, "offt.h")
+    with tempfile.TemporaryDirectory() as tmp:
+        layout = B.layout_program(hop + ["-I" + os.path.join(HERE, "..", "compile_shim"), "-I" + mpi_inc, "-include", header],
+                                  pathlib.Path(tmp), "ref")
+    htxt = open(header).read()
+    code = re.sub(r"//[^\n]*|/\*.*?\*/", " ", open(os.path.join(ref, "run-fft.c")).read(), flags=re.S)
+    owner = {f: st for st, fields in B.PUBLIC.items() for f in fields}
+    members = {f: owner[f] for f in re.findall(r"->\s*(\w+)", code) if f in owner}
+    idents = set(re.findall(r"\b\w+\b", code))
+    declared = set(re.findall(r"\b(\w+)\s*\([^;{)]*\)\s*[;{]", htxt))  # functions the header declares or defines
+    uses = {"members": dict(sorted(members.items())),
+            "macros": [m for m in B.MACROS if m in idents],
+            "switches": sorted(m for m in set(re.findall(r"#\s*ifn?def\s+(\w+)", code))
+                               if re.search(r"#\s*define\s+%s\s*(/[/*].*)?$" % m, htxt, flags=re.M)),
+            "functions": sorted(f for f in declared if re.search(r"\b%s\s*\(" % f, code))}
+    rec = {"source": "reference checkout: run-fft.c (names used) and offt.h (layout, prototype hashes); make_fixtures.py item 4",
+           "caller_uses": uses, "layout": layout,
+           "prototype_sha256": sorted(hashlib.sha256(p.encode()).hexdigest() for p in B.normalised_prototypes(header))}
+    json.dump(rec, open(os.path.join(HERE, "reference_boundary.json"), "w"), indent=1)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 2:
+        reference_boundary(sys.argv[1], sys.argv[2])
     ref_dump()
     survey_values()
     numpy_goldens()

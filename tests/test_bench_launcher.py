@@ -100,3 +100,33 @@ def test_line_blocks_are_self_consistent_across_n():
     # the rank code times the SAME mode at every N and adds the pipelined figure for N > 1
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "enqueue_only=False)" in src and '"ms_per_step_pipelined"' in src and '"ms_per_step_sync"' in src
+
+
+def test_dump_outputs_writes_the_callers_view(tmp_path, monkeypatch):
+    """--dump-outputs (no GPU needed: a CPU tensor stands in for the device array): a block that fits is written whole, in the
+    caller's (i, j, k) order through ostride; a larger one as a fixed seeded sample with its positions, within the byte cap"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert not bench.parse_args([]).full and bench.parse_args(["--full", "--dump-outputs", "d"]).dump_outputs == "d"
+    osize, ostride = [3, 4, 5], [1, 3, 12]               # a transposed layout: axis 0 fastest in memory
+    data = torch.arange(2 * 60, dtype=torch.float64)
+    paths = bench.dump_outputs(str(tmp_path / "a"), data, osize, ostride, 0, 1)
+    assert [os.path.basename(p) for p in paths] == ["output.npy"]
+    got = np.load(paths[0])
+    assert got.dtype == np.float64 and got.shape == (60, 2)
+    i, j, k = 2, 1, 3
+    assert (got[(i * 4 + j) * 5 + k] == data.view(-1, 2)[i * 1 + j * 3 + k * 12].numpy()).all()
+    # sampled: the same positions at every run, each rank's share of the cap, float32 kept as float32
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 4096)
+    big = torch.randn(2 * 64 ** 3, dtype=torch.float32)
+    osize, ostride = [64, 64, 64], [64 * 64, 64, 1]
+    p1 = bench.dump_outputs(str(tmp_path / "b"), big, osize, ostride, 1, 2)
+    p2 = bench.dump_outputs(str(tmp_path / "c"), big, osize, ostride, 1, 2)
+    assert [os.path.basename(p) for p in p1] == ["output_rank1.npy", "output_rank1_index.npy"]
+    v, idx = np.load(p1[0]), np.load(p1[1])
+    assert v.dtype == np.float32 and idx.dtype == np.float64 and len(v) == len(idx) > 100
+    assert v.nbytes + idx.nbytes <= 4096
+    assert (np.load(p2[0]) == v).all() and (np.load(p2[1]) == idx).all()
+    assert (v == big.view(-1, 2)[torch.from_numpy(idx.astype(np.int64))].numpy()).all()

@@ -1,27 +1,23 @@
-"""The drop-in boundary pinned against the reference's OWN files (container only: skipped where /root/reference or an MPI
-header is absent -- nothing of the reference travels to the GPU box).
+"""The drop-in boundary pinned against the reference's own files, through what was recorded from them: nothing of the
+reference is read at test time.  tests/golden/reference_boundary.json holds data only -- names, numbers and hashes --
+written by `tests/golden/make_fixtures.py <reference checkout>`.
 
-1. The reference's caller, run-fft.c (run-fft.c:49-57 fills through istart/isize/istride, 314-321 calls offt_3d_init with
-   17 arguments, 361-364 / 477-478 read ostart/osize/ostride and po->t), is checked with `gcc -fsyntax-only` from its
-   mounted location against include/offt.h: every name, field, macro and call signature it uses must exist with a
-   compatible type.  FFTW is absent from the image; the FFTW *names* come from a declarations-only header under
-   tests/compile_shim/ (compile check only -- nothing is built, linked or run).
-2. offsetof / sizeof of every public field of _offt_params, _offt_comm and _offt_plan are compared between include/offt.h
-   and the reference's offt.h preprocessed with its Hopper flags (-DA2AV -DSTRIDE -DSHSONG_HOPPER, Makefile:27-29)."""
+1. Every name of offt.h that the reference's caller, run-fft.c, uses (struct members it reaches through `->`, macros,
+   functions; recorded as `caller_uses`) must exist in include/offt.h as the same kind of name: a probe generated from the
+   list is checked with `gcc -fsyntax-only` against our header alone -- no MPI or FFTW header needed.
+2. offsetof / sizeof of every public field of _offt_params, _offt_comm and _offt_plan, and the values of the public
+   macros, equal those recorded from the reference's offt.h preprocessed with its Hopper flags (-DA2AV -DSTRIDE
+   -DSHSONG_HOPPER, Makefile:27-29); the five entry points' prototypes equal the recorded ones (whitespace removed,
+   compared by SHA-256)."""
+import hashlib
+import json
 import os
 import subprocess
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-SHIM = os.path.join(ROOT, "tests", "compile_shim")
-MPI_INC = next((d for d in ("/opt/conda/include", "/usr/include/mpich", "/usr/lib/x86_64-linux-gnu/mpich/include", "/usr/include/openmpi")
-                if os.path.exists(os.path.join(d, "mpi.h"))), None)
-HOP = ["-DA2AV", "-DSTRIDE", "-DSHSONG_HOPPER", "-DSHSONG_MPICH"]
-
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "run-fft.c")) or MPI_INC is None,
-                                reason="needs the mounted reference and an MPI header (development container only)")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_boundary.json")
+HEADER = os.path.join(ROOT, "include", "offt.h")
+ENTRY_POINTS = ("struct _offt_plan* offt_3d_init", "void offt_3d_", "void print_params", "void offt_print_time")
 
 PUBLIC = {
     "_offt_params": ["is_converged", "is_infeasible", "is_in_database", "v"],
@@ -37,21 +33,12 @@ MACROS = ["PARAM_COUNT", "LOG0", "_P1_", "_T1_", "_W1_", "_Px1_", "_Py1_", "_Fz_
           "FFTx", "TRANSPOSE", "PACK1", "UNPACK1", "PACK2", "UNPACK2", "GES", "TUNING_REPS", "SUBTILE_SIZE", "BUFFER_SIZE_LIMIT"]
 
 
-def test_reference_caller_compiles_against_our_header():
-    # `-include include/offt.h` comes first and shares the reference header's include guard (OFFT_INCLUDE), so the
-    # `#include "offt.h"` inside run-fft.c -- which would find the file next to it -- adds nothing: the caller sees OUR header
-    cmd = ["gcc", "-std=gnu99", "-fsyntax-only", "-Werror=implicit-function-declaration", "-Werror=incompatible-pointer-types",
-           "-Werror=int-conversion", "-w"] + HOP + ["-I" + SHIM, "-I" + MPI_INC, "-include", os.path.join(ROOT, "include", "offt.h"),
-                                                     os.path.join(REF, "run-fft.c")]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    # the guard trick must really have kept the reference's header out: its struct has MPI_Comm members, ours void *
-    probe = subprocess.run(["gcc", "-E"] + HOP + ["-I" + SHIM, "-I" + MPI_INC, "-include", os.path.join(ROOT, "include", "offt.h"),
-                                                  os.path.join(REF, "run-fft.c")], capture_output=True, text=True)
-    assert probe.returncode == 0 and "MPI_Comm *comm1" not in probe.stdout and "void *comm1" in probe.stdout
+def normalised_prototypes(path):
+    """the entry points' declarations of a header, whitespace removed"""
+    return ["".join(ln.split()) for ln in open(path) if ln.startswith(ENTRY_POINTS)]
 
 
-def _layout_program(header_args, tmp_path, tag):
+def layout_program(header_args, tmp_path, tag):
     lines = ["#include <stdio.h>", "#include <stddef.h>"]
     body = []
     for st, fields in PUBLIC.items():
@@ -68,22 +55,38 @@ def _layout_program(header_args, tmp_path, tag):
     return subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
 
 
+def uses_probe(uses):
+    """a translation unit that names every recorded use: members through offsetof, macros as constant expressions (or,
+    for a switch without a value, through #ifndef), functions through their address"""
+    lines = ["#include <stddef.h>"]
+    for m in uses["switches"]:
+        lines += [f"#ifndef {m}", f'#error "{m} is not defined"', "#endif"]
+    body = [f"  s += (long)offsetof(struct {st}, {f});" for f, st in sorted(uses["members"].items())]
+    body += [f"  s += (long)({m});" for m in uses["macros"]]
+    body += [f"  f = (const void *)&{fn};" for fn in uses["functions"]]
+    return "\n".join(lines) + "\nlong probe(void) {\n  long s = 0;\n  const void *f = 0;\n" + "\n".join(body) + "\n  return s + (f != 0);\n}\n"
+
+
+def test_reference_caller_compiles_against_our_header(tmp_path):
+    uses = json.load(open(FIXTURE))["caller_uses"]
+    assert len(uses["members"]) >= 8 and len(uses["macros"]) >= 20 and len(uses["functions"]) >= 5
+    assert all(st in PUBLIC and f in PUBLIC[st] for f, st in uses["members"].items())
+    src = tmp_path / "caller_uses.c"
+    src.write_text(uses_probe(uses))
+    cmd = ["gcc", "-std=gnu99", "-fsyntax-only", "-Werror=implicit-function-declaration", "-Werror=incompatible-pointer-types",
+           "-Werror=int-conversion", "-w", "-include", HEADER, str(src)]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-3000:]
+    # the communicator members are opaque pointers in our header: a caller needs no MPI header to include it
+    probe = subprocess.run(["gcc", "-E", "-include", HEADER, str(src)], capture_output=True, text=True)
+    assert probe.returncode == 0 and "MPI_Comm" not in probe.stdout and "void *comm1" in probe.stdout
+
+
 def test_public_field_layout_equals_the_reference_header(tmp_path):
-    ours = _layout_program(["-include", os.path.join(ROOT, "include", "offt.h")], tmp_path, "ours")
-    # the reference's header from where it lies; it pulls fftw3.h / fftw3-mpi.h / mpi.h for the types of its PRIVATE members
-    ref = _layout_program(HOP + ["-I" + SHIM, "-I" + MPI_INC, "-include", os.path.join(REF, "offt.h")], tmp_path, "ref")
-    assert len(ours) == len(ref) > 90
-    for a, b in zip(ours, ref):
+    rec = json.load(open(FIXTURE))
+    ours = layout_program(["-include", HEADER], tmp_path, "ours")
+    assert len(ours) == len(rec["layout"]) > 90
+    for a, b in zip(ours, rec["layout"]):
         assert a == b, (a, b)
-    # prototypes: the five entry points with the reference's argument lists (a conflicting redeclaration is an error)
-    both = tmp_path / "both.c"
-    both.write_text('#include "%s"\n#undef OFFT_INCLUDE\n' % os.path.join(REF, "offt.h") +
-                    "struct _offt_plan* offt_3d_init(int Nx, int Ny, int Nz, double* in, double* out, int is_r2c, int fftw_flag, int is_oned, "
-                    "int is_a2a, int is_equalxy, int is_notest, int ah_strategy, int max_loop, int tuning_mode, int is_W0, "
-                    "int extrapolation_window, struct _offt_params *custom_params);\n")
-    p = subprocess.run(["gcc", "-std=gnu99", "-fsyntax-only", "-w"] + HOP + ["-I" + SHIM, "-I" + MPI_INC, str(both)], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    protos = [ln.strip() for ln in open(os.path.join(ROOT, "include", "offt.h")) if ln.startswith(("struct _offt_plan* offt_3d_init", "void offt_3d_", "void print_params", "void offt_print_time"))]
-    refp = [ln.strip() for ln in open(os.path.join(REF, "offt.h")) if ln.startswith(("struct _offt_plan* offt_3d_init", "void offt_3d_", "void print_params", "void offt_print_time"))]
-    norm = lambda s: "".join(s.split())
-    assert len(protos) == 5 and all(any(norm(a) == norm(b) for b in refp) for a in protos), (protos, refp)
+    protos = normalised_prototypes(HEADER)
+    assert len(protos) == 5 and all(hashlib.sha256(a.encode()).hexdigest() in rec["prototype_sha256"] for a in protos), protos
