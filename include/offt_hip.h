@@ -52,7 +52,14 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
                                    struct _offt_params *custom_params, int precision);
 /* direction: -1 forward (what offt_3d_execute does), +1 inverse (unnormalised,
  * FFTW_BACKWARD convention).  The inverse consumes the forward's OUTPUT layout
- * (ostart/osize/ostride) and produces the INPUT layout (istart/isize/istride). */
+ * (ostart/osize/ostride) and produces the INPUT layout (istart/isize/istride).
+ * On a real-input plan (is_r2c = 1) the inverse is complex-to-real: Nz/2+1 complex
+ * values along z in, real rows out (element (x,y,z) at scalar index
+ * z + 2*istride[1]*y + 2*istride[0]*x), numpy.fft.irfftn(X, s=(Nx,Ny,Nz)) * Nx*Ny*Nz for
+ * even and odd Nz.  As with FFTW, the imaginary parts of the z = 0 plane (and of z = Nz/2,
+ * Nz even) have no effect; the input is consumed and the one or two scalars after each
+ * row's Nz reals are undefined afterwards.  offt_hip_set_output_scale applies to the
+ * z pass, which runs last. */
 void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int direction);
 /* run on a caller-owned hipStream_t (NULL = the plan's own stream)             */
 void offt_hip_set_stream(struct _offt_plan *po, void *stream);

@@ -50,9 +50,16 @@ typedef struct offt_pass_desc {
   int in_contig, out_contig;
   int variant;    /* static-sweep variant id, -1 = default for this n           */
   double scale;   /* multiplied into the output (1.0 = unnormalised)            */
-  /* real-to-complex z pass (fftw_plan_dft_r2c_1d, offt-compute.c:334-336, 960-961):
+  /* 0: complex.
+   * 1: real-to-complex z pass (fftw_plan_dft_r2c_1d, offt-compute.c:334-336, 960-961):
    * the input line holds n REAL values (unit stride, in_contig = 1, no split) at the
-   * start of a row of n/2+1 complex slots; only output indices 0..n/2 are stored. */
+   * start of a row of n/2+1 complex slots; only output indices 0..n/2 are stored.
+   * 2: complex-to-real z pass (the inverse of 1): the input line holds n/2+1 complex values
+   * (usual in_* strides, split and table) and stands for its conjugate-symmetric extension
+   * (the imaginary parts of index 0 and, n even, n/2 have no effect); the pass stores the n
+   * REAL values of the transform at the start of a row whose out_* strides count complex
+   * slots (out_contig = 1, out_axis_stride = 1, no split).  The row's last one or two
+   * scalars (index >= n) are not written. */
   int real_input;
   /* cache hint: 1 = the output is read again right away by the next launch (the x pass over the group of z-planes the
    * y pass has just written): store with the default cache policy so that it stays in L2 / the memory-side Infinity
@@ -70,7 +77,10 @@ typedef struct offt_pass_desc {
   int tw4_n2;
 } offt_pass_desc;
 
-/* Build device twiddle tables etc. for length n; call at plan time (allocates). */
+/* Build device twiddle tables etc. for length n; call at plan time (allocates).  precision | OFFT_HIPK_PREP_C2R: also
+ * the real-output (real_input = 2) kernels of a length whose panel kernel is compiled at plan time (the z length of a
+ * real-input plan; every precompiled length has its real-output kernels already). */
+#define OFFT_HIPK_PREP_C2R 0x200
 int offt_hipk_prepare(int n, int precision);
 /* Launch one pass on `stream` (a hipStream_t).  No allocation, no sync.        */
 int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void *stream);

@@ -1149,6 +1149,12 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
     if (!g_backend) SET_ERR("no kernel for this grid: %s", offt_hipk_last_error());
     goto fail;
   }
+  /* the complex-to-real inverse's z pass: real-output kernels of a z length whose panel kernel is compiled at plan time
+   * (here, not at the first inverse execute) */
+  if (is_r2c && !g_backend && offt_hipk_prepare(Nz, precision | OFFT_HIPK_PREP_C2R)) {
+    SET_ERR("no kernel for this grid: %s", offt_hipk_last_error());
+    goto fail;
+  }
   st->s_compute = be->stream_create(); st->own_stream = 1;
   st->ev0 = be->event_create(); st->ev1 = be->event_create();
   for (int i = 0; i < 4; i++) st->evp[i] = be->event_create();
@@ -1645,7 +1651,9 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
   const long long os0 = c->ostride[0], os1 = c->ostride[1], os2 = c->ostride[2];
   void *s = st->s_compute;
   void *W = st->work;
-  if (po->is_r2c && dir > 0) { SET_ERR("complex-to-real inverse is not built (the reference has no inverse at all)"); return -1; }
+  /* complex-to-real inverse (is_r2c, dir > 0): the same schedules, the z pass last, as a real-output pass (real_input = 2)
+   * that reads the Nz/2+1 complex values of a line and writes Nz reals at the head of its row */
+  const int c2r = po->is_r2c && dir > 0;
   offt_pass_desc d[3];
   const void *src[3];
   void *dst[3];
@@ -1668,7 +1676,7 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
     void *V = st->work2;
     s1_rot = 1;
     desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c;
+    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
     desc_init(&d[1], st, Nx, dir, 0);
     desc_init(&d[2], st, Ny, dir, 1);
     d[0].ncols = Nx; d[0].nb1 = Ny;
@@ -1698,7 +1706,7 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
   } else if (S) {
     /* x-y-z output == input layout without scratch: three in-place passes, strided along y and x */
     desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c;
+    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
     d[0].ncols = Ny; d[0].nb1 = Nx;
     d[0].in_axis_stride = d[0].out_axis_stride = 1;
     d[0].in_col_stride = d[0].out_col_stride = is1;
@@ -1716,6 +1724,10 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
     d[2].in_col_stride = d[2].out_col_stride = 1;
     d[2].in_b1_stride = d[2].out_b1_stride = is1;
     for (int i = 0; i < 3; i++) { src[i] = data; dst[i] = data; slot[i] = i; }
+    if (c2r) { /* the real-output z pass reads the half spectrum the x and y passes leave: launch order x, y, z */
+      offt_pass_desc t = d[0]; d[0] = d[2]; d[2] = t;
+      slot[0] = 2; slot[2] = 0;
+    }
   } else if (zyx) {
     /* default z-y-x output.  Every pass READS whole contiguous lines and the
      * axis rotation rides on the stores (128-B column segments, row pitch of
@@ -1728,7 +1740,7 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
     const long long wy = Ny + st->wrow;                 /* W line pitch */
     const long long wx = (long long)Nz * wy + st->wpad; /* W plane (+ optional pad, elements) */
     desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c;
+    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
     desc_init(&d[1], st, Ny, dir, 1);
     desc_init(&d[2], st, Nx, dir, 0);
     if (dir < 0) {
@@ -1774,7 +1786,7 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
     void *V = st->work2;
     yzx_rot = 1;
     desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c;
+    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
     desc_init(&d[1], st, Ny, dir, 1);
     desc_init(&d[2], st, Nx, dir, 0);
     d[0].ncols = Ny; d[0].nb1 = Nx;
@@ -1806,7 +1818,7 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
      * the x pass transposes into the caller's layout */
     const long long w1 = Nz, w0 = (long long)Ny * Nz;
     desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c;
+    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
     d[0].ncols = Ny; d[0].nb1 = Nx; d[0].in_axis_stride = d[0].out_axis_stride = 1;
     d[0].in_contig = d[0].out_contig = 1;
     desc_init(&d[1], st, Ny, dir, 1);
@@ -1858,7 +1870,7 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
    * over groups of planes -- the consumer sliced along its columns -- came out SLOWER, 17.9 against 17.4 ms at 1024^3 f64,
    * profiles/r03_layouts.txt) */
   else if (s1_rot) ia = -1;
-  else if (S || dir < 0) { ia = 0; cnt = Nx; plane_elems = (double)Ny * Nz; len_a = Nzf; len_b = Ny; }
+  else if ((S || dir < 0) && !c2r) { ia = 0; cnt = Nx; plane_elems = (double)Ny * Nz; len_a = Nzf; len_b = Ny; }
   if (ia >= 0 && d[ia].nb1 == cnt && d[ia + 1].nb1 == cnt && !d[ia].real_input &&
       (st->opt.zgroup_mib >= 0 || (len_a <= 1024 && len_b <= 1024 && (g_backend || offt_hipk_keeps_output(&d[ia]))))) {
     const int ib = ia + 1;
@@ -2039,6 +2051,7 @@ static int mirror_step(hip_state *st, const step_list *L, int i, void *sx) {
     d.out_split = f.in_split; d.out_split_nfloor = f.in_split_nfloor; d.out_block_stride = f.in_block_stride;
     d.in_block_tab = f.out_block_tab; d.out_block_tab = f.in_block_tab;
     d.in_contig = f.out_contig; d.out_contig = f.in_contig;
+    if (f.real_input == 1) d.real_input = 2; /* real input -> real output: the complex-to-real inverse's z pass */
     d.scale = e->first ? st->out_scale : 1.0;
     /* cache hint: forward, a pass with out_keep is followed by the pass that re-reads its output; mirrored, that
      * follower is the producer and this one the consumer */
@@ -2067,7 +2080,7 @@ static int execute_inverse_multi(struct _offt_plan *po, void *data) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
   void *s = st->s_compute;
-  if (po->is_r2c) { SET_ERR("complex-to-real inverse is not built (the reference has no inverse at all)"); return -1; }
+  /* (a real-input plan: the mirrored K1 z pass is the real-output pass, see mirror_step) */
   /* the forward schedule, recorded: once per (plan state, caller's array) -- a second inverse on the same array replays the
    * kept list (recording costs the host some 0.1 ms during which the device waits) */
   int rc = 0;

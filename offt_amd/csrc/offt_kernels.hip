@@ -83,7 +83,7 @@ thread_local char g_err[512] = "";
 // output per work item with r multiply-adds, so a line costs at most
 // N * sum(r_s) instead of N^2 and a prime N degenerates to the plain DFT.
 // Also handles the reference's uneven A2AV per-peer splits on either side and
-// the real-input z pass.
+// the real-input and real-output z passes.
 // ---------------------------------------------------------------------------
 #define OFFT_MIX_MAXFAC 16
 struct GenArgs {
@@ -93,7 +93,7 @@ struct GenArgs {
   int n, ncols, nb1, ncp, cols;
   int in_contig, out_contig;
   int conj;
-  int real_in;
+  int real_in;      // offt_pass_desc::real_input: 1 real input, 2 real output
   int tw_in_lds;
   unsigned xcd_lim, xcd_gshift;
   int nfac;
@@ -201,8 +201,12 @@ fft_mixed_k(GenArgs a, const typename vec2<T>::type *in, typename vec2<T>::type 
     if (a.in_contig) { c = fdiv(i, N, invN); n = i - c * N; } else { n = fdiv(i, nc, invnc); c = i - n * nc; }
     const V2 *src = in + ibase + (long long)(c0 + c) * a.in_col;
     V2 x;
-    if (a.real_in) { x.x = reinterpret_cast<const T *>(src)[n]; x.y = 0; }
-    else x = src[split_off(n, a.in_split, a.in_nfloor, a.in_blk, a.in_axis, a.in_tab)];
+    if (a.real_in == 1) { x.x = reinterpret_cast<const T *>(src)[n]; x.y = 0; }
+    else if (a.real_in == 2) {  // the conjugate-symmetric extension of the n/2+1 stored values
+      const bool lo = 2 * n <= N;
+      x = src[split_off(lo ? n : N - n, a.in_split, a.in_nfloor, a.in_blk, a.in_axis, a.in_tab)];
+      if (!lo) x.y = -x.y;
+    } else x = src[split_off(n, a.in_split, a.in_nfloor, a.in_blk, a.in_axis, a.in_tab)];
     if (a.conj) x.y = -x.y;
     buf0[c * N + n] = x;
   }
@@ -258,7 +262,7 @@ fft_mixed_k(GenArgs a, const typename vec2<T>::type *in, typename vec2<T>::type 
     Ns *= r;
   }
 
-  const int kend = a.real_in ? N / 2 + 1 : N;
+  const int kend = a.real_in == 1 ? N / 2 + 1 : N;
   const float invkend = 1.0f / (float)kend;
   for (int i = tid; i < nc * kend; i += NT) {
     int c, k;
@@ -268,7 +272,8 @@ fft_mixed_k(GenArgs a, const typename vec2<T>::type *in, typename vec2<T>::type 
     w.x = v.x * (T)a.scale;
     w.y = (a.conj ? -v.y : v.y) * (T)a.scale;
     V2 *dst = out + obase + (long long)(c0 + c) * a.out_col;
-    dst[split_off(k, a.out_split, a.out_nfloor, a.out_blk, a.out_axis, a.out_tab)] = w;
+    if (a.real_in == 2) reinterpret_cast<T *>(dst)[k] = w.x;  // n reals at the head of the row
+    else dst[split_off(k, a.out_split, a.out_nfloor, a.out_blk, a.out_axis, a.out_tab)] = w;
   }
 }
 
@@ -367,21 +372,21 @@ void build_registry() {
 std::mutex g_idx_mu;
 std::unordered_map<unsigned long long, std::vector<int>> g_idx;
 size_t g_idx_size = 0;
-unsigned long long variant_key(int n, int prec, bool inc, bool outc, bool r2c, bool keep = false, bool tw4 = false) {
-  return ((unsigned long long)n << 8) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
+unsigned long long variant_key(int n, int prec, bool inc, bool outc, bool r2c, bool keep = false, bool tw4 = false, bool c2r = false) {
+  return ((unsigned long long)n << 8) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
 }
 
-Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = false, bool keep = false, bool tw4 = false) {
+Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = false, bool keep = false, bool tw4 = false, bool c2r = false) {
   std::call_once(g_reg_once, build_registry);
   std::lock_guard<std::mutex> lk(g_idx_mu);
   auto &reg = registry();
   if (g_idx_size != reg.size()) {
     g_idx.clear();
     for (size_t i = 0; i < reg.size(); ++i)
-      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4)].push_back((int)i);
+      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r)].push_back((int)i);
     g_idx_size = reg.size();
   }
-  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4));
+  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r));
   if (it == g_idx.end()) return nullptr;
   Variant *def = nullptr;
   for (int i : it->second) {
@@ -397,7 +402,9 @@ Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = f
 // its own fft_panelx_k instances at offt_hipk_prepare(): the device part of offt_panel.hpp travels inside
 // the library as a string, a shape (radix order, threads per line, panel width) is picked with the scoring of
 // tools/sweep_mixed.py, hipRTC compiles the four (in_contig, out_contig) flavours and the two real-input ones (2-4 s in all) and the
-// code object is loaded as a module.  OFFT_RTC=0 turns it off; any failure leaves the any-length kernel in
+// code object is loaded as a module.  The two real-output flavours (the c2r inverse's z pass) are a module of their own,
+// compiled only for the z length of a real-input plan (offt_hipk_prepare with OFFT_HIPK_PREP_C2R): complex plans do not
+// wait for them.  OFFT_RTC=0 turns it off; any failure leaves the any-length kernel in
 // charge and says why on stderr once.
 // ---------------------------------------------------------------------------
 struct RtcApi {
@@ -531,10 +538,11 @@ bool rtc_enabled() {
   return on;
 }
 
-// compile and register fft_panelx_k<T, n, shape> for the four flavours; 0 on success
-int rtc_build(int n, int prec) {
+// compile and register fft_panelx_k<T, n, shape> for the four flavours; 0 on success.  c2r: the two real-output flavours
+// of the default shape instead (the complex instances exist already)
+int rtc_build(int n, int prec, bool c2r = false) {
   std::lock_guard<std::mutex> lk(g_rtc_mu);
-  if (find_variant(n, prec, true, true, -1)) return 0;  // somebody was faster
+  if (find_variant(n, prec, true, true, -1, false, false, false, c2r)) return 0;  // somebody was faster
   static bool warned = false;
   auto fail = [&](const char *what, const std::string &detail) {
     if (!warned) fprintf(stderr, "offt(hip): no plan-time kernel for n=%d (%s%s%s); using the any-length kernel\n", n, what,
@@ -545,25 +553,30 @@ int rtc_build(int n, int prec) {
   if (!rtc_load()) return fail("hipRTC library not found", "");
   static const int nshapes = getenv("OFFT_RTC_SHAPES") ? atoi(getenv("OFFT_RTC_SHAPES")) : 1;
   std::vector<Shape> shapes;
-  if (!choose_shapes(n, prec, nshapes < 1 ? 1 : (nshapes > 8 ? 8 : nshapes), &shapes)) return fail("no panel shape fits", "");
+  if (!choose_shapes(n, prec, c2r || nshapes < 1 ? 1 : (nshapes > 8 ? 8 : nshapes), &shapes)) return fail("no panel shape fits", "");
   const char *T = prec == OFFT_PREC_F64 ? "double" : "float";
   std::string src;
   for (const char *p : k_rtc_source_pieces) src += p;
   hiprtcProgram prog;
   if (g_rtc.CreateProgram(&prog, src.c_str(), "offt_panel_rtc.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
     return fail("hiprtcCreateProgram failed", "");
-  // four (in_contig, out_contig) flavours per shape, plus the two real-input z-pass flavours of the default shape
-  const bool flav[6][3] = {{true, true, false}, {false, false, false}, {true, false, false}, {false, true, false},
-                           {true, true, true}, {true, false, true}};
+  // four (in_contig, out_contig) flavours per shape, plus the two real-input z-pass flavours of the default shape; or (c2r)
+  // the two real-output flavours of the default shape (the shape choice is deterministic: the same one as the complex instances')
+  const bool flav[8][4] = {{true, true, false, false}, {false, false, false, false}, {true, false, false, false}, {false, true, false, false},
+                           {true, true, true, false}, {true, false, true, false}, {true, true, false, true}, {false, true, false, true}};
   struct Inst { int shape, f; };
   std::vector<Inst> inst;
   std::vector<std::string> expr;
   for (size_t k = 0; k < shapes.size(); ++k)
-    for (int f = 0; f < (k == 0 ? 6 : 4); ++f) {
+    for (int f = c2r ? 6 : 0; f < (c2r ? 8 : k == 0 ? 6 : 4); ++f) {
       const Shape &sh = shapes[k];
       char b[256];
-      snprintf(b, sizeof b, "offtk::fft_panelx_k<%s, %d, %d, %d, %d, %d, %d, %s, %s, true, %s>", T, n, sh.tpl, sh.r0, sh.r1, sh.r2,
-               sh.cols, flav[f][0] ? "true" : "false", flav[f][1] ? "true" : "false", flav[f][2] ? "true" : "false");
+      if (flav[f][3])
+        snprintf(b, sizeof b, "offtk::fft_c2r_panelx_k<%s, %d, %d, %d, %d, %d, %d, %s, true>", T, n, sh.tpl, sh.r0, sh.r1, sh.r2, sh.cols,
+                 flav[f][0] ? "true" : "false");
+      else
+        snprintf(b, sizeof b, "offtk::fft_panelx_k<%s, %d, %d, %d, %d, %d, %d, %s, %s, true, %s>", T, n, sh.tpl, sh.r0, sh.r1, sh.r2,
+                 sh.cols, flav[f][0] ? "true" : "false", flav[f][1] ? "true" : "false", flav[f][2] ? "true" : "false");
       expr.push_back(b);
       inst.push_back(Inst{(int)k, f});
       g_rtc.AddNameExpression(prog, expr.back().c_str());
@@ -607,6 +620,7 @@ int rtc_build(int n, int prec) {
              prec ? "f32" : "f64", n, sh.r0, sh.r1, sh.r2, sh.tpl, sh.emax, sh.cols, sh.lds);
     registry().push_back(Variant{n, prec, fl[0], fl[1], inst[e].shape, inst[e].shape == 0, fl[2], sh.cols, sh.tpl * sh.cols, sh.emax, sh.lds,
                                  nullptr, nm, false, true, n % 4 != 0, (void *)fn[e]});
+    registry().back().c2r = fl[3];
   }
   return 0;
 }
@@ -714,7 +728,7 @@ int blue_m_long(int n, int prec) {
   if (!find_variant(n1, prec, false, false, -1, false, false, true)) return 0;
   long long best = 0;
   for (auto &v : registry()) {
-    if (v.prec != prec || !v.inc || !v.outc || v.r2c || v.tw4 || v.id != 0 || v.n < 64 || v.n > 4096) continue;
+    if (v.prec != prec || !v.inc || !v.outc || v.r2c || v.c2r || v.tw4 || v.id != 0 || v.n < 64 || v.n > 4096) continue;
     const long long m = (long long)n1 * v.n;
     if (m >= need && m < (1LL << 24) && (!best || m < best)) best = m;
   }
@@ -781,8 +795,10 @@ bool pair_ok(const offt_pass_desc *d) {
 
 // the panel-kernel variant that will run this descriptor, or nullptr (-> any-length kernel)
 Variant *pick_variant0(const offt_pass_desc *d, bool allow_pair) {
-  if (d->real_input && (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->direction > 0)) return nullptr;
-  const bool inc = d->in_contig != 0, outc = d->out_contig != 0, r2c = d->real_input != 0;
+  if (d->real_input == 1 && (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->direction > 0)) return nullptr;
+  // real output: n reals at the head of a row, no split on the store side (the mirror image of the real-input restrictions)
+  if (d->real_input == 2 && (!d->out_contig || d->out_axis_stride != 1 || d->out_split || d->out_split_nfloor)) return nullptr;
+  const bool inc = d->in_contig != 0, outc = d->out_contig != 0, r2c = d->real_input == 1, c2r = d->real_input == 2;
   const bool uneven = d->in_split_nfloor > 0 || d->out_split_nfloor > 0;
   const bool odd_split = (d->in_split && !is_pow2(d->in_split)) || (d->out_split && !is_pow2(d->out_split));
   static const bool pairs_on = !(getenv("OFFT_F32_PAIRS") && atoi(getenv("OFFT_F32_PAIRS")) == 0);
@@ -794,11 +810,11 @@ Variant *pick_variant0(const offt_pass_desc *d, bool allow_pair) {
     }
     if (want >= VARIANT_PAIR0) want = -1;
   }
-  Variant *v = find_variant(d->n, d->precision, inc, outc, r2c ? -1 : want, r2c);
+  Variant *v = find_variant(d->n, d->precision, inc, outc, r2c || c2r ? -1 : want, r2c, false, false, c2r);
   if (!v) return nullptr;
   if (v->mixed || !(uneven || odd_split)) return v;
   // fft_panel_k addresses per-peer blocks with shifts: other block lengths go to the length's fft_panelx_k instance
-  Variant *w = find_variant(d->n, d->precision, inc, outc, VARIANT_ANYSPLIT, r2c);
+  Variant *w = find_variant(d->n, d->precision, inc, outc, VARIANT_ANYSPLIT, r2c, false, false, c2r);
   return (w && w->id == VARIANT_ANYSPLIT) ? w : nullptr;
 }
 
@@ -811,7 +827,7 @@ Variant *pick_variant(const offt_pass_desc *d, bool allow_pair = true) {
   }
   Variant *v = pick_variant0(d, allow_pair);
   static const bool keep_on = !(getenv("OFFT_KEEP_STORES") && atoi(getenv("OFFT_KEEP_STORES")) == 0);
-  if (v && d->out_keep && keep_on && !v->mixed && !v->r2c) {
+  if (v && d->out_keep && keep_on && !v->mixed && !v->r2c && !v->c2r) {
     Variant *k = find_variant(v->n, v->prec, v->inc, v->outc, v->id, false, true);
     if (k && k->keep && k->id == v->id) return k;
   }
@@ -944,7 +960,8 @@ int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, 
 //       gather x[j] a[j] into U[line][0..M) (zero padded) | FFT_M | times B^ | FFT_M^-1 | scatter a[k] U[line][k], k < n
 //     with the library's own M-point path (a panel kernel or the four-step decomposition) on contiguous lines;
 //   * a real-input line too long for the r2c kernels is gathered as complex, transformed by the complex path of the same
-//     length, and its first n/2 + 1 outputs scattered.
+//     length, and its first n/2 + 1 outputs scattered; a real-output line (c2r) is gathered as the conjugate-symmetric
+//     extension of its n/2 + 1 values, and the real parts of the n outputs scattered.
 // Seven (three) sweeps over scratch lines of twice the length: a few per cent of the roofline -- it exists so that no
 // grid the reference accepts is refused, not to be fast.
 // ---------------------------------------------------------------------------
@@ -975,8 +992,12 @@ long_gather_k(GenArgs a, const typename vec2<T>::type *in, typename vec2<T>::typ
   V2 x; x.x = 0; x.y = 0;
   if (j < a.n) {
     const V2 *src = in + (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)c * a.in_col;
-    if (a.real_in) x.x = reinterpret_cast<const T *>(src)[j];
-    else x = src[split_off(j, a.in_split, a.in_nfloor, a.in_blk, a.in_axis, a.in_tab)];
+    if (a.real_in == 1) x.x = reinterpret_cast<const T *>(src)[j];
+    else if (a.real_in == 2) {  // real output: the conjugate-symmetric extension of the n/2+1 stored values
+      const bool lo = 2 * j <= a.n;
+      x = src[split_off(lo ? j : a.n - j, a.in_split, a.in_nfloor, a.in_blk, a.in_axis, a.in_tab)];
+      if (!lo) x.y = -x.y;
+    } else x = src[split_off(j, a.in_split, a.in_nfloor, a.in_blk, a.in_axis, a.in_tab)];
     if (a.conj) x.y = -x.y;
     if (chirp) { const V2 w = chirp[j]; V2 t; t.x = x.x * w.x - x.y * w.y; t.y = x.x * w.y + x.y * w.x; x = t; }
   }
@@ -1010,7 +1031,8 @@ long_scatter_k(GenArgs a, const typename vec2<T>::type *U, typename vec2<T>::typ
   o.x = x.x * (T)a.scale;
   o.y = (a.conj ? -x.y : x.y) * (T)a.scale;
   V2 *dst = out + (long long)b1 * a.out_b1 + (long long)b2 * a.out_b2 + (long long)c * a.out_col;
-  dst[split_off(k, a.out_split, a.out_nfloor, a.out_blk, a.out_axis, a.out_tab)] = o;
+  if (a.real_in == 2) reinterpret_cast<T *>(dst)[k] = o.x;  // real output: n reals at the head of the row
+  else dst[split_off(k, a.out_split, a.out_nfloor, a.out_blk, a.out_axis, a.out_tab)] = o;
 }
 
 int long_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const LongTab &lt);
@@ -1035,7 +1057,7 @@ int offt_hipk_variant_count(int n, int precision) {
   std::call_once(g_reg_once, build_registry);
   int c = 0;
   for (auto &v : registry())
-    if (v.n == n && v.prec == precision && v.inc && v.outc && !v.r2c && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
+    if (v.n == n && v.prec == precision && v.inc && v.outc && !v.r2c && !v.c2r && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
   return c;
 }
 
@@ -1056,11 +1078,22 @@ const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
   const Variant *v = pick_variant(d);
   BlueTab bt;
   if (!v) return (!d->real_input && blue_lookup(d->n, d->precision, &bt) && find_blue(bt.m, d->precision, d->in_contig != 0, d->out_contig != 0)) ? "fft_bluestein_k" : "fft_mixed_k";
+  if (v->c2r) return v->mixed ? "fft_c2r_panelx_k" : "fft_c2r_panel_k";
   return v->mixed ? "fft_panelx_k" : (v->prec == OFFT_PREC_F32_PAIR ? "fft_panel_k<pairs>" : "fft_panel_k");
 }
 
 int offt_hipk_prepare(int n, int precision) {
+  const bool c2r = (precision & OFFT_HIPK_PREP_C2R) != 0;
+  precision &= ~OFFT_HIPK_PREP_C2R;
   if (n < 1) { snprintf(g_err, sizeof g_err, "offt_hipk_prepare: bad n=%d", n); return -1; }
+  if (c2r) {
+    if (offt_hipk_prepare(n, precision)) return -1;
+    // real-output instances for a length whose panel kernel was compiled at plan time (the precompiled lengths have theirs);
+    // best effort like the complex ones: without them the real-output pass runs on the any-length kernel
+    const Variant *v = find_variant(n, precision, true, true, -1);
+    if (v && v->modfn && rtc_enabled()) (void)rtc_build(n, precision, true);
+    return 0;
+  }
   Tables tb;
   if (get_tables(n, precision, tb, true)) return -1;
   // a 31-smooth length of 256 .. 4096 points without a precompiled panel kernel gets one now (best effort)
@@ -1202,11 +1235,17 @@ int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void 
   BlueTab bt;
   BlueVariant *bv = nullptr;
   if (!v && !d->real_input && blue_lookup(d->n, d->precision, &bt)) bv = find_blue(bt.m, d->precision, d->in_contig != 0, d->out_contig != 0);
-  // a REAL-input line of a Bluestein length: gathered as complex lines into scratch, transformed there by the Bluestein
-  // panel kernel, the first n/2 + 1 outputs scattered -- three sweeps, against a radix of the size of its largest prime
+  // a REAL-input (or real-output) line of a Bluestein length: gathered as complex lines into scratch, transformed there by
+  // the Bluestein panel kernel, the first n/2 + 1 outputs (the n real parts) scattered -- three sweeps, against a radix of the size of its largest prime
   // factor on the any-length kernel (OFFT_R2C_BLUESTEIN=0: that kernel, as in rounds 1-2)
   static const bool r2c_blue = !(getenv("OFFT_R2C_BLUESTEIN") && atoi(getenv("OFFT_R2C_BLUESTEIN")) == 0);
   if (!v && d->real_input && r2c_blue && blue_lookup(d->n, d->precision, &bt) && find_blue(bt.m, d->precision, true, true)) {
+    LongTab plain;
+    return long_pass(d, in, out, stream, plain);
+  }
+  // a real-output line of a length beyond the any-length kernel whose descriptor no panel kernel takes (8192 points with
+  // blocks fft_panel_k cannot address): through scratch lines, like the four-step route of such a line
+  if (!v && d->real_input == 2 && 2 * (size_t)d->n * (d->precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2)) > (size_t)160 * 1024) {
     LongTab plain;
     return long_pass(d, in, out, stream, plain);
   }
@@ -1345,7 +1384,7 @@ namespace {
 int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const FourStep &fs) {
   const int N = d->n, N1 = fs.n1, N2 = fs.n2;
   const size_t esz = d->precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
-  if (d->real_input) { LongTab plain; return long_pass(d, in, out, stream, plain); }  // gathered as complex lines, first n/2 + 1 outputs scattered
+  if (d->real_input) { LongTab plain; return long_pass(d, in, out, stream, plain); }  // gathered as complex lines (see long_pass)
   // a per-peer split must cut the axis where the decomposition can follow it: whole runs of n2 inputs / n1 outputs.  One that
   // does not (uneven blocks) sends the lines through scratch: gathered with the split, transformed as contiguous lines
   if ((d->in_split && (d->in_split_nfloor || d->in_split % N2)) || (d->out_split && (d->out_split_nfloor || d->out_split % N1))) {
@@ -1464,7 +1503,7 @@ int long_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, 
   g.scale = d->scale;
   g.in_tab = d->in_split ? d->in_block_tab : nullptr;
   g.out_tab = d->out_split ? d->out_block_tab : nullptr;
-  const int kend = d->real_input ? N / 2 + 1 : N;
+  const int kend = d->real_input == 1 ? N / 2 + 1 : N;
   const long long nlines = (long long)d->ncols * d->nb1 * d->nb2;
   long long per = (long long)(((size_t)256 << 20) / ((size_t)M * esz));
   if (per < 1) per = 1;

@@ -264,12 +264,17 @@ __device__ __forceinline__ int padidx(int i) {
   else return i + (i >> SHIFT);
 }
 
-template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C = false,
-          bool KEEP = false /* stores with the default cache policy: the next launch re-reads the output (out_keep) */,
-          bool TW4 = false /* four-step lines (offt_kernels.hip): the twiddles w_n^(j2 k1) of the long length ride on the stores */>
-__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
-fft_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
-            const typename vec2<T>::type *twq) {
+// The body of fft_panel_k and fft_c2r_panel_k (below).  The kernels are thin __global__ wrappers so that the complex and
+// real-input instances keep their symbols (a template parameter added to fft_panel_k itself, defaulted or not, would be
+// part of every instance's mangled name): profiles/ and the rocprof matching of tools/ rely on them.
+//   R2C  real-input z pass (offt_pass_desc::real_input = 1)
+//   KEEP stores with the default cache policy: the next launch re-reads the output (out_keep)
+//   TW4  four-step lines (offt_kernels.hip): the twiddles w_n^(j2 k1) of the long length ride on the stores
+//   C2R  real-output z pass (offt_pass_desc::real_input = 2): n/2+1 complex inputs, n real outputs
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool KEEP, bool TW4,
+          bool C2R>
+__device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
+                                           const typename vec2<T>::type *twq) {
   using V2 = typename vec2<T>::type;
   using S = typename lanes<T>::scalar;
   constexpr int NL = lanes<T>::n;   // memory columns per lane (2: column pairs)
@@ -284,6 +289,7 @@ fft_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type
   static_assert(E % R0 == 0 && E % R1 == 0 && E % R2 == 0 && N % E == 0, "bad E");
   static_assert(!(PAIR && R2C), "column pairs: complex input only");
   static_assert(!(PAIR && TW4), "four-step twiddles: one column per lane");
+  static_assert(!(PAIR && C2R) && !(R2C && C2R) && !(TW4 && C2R) && (!C2R || OUTC), "real output: one column per lane, contiguous rows");
 
   extern __shared__ __align__(16) unsigned char smem[];
   T *exs = reinterpret_cast<T *>(smem);
@@ -335,17 +341,35 @@ fft_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type
     const int mask = (int)((1u << a.in_shift) - 1u);
     // TAB: the blocks of the split come from a table of element offsets (in_block_tab) instead of blk * in_blk; block
     // index and offset of n = j + cn are still the sums of those of j and cn, so the lookup index is (j >> shift) + (cn >> shift)
-    auto load_all = [&](auto tabbed) {
-      constexpr bool TAB = decltype(tabbed)::value;
+    // PLAIN (C2R only): no split on the input side
+    auto load_all = [&](auto tabbed, auto plain) {
+      constexpr bool TAB = decltype(tabbed)::value, PLAIN = decltype(plain)::value;
       const int jb = j >> a.in_shift;
       const V2 *p0 = src + (TAB ? 0LL : (long long)jb * a.in_blk) + (long long)(j & mask) * a.in_axis;
+      const V2 *pm = src - (long long)j * a.in_axis;  // (C2R, PLAIN: mirrored index N - j - cn = -j + a uniform N - cn)
       static_for<0, E>([&](auto ii) {
         constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
         constexpr int cn = u * TPL + t * (N / R0);
         const int n = j + cn;
         V2 val;
         val.x = 0; val.y = 0;
-        if constexpr (R2C) {
+        if constexpr (C2R) {
+          // the conjugate-symmetric extension of the n/2+1 stored values: element n is X[n] for n <= N/2 and conj(X[N - n])
+          // above, then conj-in as for any inverse line.  The mirrored half re-reads values that this workgroup loads for
+          // its own half as well (default cache policy, so that the second read is an L2 hit, not HBM traffic).  Without a
+          // split the address is a per-lane base plus a uniform offset for either half; with one, block and offset of
+          // N - n are not sums of per-lane and uniform parts, so they are computed per element.
+          const bool lo = n <= N / 2;
+          const int m = lo ? n : N - n;
+          const V2 *p;
+          if constexpr (PLAIN) p = lo ? p0 + (long long)cn * a.in_axis : pm + (long long)(N - cn) * a.in_axis;
+          else {
+            const int blk = m >> a.in_shift;
+            p = src + (TAB ? a.in_tab[blk] : (long long)blk * a.in_blk) + (long long)(m & mask) * a.in_axis;
+          }
+          if (valid) val = *p;
+          v[decltype(ii)::value] = cx<T>{val.x, xor_sign(val.y, lo ? conj_mask : conj_mask ^ 0x80000000u)};
+        } else if constexpr (R2C) {
           // n real values at the head of the row: element n is the n-th T of the row
           if constexpr (!PAIR) {
             if (valid) val.x = reinterpret_cast<const T *>(src)[n];
@@ -372,8 +396,14 @@ fft_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type
         }
       });
     };
-    if (a.in_tab) load_all(std::true_type{});
-    else load_all(std::false_type{});
+    if constexpr (C2R) {
+      if (!a.in_split) load_all(std::false_type{}, std::true_type{});
+      else if (a.in_tab) load_all(std::true_type{}, std::false_type{});
+      else load_all(std::false_type{}, std::false_type{});
+    } else {
+      if (a.in_tab) load_all(std::true_type{}, std::false_type{});
+      else load_all(std::false_type{}, std::false_type{});
+    }
   }
 
   // ---------------- stages ---------------------------------------------------
@@ -537,6 +567,10 @@ fft_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type
               if constexpr (KEEP) { if (valid) *reinterpret_cast<f32x4 *>(p0 + off) = q; }
               else { if (valid) __builtin_nontemporal_store(q, reinterpret_cast<f32x4 *>(p0 + off)); }
             }
+          } else if constexpr (C2R) {
+            // n reals at the head of the row (out_axis_stride = 1, no split): the real part of the line, scaled
+            if (valid) __builtin_nontemporal_store(x.x * sc, reinterpret_cast<T *>(dst) + n);
+            (void)off;
           } else {
             V2 w;
             w.x = x.x * sc;
@@ -549,6 +583,20 @@ fft_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type
       else store_all(std::false_type{});
     }
   });
+}
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C = false,
+          bool KEEP = false, bool TW4 = false>
+__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twq) {
+  panel_body<T, N, E, R0, R1, R2, COLS, INC, OUTC, SPLIT, R2C, KEEP, TW4, false>(a, in, out, twq);
+}
+
+// real-output z pass: contiguous rows on the store side, either flavour on the load side
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool SPLIT>
+__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_c2r_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twq) {
+  panel_body<T, N, E, R0, R1, R2, COLS, INC, true, SPLIT, false, false, false, true>(a, in, out, twq);
 }
 
 // ---------------------------------------------------------------------------
@@ -701,10 +749,10 @@ struct PanelXCfg {
   static constexpr int WPS_E = WPS < WPS_REG ? (WPS < WPS_MIN ? WPS_MIN : WPS) : (WPS_REG < WPS_MIN ? WPS_MIN : WPS_REG);
 };
 
-template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C = false>
-__global__ void __launch_bounds__(TPL * COLS, (PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
-fft_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
-             const typename vec2<T>::type *twt) {
+// the body of fft_panelx_k and fft_c2r_panelx_k (thin wrappers below, see panel_body)
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool C2R>
+__device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
+                                            const typename vec2<T>::type *twt) {
   using V2 = typename vec2<T>::type;
   using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
   constexpr int NT = Cfg::NT, NSTAGE = Cfg::NSTAGE, LSTRIDE = Cfg::LSTRIDE, EMAX = Cfg::EMAX;
@@ -712,6 +760,7 @@ fft_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::typ
   static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
   static_assert(smooth235(R0) && smooth235(R1) && smooth235(R2), "radices must be products of primes <= 13, or primes <= 31");
   static_assert(R0 <= 32 && R1 <= 32 && R2 <= 32, "register radix <= 32");
+  static_assert(!(R2C && C2R) && (!C2R || OUTC), "real output: contiguous rows");
 
   extern __shared__ __align__(16) unsigned char smem[];
   T *exs = reinterpret_cast<T *>(smem);
@@ -754,7 +803,13 @@ fft_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::typ
         const bool live = valid && ((u + 1) * TPL <= NBF || q < NBF);
         V2 val;
         val.x = 0; val.y = 0;
-        if constexpr (R2C) {
+        if constexpr (C2R) {
+          // conjugate-symmetric extension of the n/2+1 stored values, then conj-in (see fft_panel_k)
+          const bool lo = n <= N / 2;
+          if (live)
+            val = src[split_offset<decltype(has_split)::value>(lo ? n : N - n, a.in_split, a.in_inv, a.in_nfloor, a.in_lim, a.in_inv1, a.in_blk, a.in_axis, a.in_tab)];
+          v[decltype(ii)::value] = cx<T>{val.x, ((a.conj != 0) == lo) ? -val.y : val.y};
+        } else if constexpr (R2C) {
           if (live) val.x = reinterpret_cast<const T *>(src)[n];
           v[decltype(ii)::value] = cx<T>{val.x, (T)0};
         } else {
@@ -880,7 +935,9 @@ fft_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::typ
           w.x = x.x * sc;
           w.y = (a.conj ? -x.y : x.y) * sc;
           const bool live = valid && ((u + 1) * TPL <= NBF || q < NBF);
-          if (live && (!R2C || n <= N / 2))
+          if constexpr (C2R) {
+            if (live) __builtin_nontemporal_store(w.x, reinterpret_cast<T *>(dst) + n);
+          } else if (live && (!R2C || n <= N / 2))
             gstore(&dst[split_offset<decltype(has_split)::value>(n, a.out_split, a.out_inv, a.out_nfloor, a.out_lim, a.out_inv1, a.out_blk, a.out_axis, a.out_tab)], w);
         });
       };
@@ -888,6 +945,18 @@ fft_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::typ
       else store_all(std::false_type{});
     }
   });
+}
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C = false>
+__global__ void __launch_bounds__(TPL * COLS, (PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twt) {
+  panelx_body<T, N, TPL, R0, R1, R2, COLS, INC, OUTC, SPLIT, R2C, false>(a, in, out, twt);
+}
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_c2r_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twt) {
+  panelx_body<T, N, TPL, R0, R1, R2, COLS, INC, true, SPLIT, false, true>(a, in, out, twt);
 }
 
 // ---------------------------------------------------------------------------
@@ -909,6 +978,7 @@ struct Variant {
   void *modfn;      // hipFunction_t of an instance compiled at plan time (hipRTC), launched instead of fn
   bool keep = false;  // KEEP instantiation (offt_pass_desc::out_keep): default-policy stores
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
+  bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
 // (uneven, or not a power of two: grids split over 3, 6, ... ranks)
@@ -937,6 +1007,15 @@ void reg_variant(int id, int defmask = -1) {
   // real-input z pass: only the contiguous-read flavours of the default variant need it
   if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, true>, true);
   if (defmask & F_CS) add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, true>, true);
+  // real-output z pass (the mirror image): only the contiguous-write flavours of the default variant
+  if (defmask & F_CC) {
+    add(true, true, F_CC, (const void *)fft_c2r_panel_k<T, N, E, R0, R1, R2, COLS, true, SPLIT>);
+    registry().back().c2r = true;
+  }
+  if (defmask & F_SC) {
+    add(false, true, F_SC, (const void *)fft_c2r_panel_k<T, N, E, R0, R1, R2, COLS, false, SPLIT>);
+    registry().back().c2r = true;
+  }
   // cache-keeping stores (out_keep): the contig-in / strided-out default, i.e. the y pass of the z-y-x schedules ...
   if (defmask & F_CS) {
     add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, false, true>);
@@ -1011,13 +1090,25 @@ void reg_variantx(int id, int defmask = -1) {
   if constexpr ((FLAV & F_CC) != 0) {
     add(true, true, F_CC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT>);
     if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT, true>, true);
+    // (real output: also the any-split instances of the power-of-two lengths, so that the inverse's z pass of a grid split
+    //  over 3, 5, 6 ... ranks runs here rather than on the any-length kernel)
+    if ((defmask & F_CC) || id == VARIANT_ANYSPLIT) {
+      add(true, true, F_CC, (const void *)fft_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, SPLIT>);
+      registry().back().c2r = true;
+    }
   }
   if constexpr ((FLAV & F_SS) != 0) add(false, false, F_SS, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, false, SPLIT>);
   if constexpr ((FLAV & F_CS) != 0) {
     add(true, false, F_CS, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT>);
     if (defmask & F_CS) add(true, false, F_CS, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT, true>, true);
   }
-  if constexpr ((FLAV & F_SC) != 0) add(false, true, F_SC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, true, SPLIT>);
+  if constexpr ((FLAV & F_SC) != 0) {
+    add(false, true, F_SC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, true, SPLIT>);
+    if ((defmask & F_SC) || id == VARIANT_ANYSPLIT) {
+      add(false, true, F_SC, (const void *)fft_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, SPLIT>);
+      registry().back().c2r = true;
+    }
+  }
 }
 
 // instantiation groups (offt_reg_*.hip)
