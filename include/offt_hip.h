@@ -61,6 +61,21 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
  * row's Nz reals are undefined afterwards.  offt_hip_set_output_scale applies to the
  * z pass, which runs last. */
 void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int direction);
+/* spectral convolution, in place: `data` (device memory) holds this rank's block in the INPUT layout
+ * (istart/isize/istride; real rows for an r2c plan) and receives  scale * N * ifftn(H * fftn(x))  (complex plan) or
+ * scale * N * irfftn(H * rfftn(x), s=(Nx,Ny,Nz))  (r2c plan) in the same layout, N = Nx*Ny*Nz, scale =
+ * offt_hip_set_output_scale (applied once, on the final store).  `filter` (device memory) holds H for this rank's part of
+ * the spectrum, laid out exactly like the forward's OUTPUT block (ostart/osize/ostride, offsets in complex elements; the
+ * Nz/2+1 half spectrum for r2c plans): one complex value per element, or (REAL) one scalar of the plan's precision per
+ * complex slot, at the same element index.  The forward transform of a kernel g with the same plan is such an H.
+ * Collective on several ranks; honours offt_hip_set_stream / offt_hip_set_async like offt_3d_execute_dir.  0 on success;
+ * -1 with t[ALL] = 99999999 and offt_hip_last_error() on failure, and for a NULL or host-memory filter, host-memory data or
+ * an unknown filter_kind.  offt_hip_last_device_seconds covers the whole call; offt_hip_last_pass_seconds reports zeros. */
+#define OFFT_HIP_FILTER_REAL    0   /* one scalar of the plan's precision per spectrum element */
+#define OFFT_HIP_FILTER_COMPLEX 1   /* one complex value per spectrum element                  */
+int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *filter, int filter_kind);
+/* 1 if this plan's convolve runs the fused route (one launch for forward-pass . filter . inverse-pass), 0 otherwise */
+int offt_hip_convolve_fused(const struct _offt_plan *po);
 /* run on a caller-owned hipStream_t (NULL = the plan's own stream)             */
 void offt_hip_set_stream(struct _offt_plan *po, void *stream);
 /* 0: offt_3d_execute returns after the GPU finished (timers valid, reference

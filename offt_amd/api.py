@@ -21,6 +21,7 @@ PARAM_NAMES = ["P1", "T1", "W1", "Px1", "Py1", "Fz", "FP1", "Ux1", "Uz1", "FU1",
  TRANSPOSE, PACK1, UNPACK1, PACK2, UNPACK2) = range(GES)
 FFTW_ESTIMATE = 1 << 6
 F64, F32 = 0, 1
+FILTER_REAL, FILTER_COMPLEX = 0, 1  # offt_hip.h OFFT_HIP_FILTER_REAL / OFFT_HIP_FILTER_COMPLEX
 
 
 class OfftParams(C.Structure):
@@ -91,6 +92,10 @@ def bind(L):
     L.offt_3d_execute_dir.argtypes = [PP, C.c_void_p, C.c_void_p, i]
     L.offt_3d_fin.restype = None
     L.offt_3d_fin.argtypes = [PP]
+    L.offt_hip_execute_convolve.restype = i
+    L.offt_hip_execute_convolve.argtypes = [PP, C.c_void_p, C.c_void_p, i]
+    L.offt_hip_convolve_fused.restype = i
+    L.offt_hip_convolve_fused.argtypes = [PP]
     L.print_params.restype = None
     L.print_params.argtypes = [C.POINTER(C.c_int)]
     L.offt_print_time.restype = None
@@ -176,6 +181,19 @@ def offt_3d_execute_dir(po, inp, out, direction):
     L.offt_3d_execute_dir(po, inp, out, direction)
     if po.contents.t[ALL] >= 99999999.0:
         raise RuntimeError("offt_3d_execute_dir failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_execute_convolve(po, data, filt, filter_kind=FILTER_REAL):
+    """in-place spectral convolution of this rank's block (input layout) with the filter H (device memory, laid out like
+    the forward's output block): scale * N * ifftn(H * fftn(x)), irfftn / rfftn for r2c plans (include/offt_hip.h)"""
+    L = lib()
+    if L.offt_hip_execute_convolve(po, data, filt, filter_kind) != 0:
+        raise RuntimeError("offt_hip_execute_convolve failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_convolve_fused(po):
+    """True if the plan's convolve runs the fused route (one launch for forward pass . filter . inverse pass)"""
+    return lib().offt_hip_convolve_fused(po) == 1
 
 
 def offt_3d_fin(po):

@@ -51,6 +51,12 @@ typedef struct offt_backend {
   /* offt_hipk_flag_signal / offt_hipk_flag_wait (offt_hipk.h) */
   int (*flag_signal)(int n, unsigned long long *const *addr, unsigned long long value, void *stream);
   int (*flag_wait)(int n, unsigned long long *const *addr, unsigned long long value, unsigned long long *status, double timeout_s, void *stream);
+  /* ---- spectral convolution (offt_hip_execute_convolve) ----
+   * conv_pass: offt_hipk_conv_pass -- the fused forward-pass . filter . inverse-pass launch; NULL: every convolve takes
+   * the unfused route.  pointwise: offt_hipk_pointwise -- the multiply of that route; NULL: convolve is refused. */
+  int (*conv_pass)(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, void *data, void *stream);
+  int (*pointwise)(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0, long long s1,
+                   long long s2, void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);

@@ -101,6 +101,28 @@ const char *offt_hipk_variant_name(int n, int precision, int variant);
 int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thread, int *cols);
 /* name of the kernel symbol a descriptor resolves to (for rocprof matching)    */
 const char *offt_hipk_kernel_name(const offt_pass_desc *d);
+/* ---- spectral convolution (offt_hip_execute_convolve) ------------------------------------------------------------------
+ * A filter H laid out like a forward pass's OUTPUT: kind 0 = one real scalar of the pass's precision per complex slot
+ * (scalar index = element index), 1 = one complex value per element.  Strides in complex elements. */
+#define OFFT_FILTER_REAL 0
+#define OFFT_FILTER_COMPLEX 1
+typedef struct offt_filter_desc {
+  int kind;
+  long long axis_stride, col_stride, b1_stride, b2_stride;
+} offt_filter_desc;
+/* One fused launch on the lines of `fwd` (the last pass of a forward transform): load through its in_* side, forward FFT,
+ * times H read where the pass would store (f), inverse FFT (unnormalised), times fwd->scale, store through the same in_*
+ * addressing -- in place on `data`.  fwd->out_keep: stores with the default cache policy.  -1 if no fused kernel exists. */
+int offt_hipk_conv_pass(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, void *data, void *stream);
+/* 1 if offt_hipk_conv_pass has a fused kernel for (fwd, f): power-of-two lines of 64 ... 1024 points, contiguous lines
+ * (in_contig, no split, complex input) and a unit-stride filter axis; the registry lookup needs no device */
+int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f);
+/* "fft_conv_panel_k", or "no fused kernel" (rocprof matching, tests) */
+const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f);
+/* data[i0 s0 + i1 s1 + i2 s2] *= H at the same element index, over the box n0 x n1 x n2 (complex elements, in place);
+ * kind as offt_filter_desc::kind.  Non-temporal, 16 B per lane along the smallest stride. */
+int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2,
+                        long long s0, long long s1, long long s2, void *stream);
 /* strided complex copy / permutation (used for layouts no FFT pass can fold)   */
 int offt_hipk_copy3d(const void *in, void *out, int precision,
                      int n0, int n1, int n2,

@@ -646,10 +646,21 @@ static int hb_flag_wait(int n, unsigned long long *const *addr, unsigned long lo
   if (rc) SET_ERR("flag wait failed: %s", offt_hipk_last_error());
   return rc;
 }
+static int hb_conv_pass(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, void *data, void *stream) {
+  const int rc = offt_hipk_conv_pass(fwd, f, filter, data, stream);
+  if (rc) SET_ERR("fused convolution pass n=%d failed: %s", fwd->n, offt_hipk_last_error());
+  return rc;
+}
+static int hb_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0, long long s1,
+                        long long s2, void *stream) {
+  const int rc = offt_hipk_pointwise(data, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
+  if (rc) SET_ERR("pointwise multiply failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
-    hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait};
+    hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise};
 
 /* ------------------------------------------------------------------------- */
 /* helpers                                                                    */
@@ -1640,16 +1651,24 @@ void offt_hip_last_pass_seconds(const struct _offt_plan *po, double t[3]) {
 /* single-rank direct path: three panel passes, transposes folded into the    */
 /* x pass (replaces phase1 + setup_transpose + phase2 at p = 1)               */
 /* ------------------------------------------------------------------------- */
-static int execute_single(struct _offt_plan *po, void *data, int dir) {
+/* the three launches of a single-rank transform in direction `dir` (descriptors, buffers, timer slots), and which schedule
+ * they belong to; execute_single runs them, execute_convolve_single (spectral convolution) takes them apart */
+typedef struct single_sched {
+  offt_pass_desc d[3];
+  const void *src[3];
+  void *dst[3];
+  int slot[3];
+  int S, zyx, yzx_rot, s1_rot, c2r;
+} single_sched;
+
+static void single_schedule(struct _offt_plan *po, void *data, int dir, single_sched *ss) {
   hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
   const struct _offt_comm *c = po->comm;
   /* Nzf = length of the z transform; Nz = number of z values kept afterwards
    * (Nz/2+1 for real-to-complex, offt-compute.c:63) -- every extent and stride below uses Nz */
   const int Nx = po->Nx, Ny = po->Ny, Nzf = po->Nz, Nz = po->is_r2c ? po->Nz / 2 + 1 : po->Nz;
   const long long is0 = c->istride[0], is1 = c->istride[1];
   const long long os0 = c->ostride[0], os1 = c->ostride[1], os2 = c->ostride[2];
-  void *s = st->s_compute;
   void *W = st->work;
   /* complex-to-real inverse (is_r2c, dir > 0): the same schedules, the z pass last, as a real-output pass (real_input = 2)
    * that reads the Nz/2+1 complex values of a line and writes Nz reals at the head of its row */
@@ -1845,6 +1864,23 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
     }
   }
   d[2].scale = st->out_scale; /* last launch */
+  memcpy(ss->d, d, sizeof d);
+  for (int i = 0; i < 3; i++) { ss->src[i] = src[i]; ss->dst[i] = dst[i]; ss->slot[i] = slot[i]; }
+  ss->S = S; ss->zyx = zyx; ss->yzx_rot = yzx_rot; ss->s1_rot = s1_rot; ss->c2r = c2r;
+}
+
+static int execute_single(struct _offt_plan *po, void *data, int dir) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const int Nx = po->Nx, Ny = po->Ny, Nzf = po->Nz, Nz = po->is_r2c ? po->Nz / 2 + 1 : po->Nz;
+  void *s = st->s_compute;
+  single_sched ss;
+  single_schedule(po, data, dir, &ss);
+  offt_pass_desc *d = ss.d;
+  const void *const *src = ss.src;
+  void *const *dst = ss.dst;
+  const int *slot = ss.slot;
+  const int S = ss.S, zyx = ss.zyx, yzx_rot = ss.yzx_rot, s1_rot = ss.s1_rot, c2r = ss.c2r;
   for (int i = 0; i < 3; i++) st->pass_slot[i] = slot[i];
   /* Forward z-y-x: the y pass writes out[z][y][x] plane by plane and the x pass transforms those planes in place, so
    * the two ALTERNATE over groups of z-planes small enough for the 256 MiB memory-side Infinity Cache: y(group) stores
@@ -2804,6 +2840,166 @@ void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int directi
   }
   if (staged) HCHECK(hipMemcpy(out, st->stage, bytes, hipMemcpyDeviceToHost), { t[ALL] = 99999999.0; return; });
   t[ALL] = wall_seconds() - t0;
+}
+
+/* ------------------------------------------------------------------------- */
+/* spectral convolution: forward, filter, inverse in one call                 */
+/* ------------------------------------------------------------------------- */
+/* The single-rank fused route: the forward's first two launches, ONE launch for the forward's last pass + the filter + the
+ * inverse's first pass (they work on the same lines: the caller's array in z-y-x, the scratch volume V in the rotated
+ * y-z-x layout), the inverse's last two launches.  *fd receives the fused launch's descriptor (the forward's last pass;
+ * loads and stores through its input side) and *fl the filter's addressing (that pass's output side).  0: this plan and
+ * backend have no fused route (the caller takes the unfused one). */
+static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, offt_pass_desc *fd,
+                            offt_filter_desc *fl) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_pass_desc *l = &fw->d[2], *f0 = &iv->d[0];
+  if (st->use_pipeline || !st->be->conv_pass) return 0;
+  *fd = *l;
+  fd->scale = 1.0;
+  fd->out_keep = 0;
+  memset(fl, 0, sizeof *fl);
+  fl->kind = kind;
+  fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
+  fl->b1_stride = l->out_b1_stride; fl->b2_stride = l->out_b2_stride;
+  /* the inverse's first pass must store where the forward's last one loads, with the same addressing */
+  if (iv->dst[0] != fw->src[2] || f0->n != l->n || f0->ncols != l->ncols || f0->nb1 != l->nb1 || f0->nb2 != l->nb2 ||
+      f0->out_axis_stride != l->in_axis_stride || f0->out_col_stride != l->in_col_stride || f0->out_b1_stride != l->in_b1_stride ||
+      f0->out_b2_stride != l->in_b2_stride)
+    return 0;
+  return offt_hipk_conv_has_fused(fd, fl);
+}
+
+static int execute_convolve_single(struct _offt_plan *po, void *data, const void *filter, int kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  void *s = st->s_compute;
+  single_sched fw, iv;
+  single_schedule(po, data, -1, &fw);
+  single_schedule(po, data, +1, &iv);
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  if (!conv_fused_route(po, &fw, &iv, kind, &fd, &fl)) return 1;
+  const size_t fesz = kind == OFFT_FILTER_COMPLEX ? st->esz : st->esz / 2; /* filter bytes per element */
+  /* z-y-x: the forward's y pass, the fused launch and the inverse's y pass all work on z-planes of the caller's array
+   * (nb1 = Nz, one z-plane per batch entry): they alternate over groups of planes that fit the Infinity Cache, as the y and
+   * x launches of a plain transform do (execute_single) -- y(group) keeps its stores, the fused launch re-reads and keeps,
+   * the inverse's y pass re-reads.  Same group size rule and option (OFFT_HIP_OPT_ZGROUP_MIB, 0 = plain launches). */
+  const offt_pass_desc *py = &fw.d[1], *qy = &iv.d[1];
+  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
+  int ng = 0;
+  if (fw.zyx && py->nb1 == cnt && fd.nb1 == cnt && qy->nb1 == cnt &&
+      (st->opt.zgroup_mib >= 0 || (po->Nx <= 1024 && po->Ny <= 1024 && (g_backend || offt_hipk_keeps_output(py))))) {
+    const int group_mib = st->opt.zgroup_mib >= 0 ? st->opt.zgroup_mib : 256;
+    const double plane_mib = (double)po->Nx * po->Ny * (double)st->esz / (1024.0 * 1024.0);
+    ng = group_mib > 0 ? (int)((double)group_mib / plane_mib) : 0;
+    if (ng > cnt) ng = cnt;
+  }
+  if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
+  if (ng >= 1) {
+    for (int z0 = 0; z0 < cnt; z0 += ng) {
+      const int g = cnt - z0 < ng ? cnt - z0 : ng;
+      offt_pass_desc a = *py, b = fd, q = *qy;
+      a.nb1 = b.nb1 = q.nb1 = g;
+      a.out_keep = b.out_keep = 1;
+      if (be->pass(&a, (const char *)fw.src[1] + (size_t)z0 * (size_t)a.in_b1_stride * st->esz,
+                   (char *)fw.dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * st->esz, s))
+        return -1;
+      if (be->conv_pass(&b, &fl, (const char *)filter + (size_t)z0 * (size_t)fl.b1_stride * fesz,
+                        (char *)fw.src[2] + (size_t)z0 * (size_t)b.in_b1_stride * st->esz, s))
+        return -1;
+      if (be->pass(&q, (const char *)iv.src[1] + (size_t)z0 * (size_t)q.in_b1_stride * st->esz,
+                   (char *)iv.dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * st->esz, s))
+        return -1;
+    }
+  } else {
+    if (be->pass(&fw.d[1], fw.src[1], fw.dst[1], s)) return -1;
+    if (be->conv_pass(&fd, &fl, filter, (void *)fw.src[2], s)) return -1;
+    if (be->pass(&iv.d[1], iv.src[1], iv.dst[1], s)) return -1;
+  }
+  return be->pass(&iv.d[2], iv.src[2], iv.dst[2], s) ? -1 : 0;
+}
+
+/* the multiply of the unfused route: this rank's output block (osize box, ostride addressing) times H */
+static int conv_pointwise(struct _offt_plan *po, void *data, const void *filter, int kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const struct _offt_comm *c = po->comm;
+  return st->be->pointwise(data, filter, st->prec, kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0], c->ostride[1],
+                           c->ostride[2], st->s_compute) ? -1 : 0;
+}
+
+int offt_hip_convolve_fused(const struct _offt_plan *po) {
+  if (!po || !po->hip_state) return 0;
+  single_sched fw, iv;
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  struct _offt_plan *p = (struct _offt_plan *)po;
+  if (((hip_state *)po->hip_state)->use_pipeline) return 0;
+  single_schedule(p, NULL, -1, &fw);
+  single_schedule(p, NULL, +1, &iv);
+  return conv_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, &fd, &fl);
+}
+
+int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *filter, int filter_kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  double *t = po->t;
+  memset(t, 0, GES * sizeof(double));
+  TEST_NOTE_MESH(po);
+  if (filter_kind != OFFT_HIP_FILTER_REAL && filter_kind != OFFT_HIP_FILTER_COMPLEX) {
+    SET_ERR("offt_hip_execute_convolve: unknown filter_kind %d (OFFT_HIP_FILTER_REAL or OFFT_HIP_FILTER_COMPLEX)", filter_kind);
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if (!filter || (!g_backend && !is_device_ptr(filter))) {
+    SET_ERR("offt_hip_execute_convolve: the filter must be device memory%s", filter ? "" : " (got NULL)");
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if (!data || (!g_backend && !is_device_ptr(data))) {
+    SET_ERR("offt_hip_execute_convolve: the data must be device memory (no host staging for a convolve)");
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if (!be->pointwise) {
+    SET_ERR("offt_hip_execute_convolve: this backend has no pointwise multiply");
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if ((st->uses_rccl || st->p2p) && G.comm_failed) {
+    SET_ERR("offt_hip_execute_convolve: the communicator failed earlier; make a new world (offt_hip_set_world) and plan");
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  const double t0 = wall_seconds();
+  const int timed = st->async ? 0 : 1;
+  st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros after a convolve */
+  if (timed) be->event_record(st->ev0, st->s_compute);
+  const double scale = st->out_scale;
+  int rc = st->use_pipeline ? 1 : execute_convolve_single(po, data, filter, filter_kind);
+  if (rc > 0) {
+    /* unfused: forward (unscaled), multiply on the stream the forward ends on, inverse (the output scale on its last store) */
+    st->out_scale = 1.0;
+    if (!st->use_pipeline) rc = execute_single(po, data, -1);
+    else rc = st->slab_zyx ? execute_slab(po, data) : execute_pipeline(po, data, -1);
+    st->out_scale = scale;
+    if (!rc) rc = conv_pointwise(po, data, filter, filter_kind);
+    if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, data) : execute_single(po, data, +1);
+  }
+  st->out_scale = scale;
+  st->yx_fused = 0;
+  if (timed) be->event_record(st->ev1, st->s_compute);
+  if (rc) {
+    if (st->uses_rccl) comm_fail(st);
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if (st->async) { t[ALL] = wall_seconds() - t0; return 0; }
+  if (wait_compute(st)) { t[ALL] = 99999999.0; return -1; }
+  st->last_dev_s = 1e-3 * be->event_ms(st->ev0, st->ev1);
+  for (int i = 0; i < 3; i++) st->pass_s[i] = 0.0;
+  t[ALL] = wall_seconds() - t0;
+  return 0;
 }
 
 /* asynchronous mode (offt_hip_set_async): wait for everything enqueued so far -- the same bounded, error-polling

@@ -296,6 +296,45 @@ copy3d_k(const V2 *in, V2 *out, int n0, int n1, int n2, long long is0, long long
   }
 }
 
+// pointwise multiply of a spectrum block by a filter at the same element index (offt_hipk_pointwise): rows along the
+// smallest stride, 16 B per lane (two single-precision elements when that stride is 1), non-temporal both ways --
+// every byte is touched once
+template <typename T, bool CPLX, int EPL>
+__global__ void __launch_bounds__(256)
+pointwise_k(typename vec2<T>::type *data, const void *filter, int n1, int n2, long long s0, long long s1, long long s2, long long rows) {
+  using V2 = typename vec2<T>::type;
+  const int i2 = (blockIdx.x * 256 + threadIdx.x) * EPL;
+  if (i2 >= n2) return;
+  for (long long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const long long i1 = r % n1, i0 = r / n1;
+    const long long o = i0 * s0 + i1 * s1 + (long long)i2 * s2;
+    if constexpr (EPL == 2) {  // (s2 == 1, n2 even, 16-B aligned rows: two float2 as one float4)
+      typedef float f4 __attribute__((ext_vector_type(4)));
+      typedef float f2v __attribute__((ext_vector_type(2)));
+      f4 x = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(data + o));
+      if constexpr (CPLX) {
+        const f4 h = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(reinterpret_cast<const V2 *>(filter) + o));
+        x = f4{x.x * h.x - x.y * h.y, x.x * h.y + x.y * h.x, x.z * h.z - x.w * h.w, x.z * h.w + x.w * h.z};
+      } else {
+        const f2v h = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(reinterpret_cast<const T *>(filter) + o));
+        x = f4{x.x * h.x, x.y * h.x, x.z * h.y, x.w * h.y};
+      }
+      __builtin_nontemporal_store(x, reinterpret_cast<f4 *>(data + o));
+    } else {
+      V2 x = gload(data + o);
+      if constexpr (CPLX) {
+        const V2 h = gload(reinterpret_cast<const V2 *>(filter) + o);
+        const T re = x.x * h.x - x.y * h.y, im = x.x * h.y + x.y * h.x;
+        x.x = re; x.y = im;
+      } else {
+        const T h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + o);
+        x.x *= h; x.y *= h;
+      }
+      gstore(data + o, x);
+    }
+  }
+}
+
 __device__ __forceinline__ double hash_val(int x, int y, int z, int c) {
   unsigned h = (unsigned)x * 73856093u ^ (unsigned)y * 19349663u ^ (unsigned)z * 83492791u ^
                (unsigned)c * 2654435761u;
@@ -363,6 +402,8 @@ void build_registry() {
   reg_mixed_f64_e();
   reg_mixed_f32_a();
   reg_mixed_f32_b();
+  reg_conv_f64();
+  reg_conv_f32();
   reg_bluestein_all();
 #endif
 }
@@ -372,21 +413,23 @@ void build_registry() {
 std::mutex g_idx_mu;
 std::unordered_map<unsigned long long, std::vector<int>> g_idx;
 size_t g_idx_size = 0;
-unsigned long long variant_key(int n, int prec, bool inc, bool outc, bool r2c, bool keep = false, bool tw4 = false, bool c2r = false) {
-  return ((unsigned long long)n << 8) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
+unsigned long long variant_key(int n, int prec, bool inc, bool outc, bool r2c, bool keep = false, bool tw4 = false, bool c2r = false,
+                               bool conv = false) {
+  return ((unsigned long long)n << 9) | (conv ? 256u : 0u) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
 }
 
-Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = false, bool keep = false, bool tw4 = false, bool c2r = false) {
+Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = false, bool keep = false, bool tw4 = false, bool c2r = false,
+                      bool conv = false) {
   std::call_once(g_reg_once, build_registry);
   std::lock_guard<std::mutex> lk(g_idx_mu);
   auto &reg = registry();
   if (g_idx_size != reg.size()) {
     g_idx.clear();
     for (size_t i = 0; i < reg.size(); ++i)
-      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r)].push_back((int)i);
+      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r, reg[i].conv)].push_back((int)i);
     g_idx_size = reg.size();
   }
-  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r));
+  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r, conv));
   if (it == g_idx.end()) return nullptr;
   Variant *def = nullptr;
   for (int i : it->second) {
@@ -728,7 +771,7 @@ int blue_m_long(int n, int prec) {
   if (!find_variant(n1, prec, false, false, -1, false, false, true)) return 0;
   long long best = 0;
   for (auto &v : registry()) {
-    if (v.prec != prec || !v.inc || !v.outc || v.r2c || v.c2r || v.tw4 || v.id != 0 || v.n < 64 || v.n > 4096) continue;
+    if (v.prec != prec || !v.inc || !v.outc || v.r2c || v.c2r || v.tw4 || v.conv || v.id != 0 || v.n < 64 || v.n > 4096) continue;
     const long long m = (long long)n1 * v.n;
     if (m >= need && m < (1LL << 24) && (!best || m < best)) best = m;
   }
@@ -1057,7 +1100,7 @@ int offt_hipk_variant_count(int n, int precision) {
   std::call_once(g_reg_once, build_registry);
   int c = 0;
   for (auto &v : registry())
-    if (v.n == n && v.prec == precision && v.inc && v.outc && !v.r2c && !v.c2r && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
+    if (v.n == n && v.prec == precision && v.inc && v.outc && !v.r2c && !v.c2r && !v.conv && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
   return c;
 }
 
@@ -1621,6 +1664,90 @@ int offt_hipk_flag_signal(int n, unsigned long long *const *addr, unsigned long 
 int offt_hipk_flag_wait(int n, unsigned long long *const *addr, unsigned long long value, unsigned long long *status, double timeout_s,
                         void *stream) {
   return flag_launch(true, n, addr, value, status, timeout_s, stream);
+}
+
+// ---- spectral convolution (offt_hipk.h) ----
+namespace {
+// the fused instance for (fwd, f), or nullptr: contiguous complex lines without a split, a unit-stride filter axis
+Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep) {
+  if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
+  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
+  if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || f->axis_stride != 1)
+    return nullptr;
+  Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true);
+  return v && v->conv && v->keep == keep ? v : nullptr;
+}
+}  // namespace
+
+int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false) != nullptr; }
+
+const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
+  return pick_conv(fwd, f, false) ? "fft_conv_panel_k" : "no fused kernel";
+}
+
+int offt_hipk_conv_pass(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream) {
+  Variant *v = pick_conv(d, f, d && d->out_keep);
+  if (!v && d && d->out_keep) v = pick_conv(d, f, false);
+  if (!v) { snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass: no fused convolution kernel for this descriptor (n=%d)", d ? d->n : 0); return -1; }
+  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  PassArgs a;
+  memset(&a, 0, sizeof a);
+  a.in_axis = d->in_axis_stride; a.in_col = d->in_col_stride; a.in_b1 = d->in_b1_stride; a.in_b2 = d->in_b2_stride;
+  a.in_shift = a.out_shift = 31;
+  a.ncols = d->ncols;
+  a.ncp = (d->ncols + v->cols - 1) / v->cols;
+  a.nb1 = d->nb1;
+  a.scale = d->scale;
+  ConvArgs fa;
+  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
+  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
+  const long long nblk = (long long)a.ncp * d->nb1 * d->nb2;
+  if (nblk > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass: grid too large"); return -1; }
+  xcd_order(nblk, &a.xcd_lim, &a.xcd_gshift);
+  void *args[] = {(void *)&a, (void *)&fa, (void *)&data, (void *)&filter, (void *)&tb.full};
+  if (!v->attr_set) {
+    if (v->lds > 48 * 1024) HIPK_CHECK(hipFuncSetAttribute(v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
+    v->attr_set = true;
+  }
+  HIPK_CHECK(hipLaunchKernel(v->fn, dim3((unsigned)nblk), dim3(v->threads), args, v->lds, (hipStream_t)stream));
+  return 0;
+}
+
+int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0, long long s1,
+                        long long s2, void *stream) {
+  if (kind != OFFT_FILTER_REAL && kind != OFFT_FILTER_COMPLEX) { snprintf(g_err, sizeof g_err, "offt_hipk_pointwise: bad filter kind %d", kind); return -1; }
+  if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
+  // rows along the smallest stride
+  int n[3] = {n0, n1, n2};
+  long long st[3] = {s0, s1, s2};
+  for (int a = 0; a < 2; a++)
+    for (int b = 0; b < 2 - a; b++)
+      if (st[b] < st[b + 1]) { int tn = n[b]; n[b] = n[b + 1]; n[b + 1] = tn; long long ts = st[b]; st[b] = st[b + 1]; st[b + 1] = ts; }
+  const long long rows = (long long)n[0] * n[1];
+  const bool f32 = precision == OFFT_PREC_F32;
+  // two single-precision elements per lane: unit stride, whole pairs, 16-B aligned rows and bases
+  const bool pair = f32 && st[2] == 1 && !(n[2] & 1) && !(st[1] & 1) && !(st[0] & 1) && !((uintptr_t)data & 15) &&
+                    !((uintptr_t)filter & (kind == OFFT_FILTER_COMPLEX ? 15 : 7));
+  const int epl = pair ? 2 : 1;
+  const unsigned gx = (unsigned)((n[2] / epl + 255) / 256);
+  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
+  hipStream_t sm = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const bool cx = kind == OFFT_FILTER_COMPLEX;
+  if (!f32) {
+    if (cx) hipLaunchKernelGGL((pointwise_k<double, true, 1>), dim3(gx, gy), dim3(256), 0, sm, (double2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
+    else hipLaunchKernelGGL((pointwise_k<double, false, 1>), dim3(gx, gy), dim3(256), 0, sm, (double2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
+  } else if (pair) {
+    if (cx) hipLaunchKernelGGL((pointwise_k<float, true, 2>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
+    else hipLaunchKernelGGL((pointwise_k<float, false, 2>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
+  } else {
+    if (cx) hipLaunchKernelGGL((pointwise_k<float, true, 1>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
+    else hipLaunchKernelGGL((pointwise_k<float, false, 1>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
+  }
+  HIPK_CHECK(hipGetLastError());
+  return 0;
 }
 
 int offt_hipk_copy3d(const void *in, void *out, int precision, int n0, int n1, int n2, long long is0,

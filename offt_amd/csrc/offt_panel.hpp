@@ -600,6 +600,262 @@ fft_c2r_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::
 }
 
 // ---------------------------------------------------------------------------
+// Spectral convolution of whole lines (offt_hipk_conv_pass): load a panel, forward stages, multiply every output by the
+// filter, conjugate, one LDS round trip back into the load distribution, the stages again (an inverse by conj-in /
+// conj-out), conjugate, scale, store where the lines came from.  The last pass of a forward 3-D transform and the first
+// pass of the inverse work on the same lines: one launch instead of two, and no sweep for the multiply.
+// Only the contiguous-line flavour (lanes along the line on both sides, no split, one column per lane): with it the
+// thread mapping (column c = tid / TPL, line offset j = tid % TPL) is the same in every stage, so the exchanges are those
+// of panel_body's contiguous / contiguous kernels.  In place: a workgroup owns whole lines and has loaded all of them
+// before its first exchange, i.e. before any of its stores.
+struct ConvArgs {
+  long long axis, col, b1, b2;  // filter strides in complex elements (the forward pass's store side)
+  int cplx;                     // 1: one complex value per element, 0: one real scalar per complex slot (same element index)
+};
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP>
+__device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter,
+                                          const typename vec2<T>::type *twq) {
+  using V2 = typename vec2<T>::type;
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int TPL = Cfg::TPL, NT = Cfg::NT, NSTAGE = Cfg::NSTAGE;
+  constexpr int LSTRIDE = Cfg::LSTRIDE;
+  constexpr bool SWZ = Cfg::SWZ;
+  constexpr int PS = SWZ ? Cfg::SWZSHIFT : Cfg::PADSHIFT;
+  static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
+  static_assert(E % R0 == 0 && E % R1 == 0 && E % R2 == 0 && N % E == 0, "bad E");
+  static_assert(NSTAGE > 1, "the round trip goes through the exchange image");
+  constexpr int RL = NSTAGE == 3 ? R2 : R1;  // radix of the last stage
+  constexpr int LRL = ilog2(RL);
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T *exs = reinterpret_cast<T *>(smem);
+  V2 *exv = reinterpret_cast<V2 *>(smem);
+  V2 *tw = reinterpret_cast<V2 *>(smem + Cfg::TW_OFF);
+  V2 *tw1 = reinterpret_cast<V2 *>(smem + Cfg::T1_OFF);
+
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Cfg::QT; i += NT) tw[i] = twq[i];
+  if constexpr (Cfg::USE_T1) {
+    constexpr int M1 = N / (R0 * R1);
+    for (int i = tid; i < Cfg::T1N; i += NT) {
+      const int t = i / R0 + 1, k = i - (t - 1) * R0;
+      tw1[i] = twq[k * M1 * t];
+    }
+  }
+
+  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const int cp = bid % (unsigned)a.ncp;
+  const unsigned rest = bid / (unsigned)a.ncp;
+  const int b1 = rest % (unsigned)a.nb1;
+  const int b2 = rest / (unsigned)a.nb1;
+  const int c0 = cp * COLS;
+  const int j = tid % TPL, c = tid / TPL;
+  const bool valid = (c0 + c) < a.ncols;
+  V2 *line = data + (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col + (long long)j * a.in_axis;
+  const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col + (long long)j * f.axis;
+
+  // a wave owns whole columns when TPL divides 64: its exchanges need no workgroup barrier (see panel_body)
+  constexpr bool WAVE_COLS = (64 % TPL == 0) && (NT % 64 == 0);
+  auto xsync = [&]() {
+    if constexpr (WAVE_COLS) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    } else {
+      __syncthreads();
+    }
+  };
+  auto at = [&](int i) { return c * LSTRIDE + padidx<SWZ, PS>(i); };
+
+  cx<T> v[E];
+  static_for<0, E>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+    constexpr int cn = u * TPL + t * (N / R0);
+    V2 val;
+    val.x = 0; val.y = 0;
+    if (valid) val = gload(line + (long long)cn * a.in_axis);
+    v[decltype(ii)::value] = cx<T>{val.x, val.y};
+  });
+
+  // the forward stages of panel_body (contiguous / contiguous), ending in the last stage's register order:
+  // v[u RL + bitrev(t)] holds line index j + u TPL + t N/RL
+  auto stages = [&]() {
+    static_for<0, NSTAGE>([&](auto sidx) {
+      constexpr int s = decltype(sidx)::value;
+      constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
+      constexpr int Ns = (s == 0) ? 1 : ((s == 1) ? R0 : R0 * R1);
+      constexpr int NB = E / R;
+      constexpr int LR = ilog2(R);
+      if constexpr (s > 0) {
+        constexpr int M = N / (Ns * R);
+        if constexpr (s == 1 && WAVE_COLS) __syncthreads();  // the twiddle tables staged at entry are visible
+        static_for<0, NB>([&](auto uu) {
+          constexpr int u = decltype(uu)::value;
+          const int q = j + u * TPL;
+          const int km = (q & (Ns - 1)) * M;
+          static_for<1, R>([&](auto tt) {
+            constexpr int t = decltype(tt)::value;
+            T cr, ci;
+            if constexpr (s == 1 && Cfg::USE_T1) {
+              const V2 w = tw1[(t - 1) * R0 + (q & (R0 - 1))];
+              cr = w.x; ci = w.y;
+            } else if constexpr (Cfg::USE_HALF) {
+              const int e = km * t;
+              const V2 w = tw[e & (N / 2 - 1)];
+              const unsigned sm = ((unsigned)e << (32 - ilog2(N))) & 0x80000000u;
+              cr = xor_sign(w.x, sm); ci = xor_sign(w.y, sm);
+            } else {
+              const int e = km * t;
+              const int qd = e / (N / 4);
+              const V2 w = tw[e & (N / 4 - 1)];
+              cr = (qd & 1) ? w.y : w.x;
+              ci = (qd & 1) ? -w.x : w.y;
+              if (qd & 2) { cr = -cr; ci = -ci; }
+            }
+            const cx<T> x = v[u * R + t];
+            v[u * R + t] = cx<T>{x.x * cr - x.y * ci, x.x * ci + x.y * cr};
+          });
+        });
+      }
+      static_for<0, NB>([&](auto uu) { dft_reg<T, R>(&v[decltype(uu)::value * R]); });
+      if constexpr (s < NSTAGE - 1) {
+        constexpr int Rn = (s == 0) ? R1 : R2;
+        auto wr_idx = [&](int u, int t) {
+          const int q = j + u * TPL;
+          const int k = q & (Ns - 1);
+          return at((q - k) * R + k + t * Ns);
+        };
+        auto rd_idx = [&](int u, int t) { return at(j + u * TPL + t * (N / Rn)); };
+        if constexpr (s > 0) xsync();  // previous exchange's reads done
+        if constexpr (SPLIT) {
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].x;
+          });
+          xsync();
+          T re[E];
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            re[decltype(ii)::value] = exs[rd_idx(u, t)];
+          });
+          xsync();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].y;
+          });
+          xsync();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], exs[rd_idx(u, t)]};
+          });
+        } else {
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            const cx<T> x = v[u * R + bitrev(t, LR)];
+            V2 w; w.x = x.x; w.y = x.y;
+            exv[wr_idx(u, t)] = w;
+          });
+          xsync();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            const V2 w = exv[rd_idx(u, t)];
+            v[decltype(ii)::value] = cx<T>{w.x, w.y};
+          });
+        }
+      }
+    });
+  };
+
+  stages();
+
+  // times H[n], then conjugated (the inverse as conj(F(conj(.)))); filter values are read once: non-temporal
+  auto filt = [&](auto complex_filter) {
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int cn = u * TPL + t * (N / RL);
+      const int r = u * RL + bitrev(t, LRL);
+      const long long off = fb + (long long)cn * f.axis;
+      const cx<T> x = v[r];
+      if constexpr (decltype(complex_filter)::value) {
+        V2 h;
+        h.x = 0; h.y = 0;
+        if (valid) h = gload(reinterpret_cast<const V2 *>(filter) + off);
+        v[r] = cx<T>{x.x * h.x - x.y * h.y, -(x.x * h.y + x.y * h.x)};
+      } else {
+        T h = 0;
+        if (valid) h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + off);
+        v[r] = cx<T>{x.x * h, -(x.y * h)};
+      }
+    });
+  };
+  if (f.cplx) filt(std::true_type{});
+  else filt(std::false_type{});
+
+  // round trip through the exchange image: from the last stage's order back into the load distribution
+  xsync();  // the last exchange's reads done
+  if constexpr (SPLIT) {
+    T re[E];
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      exs[at(j + u * TPL + t * (N / RL))] = v[u * RL + bitrev(t, LRL)].x;
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      re[decltype(ii)::value] = exs[at(j + u * TPL + t * (N / R0))];
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      exs[at(j + u * TPL + t * (N / RL))] = v[u * RL + bitrev(t, LRL)].y;
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], exs[at(j + u * TPL + t * (N / R0))]};
+    });
+  } else {
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      const cx<T> x = v[u * RL + bitrev(t, LRL)];
+      V2 w; w.x = x.x; w.y = x.y;
+      exv[at(j + u * TPL + t * (N / RL))] = w;
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      const V2 w = exv[at(j + u * TPL + t * (N / R0))];
+      v[decltype(ii)::value] = cx<T>{w.x, w.y};
+    });
+  }
+  xsync();  // the round trip's reads done before the first exchange of the second half writes
+
+  stages();
+
+  const T sc = (T)a.scale;
+  static_for<0, E>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+    constexpr int cn = u * TPL + t * (N / RL);
+    const cx<T> x = v[u * RL + bitrev(t, LRL)];
+    V2 w;
+    w.x = x.x * sc;
+    w.y = -x.y * sc;
+    if (valid) gstore_p<KEEP>(line + (long long)cn * a.in_axis, w);
+  });
+}
+
+// (the filter values and the second half's live ranges cost registers the plain pass does not need: at most 2 waves per
+//  SIMD, 256 VGPRs, so that no instance spills)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+constexpr int conv_wps() { return PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E < 2 ? PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E : 2; }
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_panel_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twq) {
+  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP>(a, f, data, filter, twq);
+}
+
+// ---------------------------------------------------------------------------
 // Mixed-radix panel kernel: the same three-stage register/LDS Stockham scheme for
 // lengths N = R0 * R1 * R2 whose radices are products of small primes (2, 3, 5 with hand-written
 // butterflies, 7, 11, 13 as direct DFTs): 768 = 12 x 8 x 8, 1000 = 10 x 10 x 10, 896 = 8 x 8 x 14, ...  Differences from fft_panel_k:
@@ -979,6 +1235,7 @@ struct Variant {
   bool keep = false;  // KEEP instantiation (offt_pass_desc::out_keep): default-policy stores
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
+  bool conv = false;  // fft_conv_panel_k instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
 // (uneven, or not a power of two: grids split over 3, 6, ... ranks)
@@ -1072,6 +1329,24 @@ void reg_variant_pair(int id, int defmask) {
   }
 }
 
+// fused convolution instances (fft_conv_panel_k, offt_reg_conv_*.hip): contiguous lines, plus a twin with cache-keeping
+// stores for the alternating launches over groups of z-planes (offt_host.c)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variant_conv() {
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  char nm[160];
+  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s convolution lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2,
+           COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  auto add = [&](bool keep, const void *fn) {
+    registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
+    registry().back().keep = keep;
+    registry().back().conv = true;
+  };
+  add(false, (const void *)fft_conv_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
+  add(true, (const void *)fft_conv_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
+}
+
 // mixed-radix (2^a 3^b 5^c) panel kernel: TPL threads per line instead of elements per thread.
 // FLAV limits which (in_contig, out_contig) flavours are instantiated at all (compile time), defmask says for
 // which of them this variant is the default.
@@ -1127,6 +1402,8 @@ void reg_mixed_f64_d();
 void reg_mixed_f64_e();
 void reg_mixed_f32_a();
 void reg_mixed_f32_b();
+void reg_conv_f64();
+void reg_conv_f32();
 void reg_dev();
 
 }  // namespace offtk

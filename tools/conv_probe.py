@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Developer probe: spectral convolution (offt_hip_execute_convolve) against the two ways a caller has without it, in one
+process.  After a warm-up the three ALTERNATE, so that all see the same box state, and the best of each is reported:
+  (a) forward + inverse            offt_3d_execute, offt_3d_execute_dir(+1)
+  (b) the caller's route           (a) with a torch multiply of the spectrum by H in between
+  (c) the convolve                 one call (fused route where the plan has one)
+against the byte model for complex data with a real filter, per point: (a) 6 x 2 esz x 2 (every pass reads and writes the
+volume), (b) (a) + 2 x 2 esz + esz (multiply sweep: read, filter, write), (c) 4 x 2 esz x 2 + 2 x 2 esz + esz (r2c: the
+same counts on the half spectrum for the y / x / fused passes, the z passes on the real rows).
+usage: conv_probe.py [f64|f32|r2c:]N ... [--zgroup-mib M]   (default: 1024 f32:1024 r2c:512)"""
+import ctypes as C
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from offt_amd import api  # noqa: E402
+
+L = api.lib()
+REPS = int(os.environ.get("CONV_PROBE_REPS", "5"))
+OPT_ZGROUP_MIB = 0  # include/offt_hip.h
+
+
+def model(n, esz, r2c):
+    """bytes of (a), (b), (c)"""
+    if not r2c:
+        v = 2 * esz * float(n) ** 3               # complex volume
+        a = 6 * 2 * v
+        mul = 2 * v + esz * float(n) ** 3
+        return a, a + mul, 4 * 2 * v + mul
+    h = n // 2 + 1
+    vr, vh = esz * float(n) ** 3, 2 * esz * float(h) * n * n
+    z = vr + vh                                   # one z pass: real rows one way, half spectrum the other
+    a = 2 * z + 4 * 2 * vh
+    mul = 2 * vh + esz * float(h) * n * n
+    return a, a + mul, 2 * z + 2 * 2 * vh + mul
+
+
+def main():
+    args = sys.argv[1:]
+    zg = None
+    if "--zgroup-mib" in args:
+        i = args.index("--zgroup-mib")
+        zg = int(args[i + 1])
+        del args[i:i + 2]
+    specs = args or ["1024", "f32:1024", "r2c:512"]
+    torch.cuda.set_device(0)
+    for spec in specs:
+        kind, _, n_s = spec.rpartition(":")
+        n = int(n_s)
+        prec = api.F32 if kind == "f32" else api.F64
+        r2c = kind == "r2c"
+        po = api.offt_3d_init(n, n, n, precision=prec, is_r2c=int(r2c))
+        if zg is not None:
+            L.offt_hip_set_option(po, OPT_ZGROUP_MIB, zg)
+        c = api.comm_dict(po)
+        td = torch.float32 if prec == api.F32 else torch.float64
+        esz = 4 if prec == api.F32 else 8
+        dev = torch.zeros(api.local_elems(po) * 2, dtype=td, device="cuda")
+        L.offt_hip_fill_input(po, dev.data_ptr(), 1)
+        H = torch.rand(api.local_elems(po), dtype=td, device="cuda") * (1.0 / float(n) ** 3)  # keeps the field bounded
+        o = c["ostride"]
+        osz = tuple(c["osize"])
+        spec_v = torch.as_strided(dev, osz + (2,), (2 * o[0], 2 * o[1], 2 * o[2], 1))
+        hv = torch.as_strided(H, osz + (1,), (o[0], o[1], o[2], 0))
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+        def run(fn):
+            ev[0].record()
+            fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) * 1e-3
+
+        def a():
+            api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+            L.offt_hip_set_output_scale(po, 1.0 / float(n) ** 3)
+            api.offt_3d_execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
+            L.offt_hip_set_output_scale(po, 1.0)
+
+        def b():
+            api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+            spec_v.mul_(hv)
+            api.offt_3d_execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
+
+        def cv():
+            api.offt_hip_execute_convolve(po, dev.data_ptr(), H.data_ptr(), api.FILTER_REAL)
+
+        for _ in range(2):
+            a(); b(); cv()
+        best = [1e30, 1e30, 1e30]
+        for _ in range(REPS):
+            for i, fn in enumerate((a, b, cv)):
+                best[i] = min(best[i], run(fn))
+        ma, mb, mc = model(n, esz, r2c)
+        tag = f"{'r2c f64' if r2c else ('f32' if prec == api.F32 else 'f64')} {n}^3"
+        fused = api.offt_hip_convolve_fused(po)
+        print(f"{tag}: (a) fwd+inv {best[0] * 1e3:.3f} ms ({ma / best[0] / 1e9:.0f} GB/s model)  "
+              f"(b) caller's route {best[1] * 1e3:.3f} ms ({mb / best[1] / 1e9:.0f} GB/s)  "
+              f"(c) convolve[{'fused' if fused else 'unfused'}] {best[2] * 1e3:.3f} ms ({mc / best[2] / 1e9:.0f} GB/s)  "
+              f"c/b {best[2] / best[1]:.3f}  c/a {best[2] / best[0]:.3f}  zgroup_mib {L.offt_hip_get_option(po, OPT_ZGROUP_MIB)}",
+              flush=True)
+        api.offt_3d_fin(po)
+        del dev, H, spec_v, hv
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
