@@ -1657,9 +1657,29 @@ typedef struct single_sched {
   offt_pass_desc d[3];
   const void *src[3];
   void *dst[3];
-  int slot[3];
-  int S, zyx, yzx_rot, s1_rot, c2r;
+  int slot[3];        /* which timer slot (0 = z, 1 = y, 2 = x) each launch feeds */
+  int zyx;            /* the default z-y-x layout */
+  /* the two launches that work through the same planes one after the other, and may alternate over groups of them that fit
+   * the Infinity Cache (execute_single): */
+  int pair;           /* the producer launch (the consumer is the next one); -1: none */
+  int planes;         /* planes the two share (nb1 of both) */
+  double plane_elems; /* elements per plane */
 } single_sched;
+
+/* a pass descriptor turned into its mirror image: input and output sides exchanged, the sign of the exponent flipped, the
+ * real-input pass become the real-output one.  `scale` and `out_keep` stay as they are: the callers set them, each by its
+ * own rule. */
+static void desc_mirror(offt_pass_desc *d) {
+  const offt_pass_desc f = *d;
+  d->direction = +1;
+  d->in_axis_stride = f.out_axis_stride; d->in_col_stride = f.out_col_stride; d->in_b1_stride = f.out_b1_stride; d->in_b2_stride = f.out_b2_stride;
+  d->out_axis_stride = f.in_axis_stride; d->out_col_stride = f.in_col_stride; d->out_b1_stride = f.in_b1_stride; d->out_b2_stride = f.in_b2_stride;
+  d->in_split = f.out_split; d->in_split_nfloor = f.out_split_nfloor; d->in_block_stride = f.out_block_stride;
+  d->out_split = f.in_split; d->out_split_nfloor = f.in_split_nfloor; d->out_block_stride = f.in_block_stride;
+  d->in_block_tab = f.out_block_tab; d->out_block_tab = f.in_block_tab;
+  d->in_contig = f.out_contig; d->out_contig = f.in_contig;
+  if (f.real_input == 1) d->real_input = 2; /* real input -> real output: the complex-to-real inverse's z pass */
+}
 
 static void single_schedule(struct _offt_plan *po, void *data, int dir, single_sched *ss) {
   hip_state *st = (hip_state *)po->hip_state;
@@ -1670,17 +1690,16 @@ static void single_schedule(struct _offt_plan *po, void *data, int dir, single_s
   const long long is0 = c->istride[0], is1 = c->istride[1];
   const long long os0 = c->ostride[0], os1 = c->ostride[1], os2 = c->ostride[2];
   void *W = st->work;
-  /* complex-to-real inverse (is_r2c, dir > 0): the same schedules, the z pass last, as a real-output pass (real_input = 2)
-   * that reads the Nz/2+1 complex values of a line and writes Nz reals at the head of its row */
-  const int c2r = po->is_r2c && dir > 0;
-  offt_pass_desc d[3];
-  const void *src[3];
-  void *dst[3];
-  int slot[3]; /* which timer slot (0 = z, 1 = y, 2 = x) each launch feeds */
   const int S = po->params->v[_S_] != 0;
-  const int zyx = !S && !(po->is_equalxy && c->M1 == c->M4);
+  /* every layout is stated once, as its FORWARD launches P1, P2, P3; the inverse is derived from them at the end */
+  offt_pass_desc *d = ss->d;
+  const void **src = ss->src;
+  void **dst = ss->dst;
+  int *slot = ss->slot;
+  int own_mirror = 0; /* the schedule is its own mirror image: every pass in place with the same addressing on both sides */
+  ss->zyx = !S && !(po->is_equalxy && c->M1 == c->M4);
+  ss->pair = -1; ss->planes = 0; ss->plane_elems = 0.0;
 
-  int s1_rot = 0, yzx_rot = 0;
   if (S && st->work && st->work2) {
     /* x-y-z output == input layout, x outermost on both sides: an FFT along x that touched this layout directly would walk
      * memory at a plane-sized stride (16 MiB at 1024^3: 56 % of the roofline, profiles/r02_layouts_zgroup.txt).  Instead
@@ -1689,65 +1708,49 @@ static void single_schedule(struct _offt_plan *po, void *data, int dir, single_s
      *   P1  in[x][y][z] --FFTz--> W[y][z][x]    columns = 8 x-planes: eight lines gathered from eight planes
      *   P2  W[y][z][x]  --FFTx--> V[z][x][y]    columns = 8 y
      *   P3  V[z][x][y]  --FFTy--> out[x][y][z]  columns = 8 z
-     * (the inverse runs y, x, z with loads and stores swapped).  Three contig-in / strided-out passes. */
+     * Three contig-in / strided-out passes. */
     const long long wy = (long long)Nz * Nx + st->wpad;  /* W: y-plane pitch */
     const long long vz = (long long)Nx * Ny + st->wpad;  /* V: z-plane pitch */
     void *V = st->work2;
-    s1_rot = 1;
-    desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
-    desc_init(&d[1], st, Nx, dir, 0);
-    desc_init(&d[2], st, Ny, dir, 1);
+    desc_init(&d[0], st, Nzf, -1, 2);
+    desc_init(&d[1], st, Nx, -1, 0);
+    desc_init(&d[2], st, Ny, -1, 1);
     d[0].ncols = Nx; d[0].nb1 = Ny;
     d[1].ncols = Ny; d[1].nb1 = Nz;
     d[2].ncols = Nz; d[2].nb1 = Nx;
-    if (dir < 0) {
-      d[0].in_axis_stride = 1; d[0].in_col_stride = is0; d[0].in_b1_stride = is1; d[0].in_contig = 1;
-      d[0].out_axis_stride = Nx; d[0].out_col_stride = 1; d[0].out_b1_stride = wy; d[0].out_contig = 0;
-      d[1].in_axis_stride = 1; d[1].in_col_stride = wy; d[1].in_b1_stride = Nx; d[1].in_contig = 1;
-      d[1].out_axis_stride = Ny; d[1].out_col_stride = 1; d[1].out_b1_stride = vz; d[1].out_contig = 0;
-      d[2].in_axis_stride = 1; d[2].in_col_stride = vz; d[2].in_b1_stride = Ny; d[2].in_contig = 1;
-      d[2].out_axis_stride = os1; d[2].out_col_stride = os2; d[2].out_b1_stride = os0; d[2].out_contig = 0;
-      src[0] = data; dst[0] = W; src[1] = W; dst[1] = V; src[2] = V; dst[2] = data;
-      slot[0] = 0; slot[1] = 2; slot[2] = 1;
-    } else {
-      offt_pass_desc t;
-      d[2].in_axis_stride = os1; d[2].in_col_stride = os2; d[2].in_b1_stride = os0; d[2].in_contig = 0;
-      d[2].out_axis_stride = 1; d[2].out_col_stride = vz; d[2].out_b1_stride = Ny; d[2].out_contig = 1;
-      d[1].in_axis_stride = Ny; d[1].in_col_stride = 1; d[1].in_b1_stride = vz; d[1].in_contig = 0;
-      d[1].out_axis_stride = 1; d[1].out_col_stride = wy; d[1].out_b1_stride = Nx; d[1].out_contig = 1;
-      d[0].in_axis_stride = Nx; d[0].in_col_stride = 1; d[0].in_b1_stride = wy; d[0].in_contig = 0;
-      d[0].out_axis_stride = 1; d[0].out_col_stride = is0; d[0].out_b1_stride = is1; d[0].out_contig = 1;
-      t = d[0]; d[0] = d[2]; d[2] = t; /* launch order y, x, z */
-      src[0] = data; dst[0] = V; src[1] = V; dst[1] = W; src[2] = W; dst[2] = data;
-      slot[0] = 1; slot[1] = 2; slot[2] = 0;
-    }
+    d[0].in_axis_stride = 1; d[0].in_col_stride = is0; d[0].in_b1_stride = is1; d[0].in_contig = 1;
+    d[0].out_axis_stride = Nx; d[0].out_col_stride = 1; d[0].out_b1_stride = wy; d[0].out_contig = 0;
+    d[1].in_axis_stride = 1; d[1].in_col_stride = wy; d[1].in_b1_stride = Nx; d[1].in_contig = 1;
+    d[1].out_axis_stride = Ny; d[1].out_col_stride = 1; d[1].out_b1_stride = vz; d[1].out_contig = 0;
+    d[2].in_axis_stride = 1; d[2].in_col_stride = vz; d[2].in_b1_stride = Ny; d[2].in_contig = 1;
+    d[2].out_axis_stride = os1; d[2].out_col_stride = os2; d[2].out_b1_stride = os0; d[2].out_contig = 0;
+    src[0] = data; dst[0] = W; src[1] = W; dst[1] = V; src[2] = V; dst[2] = data;
+    slot[0] = 0; slot[1] = 2; slot[2] = 1;
+    /* (no pair: P1 and P2 do share y-planes of W, but alternating them over groups of planes -- the consumer sliced along
+     * its columns -- came out SLOWER, 17.9 against 17.4 ms at 1024^3 f64, profiles/r03_layouts.txt) */
   } else if (S) {
     /* x-y-z output == input layout without scratch: three in-place passes, strided along y and x */
-    desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
+    desc_init(&d[0], st, Nzf, -1, 2);
     d[0].ncols = Ny; d[0].nb1 = Nx;
     d[0].in_axis_stride = d[0].out_axis_stride = 1;
     d[0].in_col_stride = d[0].out_col_stride = is1;
     d[0].in_b1_stride = d[0].out_b1_stride = is0;
     d[0].in_contig = d[0].out_contig = 1;
-    desc_init(&d[1], st, Ny, dir, 1);
+    desc_init(&d[1], st, Ny, -1, 1);
     d[1].ncols = Nz; d[1].nb1 = Nx;
     d[1].in_axis_stride = d[1].out_axis_stride = is1;
     d[1].in_col_stride = d[1].out_col_stride = 1;
     d[1].in_b1_stride = d[1].out_b1_stride = is0;
-    desc_init(&d[2], st, Nx, dir, 0);
+    desc_init(&d[2], st, Nx, -1, 0);
     if (is0 == (long long)Ny * is1 && is1 == Nz) { d[2].ncols = Ny * Nz; d[2].nb1 = 1; }
     else { d[2].ncols = Nz; d[2].nb1 = Ny; }
     d[2].in_axis_stride = d[2].out_axis_stride = is0;
     d[2].in_col_stride = d[2].out_col_stride = 1;
     d[2].in_b1_stride = d[2].out_b1_stride = is1;
     for (int i = 0; i < 3; i++) { src[i] = data; dst[i] = data; slot[i] = i; }
-    if (c2r) { /* the real-output z pass reads the half spectrum the x and y passes leave: launch order x, y, z */
-      offt_pass_desc t = d[0]; d[0] = d[2]; d[2] = t;
-      slot[0] = 2; slot[2] = 0;
-    }
-  } else if (zyx) {
+    own_mirror = 1;
+    ss->pair = 0; ss->planes = Nx; ss->plane_elems = (double)Ny * Nz; /* z and y both work inside x-planes */
+  } else if (ss->zyx) {
     /* default z-y-x output.  Every pass READS whole contiguous lines and the
      * axis rotation rides on the stores (128-B column segments, row pitch of
      * one line), so no pass walks memory at a plane-sized stride:
@@ -1758,42 +1761,23 @@ static void single_schedule(struct _offt_plan *po, void *data, int dir, single_s
      * + FFTy + FFTx of the reference (offt-compute.c:625-634, 4019-4036). */
     const long long wy = Ny + st->wrow;                 /* W line pitch */
     const long long wx = (long long)Nz * wy + st->wpad; /* W plane (+ optional pad, elements) */
-    desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
-    desc_init(&d[1], st, Ny, dir, 1);
-    desc_init(&d[2], st, Nx, dir, 0);
-    if (dir < 0) {
-      d[0].ncols = Ny; d[0].nb1 = Nx;
-      d[0].in_axis_stride = 1; d[0].in_col_stride = is1; d[0].in_b1_stride = is0; d[0].in_contig = 1;
-      d[0].out_axis_stride = wy; d[0].out_col_stride = 1; d[0].out_b1_stride = wx; d[0].out_contig = 0;
-      d[1].ncols = Nx; d[1].nb1 = Nz;
-      d[1].in_axis_stride = 1; d[1].in_col_stride = wx; d[1].in_b1_stride = wy; d[1].in_contig = 1;
-      d[1].out_axis_stride = os1; d[1].out_col_stride = os0; d[1].out_b1_stride = os2; d[1].out_contig = 0;
-      d[2].ncols = Ny; d[2].nb1 = Nz;
-      d[2].in_axis_stride = d[2].out_axis_stride = os0;
-      d[2].in_col_stride = d[2].out_col_stride = os1;
-      d[2].in_b1_stride = d[2].out_b1_stride = os2;
-      d[2].in_contig = d[2].out_contig = 1;
-      src[0] = data; dst[0] = W; src[1] = W; dst[1] = data; src[2] = data; dst[2] = data;
-      slot[0] = 0; slot[1] = 1; slot[2] = 2;
-    } else {
-      /* inverse: the same three steps backwards (x in place, y -> W, z -> input layout) */
-      offt_pass_desc t;
-      d[2].ncols = Ny; d[2].nb1 = Nz;
-      d[2].in_axis_stride = d[2].out_axis_stride = os0;
-      d[2].in_col_stride = d[2].out_col_stride = os1;
-      d[2].in_b1_stride = d[2].out_b1_stride = os2;
-      d[2].in_contig = d[2].out_contig = 1;
-      d[1].ncols = Nx; d[1].nb1 = Nz;
-      d[1].in_axis_stride = os1; d[1].in_col_stride = os0; d[1].in_b1_stride = os2; d[1].in_contig = 0;
-      d[1].out_axis_stride = 1; d[1].out_col_stride = wx; d[1].out_b1_stride = wy; d[1].out_contig = 1;
-      d[0].ncols = Ny; d[0].nb1 = Nx;
-      d[0].in_axis_stride = wy; d[0].in_col_stride = 1; d[0].in_b1_stride = wx; d[0].in_contig = 0;
-      d[0].out_axis_stride = 1; d[0].out_col_stride = is1; d[0].out_b1_stride = is0; d[0].out_contig = 1;
-      t = d[0]; d[0] = d[2]; d[2] = t; /* launch order x, y, z */
-      src[0] = data; dst[0] = data; src[1] = data; dst[1] = W; src[2] = W; dst[2] = data;
-      slot[0] = 2; slot[1] = 1; slot[2] = 0;
-    }
+    desc_init(&d[0], st, Nzf, -1, 2);
+    desc_init(&d[1], st, Ny, -1, 1);
+    desc_init(&d[2], st, Nx, -1, 0);
+    d[0].ncols = Ny; d[0].nb1 = Nx;
+    d[0].in_axis_stride = 1; d[0].in_col_stride = is1; d[0].in_b1_stride = is0; d[0].in_contig = 1;
+    d[0].out_axis_stride = wy; d[0].out_col_stride = 1; d[0].out_b1_stride = wx; d[0].out_contig = 0;
+    d[1].ncols = Nx; d[1].nb1 = Nz;
+    d[1].in_axis_stride = 1; d[1].in_col_stride = wx; d[1].in_b1_stride = wy; d[1].in_contig = 1;
+    d[1].out_axis_stride = os1; d[1].out_col_stride = os0; d[1].out_b1_stride = os2; d[1].out_contig = 0;
+    d[2].ncols = Ny; d[2].nb1 = Nz;
+    d[2].in_axis_stride = d[2].out_axis_stride = os0;
+    d[2].in_col_stride = d[2].out_col_stride = os1;
+    d[2].in_b1_stride = d[2].out_b1_stride = os2;
+    d[2].in_contig = d[2].out_contig = 1;
+    src[0] = data; dst[0] = W; src[1] = W; dst[1] = data; src[2] = data; dst[2] = data;
+    slot[0] = 0; slot[1] = 1; slot[2] = 2;
+    ss->pair = 1; ss->planes = Nz; ss->plane_elems = (double)Nx * Ny; /* y writes z-planes of out, x transforms them */
   } else if (st->work2) {
     /* y-z-x output (is_equalxy) as a variation of the z-y-x schedule: the same two rotations, the second one into a second
      * scratch volume V[z][y][x], and the x pass -- whole contiguous lines on both sides -- puts every line where the
@@ -1803,171 +1787,162 @@ static void single_schedule(struct _offt_plan *po, void *data, int dir, single_s
     const long long wy = Ny + st->wrow, wx = (long long)Nz * wy + st->wpad;
     const long long vz = (long long)Nx * Ny + st->wpad;
     void *V = st->work2;
-    yzx_rot = 1;
-    desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
-    desc_init(&d[1], st, Ny, dir, 1);
-    desc_init(&d[2], st, Nx, dir, 0);
+    desc_init(&d[0], st, Nzf, -1, 2);
+    desc_init(&d[1], st, Ny, -1, 1);
+    desc_init(&d[2], st, Nx, -1, 0);
     d[0].ncols = Ny; d[0].nb1 = Nx;
     d[1].ncols = Nx; d[1].nb1 = Nz;
     d[2].ncols = Ny; d[2].nb1 = Nz;
-    if (dir < 0) {
-      d[0].in_axis_stride = 1; d[0].in_col_stride = is1; d[0].in_b1_stride = is0; d[0].in_contig = 1;
-      d[0].out_axis_stride = wy; d[0].out_col_stride = 1; d[0].out_b1_stride = wx; d[0].out_contig = 0;
-      d[1].in_axis_stride = 1; d[1].in_col_stride = wx; d[1].in_b1_stride = wy; d[1].in_contig = 1;
-      d[1].out_axis_stride = Nx; d[1].out_col_stride = 1; d[1].out_b1_stride = vz; d[1].out_contig = 0;
-      d[2].in_axis_stride = 1; d[2].in_col_stride = Nx; d[2].in_b1_stride = vz; d[2].in_contig = 1;
-      d[2].out_axis_stride = os0; d[2].out_col_stride = os1; d[2].out_b1_stride = os2; d[2].out_contig = 1;
-      src[0] = data; dst[0] = W; src[1] = W; dst[1] = V; src[2] = V; dst[2] = data;
-      slot[0] = 0; slot[1] = 1; slot[2] = 2;
-    } else {
-      offt_pass_desc t;
-      d[2].in_axis_stride = os0; d[2].in_col_stride = os1; d[2].in_b1_stride = os2; d[2].in_contig = 1;
-      d[2].out_axis_stride = 1; d[2].out_col_stride = Nx; d[2].out_b1_stride = vz; d[2].out_contig = 1;
-      d[1].in_axis_stride = Nx; d[1].in_col_stride = 1; d[1].in_b1_stride = vz; d[1].in_contig = 0;
-      d[1].out_axis_stride = 1; d[1].out_col_stride = wx; d[1].out_b1_stride = wy; d[1].out_contig = 1;
-      d[0].in_axis_stride = wy; d[0].in_col_stride = 1; d[0].in_b1_stride = wx; d[0].in_contig = 0;
-      d[0].out_axis_stride = 1; d[0].out_col_stride = is1; d[0].out_b1_stride = is0; d[0].out_contig = 1;
-      t = d[0]; d[0] = d[2]; d[2] = t; /* launch order x, y, z */
-      src[0] = data; dst[0] = V; src[1] = V; dst[1] = W; src[2] = W; dst[2] = data;
-      slot[0] = 2; slot[1] = 1; slot[2] = 0;
-    }
+    d[0].in_axis_stride = 1; d[0].in_col_stride = is1; d[0].in_b1_stride = is0; d[0].in_contig = 1;
+    d[0].out_axis_stride = wy; d[0].out_col_stride = 1; d[0].out_b1_stride = wx; d[0].out_contig = 0;
+    d[1].in_axis_stride = 1; d[1].in_col_stride = wx; d[1].in_b1_stride = wy; d[1].in_contig = 1;
+    d[1].out_axis_stride = Nx; d[1].out_col_stride = 1; d[1].out_b1_stride = vz; d[1].out_contig = 0;
+    d[2].in_axis_stride = 1; d[2].in_col_stride = Nx; d[2].in_b1_stride = vz; d[2].in_contig = 1;
+    d[2].out_axis_stride = os0; d[2].out_col_stride = os1; d[2].out_b1_stride = os2; d[2].out_contig = 1;
+    src[0] = data; dst[0] = W; src[1] = W; dst[1] = V; src[2] = V; dst[2] = data;
+    slot[0] = 0; slot[1] = 1; slot[2] = 2;
+    ss->pair = 1; ss->planes = Nz; ss->plane_elems = (double)Nx * Ny; /* the same y / x pair over z-planes as z-y-x, in V */
   } else {
     /* y-z-x output (is_equalxy), one scratch volume: z and y passes in the natural layout inside W,
      * the x pass transposes into the caller's layout */
     const long long w1 = Nz, w0 = (long long)Ny * Nz;
-    desc_init(&d[0], st, Nzf, dir, 2);
-    d[0].real_input = po->is_r2c ? (dir > 0 ? 2 : 1) : 0;
+    desc_init(&d[0], st, Nzf, -1, 2);
     d[0].ncols = Ny; d[0].nb1 = Nx; d[0].in_axis_stride = d[0].out_axis_stride = 1;
     d[0].in_contig = d[0].out_contig = 1;
-    desc_init(&d[1], st, Ny, dir, 1);
+    d[0].in_col_stride = is1; d[0].in_b1_stride = is0; d[0].out_col_stride = w1; d[0].out_b1_stride = w0;
+    desc_init(&d[1], st, Ny, -1, 1);
     d[1].ncols = Nz; d[1].nb1 = Nx;
     d[1].in_axis_stride = d[1].out_axis_stride = w1;
     d[1].in_col_stride = d[1].out_col_stride = 1;
     d[1].in_b1_stride = d[1].out_b1_stride = w0;
-    desc_init(&d[2], st, Nx, dir, 0);
+    desc_init(&d[2], st, Nx, -1, 0);
     d[2].ncols = Nz; d[2].nb1 = Ny;
-    if (dir < 0) {
-      d[0].in_col_stride = is1; d[0].in_b1_stride = is0; d[0].out_col_stride = w1; d[0].out_b1_stride = w0;
-      d[2].in_axis_stride = w0; d[2].in_col_stride = 1; d[2].in_b1_stride = w1;
-      d[2].out_axis_stride = os0; d[2].out_col_stride = os2; d[2].out_b1_stride = os1; d[2].out_contig = (os0 == 1);
-      src[0] = data; dst[0] = W; src[1] = W; dst[1] = W; src[2] = W; dst[2] = data;
-      slot[0] = 0; slot[1] = 1; slot[2] = 2;
-    } else {
-      offt_pass_desc t;
-      d[2].in_axis_stride = os0; d[2].in_col_stride = os2; d[2].in_b1_stride = os1; d[2].in_contig = (os0 == 1);
-      d[2].out_axis_stride = w0; d[2].out_col_stride = 1; d[2].out_b1_stride = w1;
-      d[0].in_col_stride = w1; d[0].in_b1_stride = w0; d[0].out_col_stride = is1; d[0].out_b1_stride = is0;
-      t = d[0]; d[0] = d[2]; d[2] = t;
-      src[0] = data; dst[0] = W; src[1] = W; dst[1] = W; src[2] = W; dst[2] = data;
-      slot[0] = 2; slot[1] = 1; slot[2] = 0;
+    d[2].in_axis_stride = w0; d[2].in_col_stride = 1; d[2].in_b1_stride = w1;
+    d[2].out_axis_stride = os0; d[2].out_col_stride = os2; d[2].out_b1_stride = os1; d[2].out_contig = (os0 == 1);
+    src[0] = data; dst[0] = W; src[1] = W; dst[1] = W; src[2] = W; dst[2] = data;
+    slot[0] = 0; slot[1] = 1; slot[2] = 2;
+    ss->pair = 0; ss->planes = Nx; ss->plane_elems = (double)Ny * Nz; /* z into the scratch volume, y in place there */
+  }
+  d[0].real_input = po->is_r2c ? 1 : 0; /* P1 is the z pass in every layout */
+
+  if (dir > 0) {
+    /* The inverse is the forward schedule mirrored, on one rank as on several (mirror_step): every pass with its two sides
+     * exchanged, the buffers of every launch exchanged, the launches in reverse order -- x, y, z where the forward runs z, y,
+     * x, the real-input z pass become the real-output pass of a complex-to-real inverse (is_r2c), which reads the Nz/2+1
+     * complex values of a line and writes Nz reals at the head of its row.
+     * One exception: the in-place x-y-z schedule is its own mirror image and KEEPS the order z, y, x on a complex plan.  The
+     * order of the passes is part of the result's bits, so it stays as it has always been; only the complex-to-real inverse
+     * runs it backwards, because the real-output z pass must come last: it reads the half spectrum the x and y passes leave. */
+    for (int i = 0; i < 3; i++) {
+      const void *t = src[i];
+      desc_mirror(&d[i]);
+      src[i] = dst[i]; dst[i] = (void *)t;
+    }
+    if (!own_mirror || po->is_r2c) {
+      const offt_pass_desc td = d[0];
+      const void *ts = src[0];
+      void *to = dst[0];
+      const int tl = slot[0];
+      d[0] = d[2]; d[2] = td;
+      src[0] = src[2]; src[2] = ts;
+      dst[0] = dst[2]; dst[2] = to;
+      slot[0] = slot[2]; slot[2] = tl;
+      /* the y / x pair over z-planes is now the first two launches, x producing; a z / y pair turned round (y producing)
+       * runs as plain launches */
+      ss->pair = ss->pair == 1 ? 0 : -1;
     }
   }
-  d[2].scale = st->out_scale; /* last launch */
-  memcpy(ss->d, d, sizeof d);
-  for (int i = 0; i < 3; i++) { ss->src[i] = src[i]; ss->dst[i] = dst[i]; ss->slot[i] = slot[i]; }
-  ss->S = S; ss->zyx = zyx; ss->yzx_rot = yzx_rot; ss->s1_rot = s1_rot; ss->c2r = c2r;
+  d[2].scale = st->out_scale; /* the last launch, in either direction */
+}
+
+/* Launches that alternate over groups of planes small enough for the Infinity Cache (execute_single): how many planes per
+ * group, or 0 for plain launches.  `plane_elems` elements per plane, `cnt` planes, the two launches' line lengths, the
+ * producer's descriptor.  OFFT_ZGROUP_MIB sets the group size (0: off).  Without it the groups are 256 MiB, and only
+ * lines of up to 1024 points get them (the 2048-point kernels fill a CU with one workgroup, a group launch of theirs ends
+ * in a long tail, and 2048^3 f32 came out 2 % slower -- profiles/r02_zgroup2.txt), and only where the producer has a
+ * kernel with cache-keeping stores (without them the groups are just more launches -- the mixed-radix lengths lost
+ * 3-6 %, profiles/r02_size_table_final2.txt; a test backend counts as having one). */
+static int plane_group(const hip_state *st, double plane_elems, int cnt, int len_a, int len_b, const offt_pass_desc *producer) {
+  if (st->opt.zgroup_mib < 0 && !(len_a <= 1024 && len_b <= 1024 && (g_backend || offt_hipk_keeps_output(producer)))) return 0;
+  const int group_mib = st->opt.zgroup_mib >= 0 ? st->opt.zgroup_mib : 256;
+  const double plane_mib = plane_elems * (double)st->esz / (1024.0 * 1024.0);
+  const int ng = group_mib > 0 ? (int)((double)group_mib / plane_mib) : 0;
+  return ng > cnt ? cnt : ng;
 }
 
 static int execute_single(struct _offt_plan *po, void *data, int dir) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
-  const int Nx = po->Nx, Ny = po->Ny, Nzf = po->Nz, Nz = po->is_r2c ? po->Nz / 2 + 1 : po->Nz;
   void *s = st->s_compute;
   single_sched ss;
   single_schedule(po, data, dir, &ss);
-  offt_pass_desc *d = ss.d;
-  const void *const *src = ss.src;
-  void *const *dst = ss.dst;
-  const int *slot = ss.slot;
-  const int S = ss.S, zyx = ss.zyx, yzx_rot = ss.yzx_rot, s1_rot = ss.s1_rot, c2r = ss.c2r;
-  for (int i = 0; i < 3; i++) st->pass_slot[i] = slot[i];
+  for (int i = 0; i < 3; i++) st->pass_slot[i] = ss.slot[i];
   /* Forward z-y-x: the y pass writes out[z][y][x] plane by plane and the x pass transforms those planes in place, so
    * the two ALTERNATE over groups of z-planes small enough for the 256 MiB memory-side Infinity Cache: y(group) stores
    * with the default cache policy (out_keep), x(group) finds its input there instead of in HBM -- one of the six
    * read/write sweeps of the transform is served by the cache.  1024^3 f64: y + x 11.5 -> 10.7 ms, the transform
-   * 17.3 -> 16.5 ms (tools/mall_probe.py, profiles/r02_mall_probe.txt, r02_zgroup*.txt).  OFFT_ZGROUP_MIB sets
-   * the group size (0: off). */
-  st->yx_fused = 0;
-  /* (lines of up to 1024 points: the 2048-point kernels fill a CU with one workgroup, a group launch of theirs ends in
-   * a long tail, and 2048^3 f32 came out 2 % slower -- profiles/r02_zgroup2.txt) */
-  /* (... and only where the y pass has a kernel with cache-keeping stores: without them the groups are just more
-   * launches -- the mixed-radix lengths lost 3-6 %, profiles/r02_size_table_final2.txt) */
-  /* The inverse runs the same three steps backwards (x in place, y, z): there the x launch of a group is the producer
+   * 17.3 -> 16.5 ms (tools/mall_probe.py, profiles/r02_mall_probe.txt, r02_zgroup*.txt).
+   * The inverse runs the same three steps backwards (x in place, y, z): there the x launch of a group is the producer
    * and the y launch the consumer.  The other two layouts have such a pair as well: their z and y passes both work
    * inside x-planes (x-y-z: both in place; y-z-x forward: z into the scratch volume, y in place there), so z(group of
-   * x-planes) keeps and y(group) re-reads. */
-  int ia = -1, cnt = 0;       /* producer launch (the consumer is the next one); planes the two share */
-  double plane_elems = 0.0;
-  int len_a = 0, len_b = 0;   /* their line lengths */
-  /* (the rotating y-z-x schedule has the same y / x pair over z-planes as z-y-x) */
-  if (zyx || yzx_rot) { ia = dir < 0 ? 1 : 0; cnt = Nz; plane_elems = (double)Nx * Ny; len_a = dir < 0 ? Ny : Nx; len_b = dir < 0 ? Nx : Ny; }
-  /* (the rotating x-y-z schedule runs its three launches plainly: P1 and P2 do share y-planes of W, but alternating them
-   * over groups of planes -- the consumer sliced along its columns -- came out SLOWER, 17.9 against 17.4 ms at 1024^3 f64,
-   * profiles/r03_layouts.txt) */
-  else if (s1_rot) ia = -1;
-  else if ((S || dir < 0) && !c2r) { ia = 0; cnt = Nx; plane_elems = (double)Ny * Nz; len_a = Nzf; len_b = Ny; }
-  if (ia >= 0 && d[ia].nb1 == cnt && d[ia + 1].nb1 == cnt && !d[ia].real_input &&
-      (st->opt.zgroup_mib >= 0 || (len_a <= 1024 && len_b <= 1024 && (g_backend || offt_hipk_keeps_output(&d[ia]))))) {
-    const int ib = ia + 1;
-    const int group_mib = st->opt.zgroup_mib >= 0 ? st->opt.zgroup_mib : 256;
-    /* OFFT_ZGROUP_STREAMS=2: consumer launches on a second stream (then 128 MiB groups do as well as 256 MiB on one stream) */
-    const int two_streams = st->opt.zgroup_streams >= 2;
-    const double plane_mib = plane_elems * (double)st->esz / (1024.0 * 1024.0);
-    int ng = group_mib > 0 ? (int)((double)group_mib / plane_mib) : 0;
-    if (ng >= 1) {
-      if (ng > cnt) ng = cnt;
-      /* the consumer of a group runs on a second stream behind its producer, so that the next group's producer fills the
-       * CUs its last workgroups leave idle: groups can be small (good for the cache) without paying a launch tail each */
-      int aux = two_streams && ng < cnt;
-      if (aux && !st->s_aux) {
-        st->s_aux = be->stream_create();
-        for (int i = 0; i < 4; i++) st->ev_aux[i] = be->event_create();
-        if (!st->s_aux || !st->ev_aux[0] || !st->ev_aux[1] || !st->ev_aux[2] || !st->ev_aux[3]) aux = 0;
-      }
-      for (int i = 0; i < ia; i++) { /* the launch ahead of the pair */
-        if (st->timed) be->event_record(st->evp[i], s);
-        if (be->pass(&d[i], src[i], dst[i], s)) return -1;
-      }
-      if (st->timed) be->event_record(st->evp[ia], s);
-      int k = 0;
-      for (int z0 = 0; z0 < cnt; z0 += ng, k++) {
-        const int g = cnt - z0 < ng ? cnt - z0 : ng;
-        offt_pass_desc da = d[ia], db = d[ib];
-        da.nb1 = g; db.nb1 = g;
-        da.out_keep = 1;
-        const char *sa = (const char *)src[ia] + (size_t)z0 * (size_t)da.in_b1_stride * st->esz;
-        char *oa = (char *)dst[ia] + (size_t)z0 * (size_t)da.out_b1_stride * st->esz;
-        const char *sb = (const char *)src[ib] + (size_t)z0 * (size_t)db.in_b1_stride * st->esz;
-        char *ob = (char *)dst[ib] + (size_t)z0 * (size_t)db.out_b1_stride * st->esz;
-        if (be->pass(&da, sa, oa, s)) return -1;
-        if (aux) {
-          be->event_record(st->ev_aux[k & 3], s);
-          be->stream_wait(st->s_aux, st->ev_aux[k & 3]);
-        }
-        if (be->pass(&db, sb, ob, aux ? st->s_aux : s)) return -1;
-      }
-      if (aux) { /* the compute stream goes on behind the last consumer launch */
-        be->event_record(st->ev_aux[k & 3], st->s_aux);
-        be->stream_wait(s, st->ev_aux[k & 3]);
-      }
-      /* (the events around the pair span both launches; the boundary inside it is recorded at its end: the reader
-       *  splits the pair's time evenly) */
-      if (st->timed) { be->event_record(st->evp[ib], s); be->event_record(st->evp[ib + 1], s); }
-      for (int i = ib + 1; i < 3; i++) { /* the launch behind the pair */
-        if (be->pass(&d[i], src[i], dst[i], s)) return -1;
-        if (st->timed) be->event_record(st->evp[i + 1], s);
-      }
-      st->yx_fused = ia + 1;
-      return 0;
+   * x-planes) keeps and y(group) re-reads.  single_schedule names the pair; plane_group has the rule for the group size. */
+  st->yx_fused = 0;
+  const int ia = ss.pair, ib = ia + 1, cnt = ss.planes; /* producer and consumer launch; planes the two share */
+  int ng = 0;
+  if (ia >= 0 && ss.d[ia].nb1 == cnt && ss.d[ib].nb1 == cnt && !ss.d[ia].real_input)
+    ng = plane_group(st, ss.plane_elems, cnt, ss.d[ia].n, ss.d[ib].n, &ss.d[ia]);
+  if (ng >= 1) {
+    /* OFFT_ZGROUP_STREAMS=2: consumer launches on a second stream (then 128 MiB groups do as well as 256 MiB on one stream).
+     * The consumer of a group runs on a second stream behind its producer, so that the next group's producer fills the
+     * CUs its last workgroups leave idle: groups can be small (good for the cache) without paying a launch tail each */
+    int aux = st->opt.zgroup_streams >= 2 && ng < cnt;
+    if (aux && !st->s_aux) {
+      st->s_aux = be->stream_create();
+      for (int i = 0; i < 4; i++) st->ev_aux[i] = be->event_create();
+      if (!st->s_aux || !st->ev_aux[0] || !st->ev_aux[1] || !st->ev_aux[2] || !st->ev_aux[3]) aux = 0;
     }
+    for (int i = 0; i < ia; i++) { /* the launch ahead of the pair */
+      if (st->timed) be->event_record(st->evp[i], s);
+      if (be->pass(&ss.d[i], ss.src[i], ss.dst[i], s)) return -1;
+    }
+    if (st->timed) be->event_record(st->evp[ia], s);
+    int k = 0;
+    for (int z0 = 0; z0 < cnt; z0 += ng, k++) {
+      const int g = cnt - z0 < ng ? cnt - z0 : ng;
+      offt_pass_desc da = ss.d[ia], db = ss.d[ib];
+      da.nb1 = g; db.nb1 = g;
+      da.out_keep = 1;
+      const char *sa = (const char *)ss.src[ia] + (size_t)z0 * (size_t)da.in_b1_stride * st->esz;
+      char *oa = (char *)ss.dst[ia] + (size_t)z0 * (size_t)da.out_b1_stride * st->esz;
+      const char *sb = (const char *)ss.src[ib] + (size_t)z0 * (size_t)db.in_b1_stride * st->esz;
+      char *ob = (char *)ss.dst[ib] + (size_t)z0 * (size_t)db.out_b1_stride * st->esz;
+      if (be->pass(&da, sa, oa, s)) return -1;
+      if (aux) {
+        be->event_record(st->ev_aux[k & 3], s);
+        be->stream_wait(st->s_aux, st->ev_aux[k & 3]);
+      }
+      if (be->pass(&db, sb, ob, aux ? st->s_aux : s)) return -1;
+    }
+    if (aux) { /* the compute stream goes on behind the last consumer launch */
+      be->event_record(st->ev_aux[k & 3], st->s_aux);
+      be->stream_wait(s, st->ev_aux[k & 3]);
+    }
+    /* (the events around the pair span both launches; the boundary inside it is recorded at its end: the reader
+     *  splits the pair's time evenly) */
+    if (st->timed) { be->event_record(st->evp[ib], s); be->event_record(st->evp[ib + 1], s); }
+    for (int i = ib + 1; i < 3; i++) { /* the launch behind the pair */
+      if (be->pass(&ss.d[i], ss.src[i], ss.dst[i], s)) return -1;
+      if (st->timed) be->event_record(st->evp[i + 1], s);
+    }
+    st->yx_fused = ia + 1;
+    return 0;
   }
   /* per-pass timing events only when somebody will read them: in asynchronous mode the call returns before
    * the GPU has finished, and each record costs a barrier packet (~2 us) between launches -- 20 % of a
    * 128^3 transform */
   for (int i = 0; i < 3; i++) {
     if (st->timed) be->event_record(st->evp[i], s);
-    if (be->pass(&d[i], src[i], dst[i], s)) return -1;
+    if (be->pass(&ss.d[i], ss.src[i], ss.dst[i], s)) return -1;
   }
   if (st->timed) be->event_record(st->evp[3], s);
   return 0;
@@ -2079,19 +2054,12 @@ static int mirror_step(hip_state *st, const step_list *L, int i, void *sx) {
   const offt_backend *be = st->be;
   const step *e = &L->v[i];
   if (e->kind == 0) {
-    offt_pass_desc d = e->d, f = e->d;
-    d.direction = +1;
-    d.in_axis_stride = f.out_axis_stride; d.in_col_stride = f.out_col_stride; d.in_b1_stride = f.out_b1_stride; d.in_b2_stride = f.out_b2_stride;
-    d.out_axis_stride = f.in_axis_stride; d.out_col_stride = f.in_col_stride; d.out_b1_stride = f.in_b1_stride; d.out_b2_stride = f.in_b2_stride;
-    d.in_split = f.out_split; d.in_split_nfloor = f.out_split_nfloor; d.in_block_stride = f.out_block_stride;
-    d.out_split = f.in_split; d.out_split_nfloor = f.in_split_nfloor; d.out_block_stride = f.in_block_stride;
-    d.in_block_tab = f.out_block_tab; d.out_block_tab = f.in_block_tab;
-    d.in_contig = f.out_contig; d.out_contig = f.in_contig;
-    if (f.real_input == 1) d.real_input = 2; /* real input -> real output: the complex-to-real inverse's z pass */
+    offt_pass_desc d = e->d;
+    desc_mirror(&d);
     d.scale = e->first ? st->out_scale : 1.0;
     /* cache hint: forward, a pass with out_keep is followed by the pass that re-reads its output; mirrored, that
      * follower is the producer and this one the consumer */
-    d.out_keep = (i > 0 && L->v[i - 1].kind == 0 && L->v[i - 1].d.out_keep && !f.out_keep) ? 1 : 0;
+    d.out_keep = (i > 0 && L->v[i - 1].kind == 0 && L->v[i - 1].d.out_keep && !e->d.out_keep) ? 1 : 0;
     return be->pass(&d, e->dst, (void *)e->src, sx);
   }
   if (e->kind == 2)
@@ -2862,7 +2830,9 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
   fl->kind = kind;
   fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
   fl->b1_stride = l->out_b1_stride; fl->b2_stride = l->out_b2_stride;
-  /* the inverse's first pass must store where the forward's last one loads, with the same addressing */
+  /* the inverse's first pass must store where the forward's last one loads, with the same addressing.  Where the inverse
+   * is the forward schedule mirrored (single_schedule) that holds by construction; the one schedule that keeps its launch
+   * order, in-place x-y-z on a complex plan, starts its inverse with the z pass and has no fused route */
   if (iv->dst[0] != fw->src[2] || f0->n != l->n || f0->ncols != l->ncols || f0->nb1 != l->nb1 || f0->nb2 != l->nb2 ||
       f0->out_axis_stride != l->in_axis_stride || f0->out_col_stride != l->in_col_stride || f0->out_b1_stride != l->in_b1_stride ||
       f0->out_b2_stride != l->in_b2_stride)
@@ -2888,13 +2858,8 @@ static int execute_convolve_single(struct _offt_plan *po, void *data, const void
   const offt_pass_desc *py = &fw.d[1], *qy = &iv.d[1];
   const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
   int ng = 0;
-  if (fw.zyx && py->nb1 == cnt && fd.nb1 == cnt && qy->nb1 == cnt &&
-      (st->opt.zgroup_mib >= 0 || (po->Nx <= 1024 && po->Ny <= 1024 && (g_backend || offt_hipk_keeps_output(py))))) {
-    const int group_mib = st->opt.zgroup_mib >= 0 ? st->opt.zgroup_mib : 256;
-    const double plane_mib = (double)po->Nx * po->Ny * (double)st->esz / (1024.0 * 1024.0);
-    ng = group_mib > 0 ? (int)((double)group_mib / plane_mib) : 0;
-    if (ng > cnt) ng = cnt;
-  }
+  if (fw.zyx && py->nb1 == cnt && fd.nb1 == cnt && qy->nb1 == cnt)
+    ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, py);
   if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
   if (ng >= 1) {
     for (int z0 = 0; z0 < cnt; z0 += ng) {
