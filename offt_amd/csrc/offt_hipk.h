@@ -89,9 +89,6 @@ int offt_hipk_keeps_output(const offt_pass_desc *d);
 /* 1 if a register/LDS Stockham panel kernel exists for (n, precision): powers of two up to 4096
  * and the swept 2^a 3^b 5^c lengths; 0 if the pass will run on the any-length kernel.        */
 int offt_hipk_has_fast_path(int n, int precision);
-/* 1 if lines of n points have no single-launch kernel and run as a four-step decomposition n = n1 n2 (two sub-passes and a
- * twiddle sweep through scratch; complex input only).  Valid after offt_hipk_prepare(n, precision).                    */
-int offt_hipk_is_four_step(int n, int precision);
 /* number of sweep variants registered for (n, precision, in_contig, out_contig) */
 int offt_hipk_variant_count(int n, int precision);
 /* human-readable description of a variant, for sweep logs                      */
@@ -99,7 +96,9 @@ const char *offt_hipk_variant_name(int n, int precision, int variant);
 /* panel shape of a variant (variant = -1: the default): elements per thread and columns
  * per workgroup; returns the variant id or -1 if (n, precision, variant) does not exist  */
 int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thread, int *cols);
-/* name of the kernel symbol a descriptor resolves to (for rocprof matching)    */
+/* name of the kernel symbol a descriptor resolves to as ONE launch (for rocprof matching): the direct layer of the
+ * launcher's resolve().  A pass that is decomposed (four-step, lines through scratch) launches several kernels and is
+ * named by the kernel that would take its descriptor alone.                      */
 const char *offt_hipk_kernel_name(const offt_pass_desc *d);
 /* ---- spectral convolution (offt_hip_execute_convolve) ------------------------------------------------------------------
  * A filter H laid out like a forward pass's OUTPUT: kind 0 = one real scalar of the pass's precision per complex slot

@@ -381,6 +381,31 @@ fill_real_k(T *buf, int kind, int n0, int n1, int n2, int s0, int s1, int s2, lo
 // ---------------------------------------------------------------------------
 // host side: kernel registry lookup, twiddle tables, launchers
 // ---------------------------------------------------------------------------
+// Environment switches of the launcher, read once at first use.  A switch that is "on" by default is on when unset or
+// non-zero (atoi); the hipRTC library path (OFFT_HIPRTC_LIB) stays with its loader, rtc_load().
+struct Env {
+  static int num(const char *name, int dflt) { const char *s = getenv(name); return s ? atoi(s) : dflt; }
+  static int positive(const char *name, int dflt) { const int v = num(name, dflt); return v > 0 ? v : dflt; }
+  const bool rtc = num("OFFT_RTC", 1) != 0;                              // plan-time kernels through hipRTC
+  const int rtc_shapes = num("OFFT_RTC_SHAPES", 1);                      // shapes compiled per plan-time length (static sweep: up to 8)
+  const bool bluestein = num("OFFT_BLUESTEIN", 1) != 0;                  // Bluestein panel kernel, and the Bluestein lines through scratch
+  const int xcd_remap = num("OFFT_XCD_REMAP", 32);                       // XCD-aware panel order: 0 off, a power of two = run length G
+  const bool f32_pairs = num("OFFT_F32_PAIRS", 1) != 0;                  // single-precision column-pair kernels
+  const bool keep_stores = num("OFFT_KEEP_STORES", 1) != 0;              // cache-keeping twins for out_keep descriptors
+  const bool fourstep = num("OFFT_FOURSTEP", 1) != 0;                    // four-step decomposition
+  const int fourstep_n1 = num("OFFT_FOURSTEP_N1", 0);                    // force the first factor of a four-step split (sweeps)
+  const int fourstep_chunk_mib = positive("OFFT_FOURSTEP_CHUNK_MIB", 192);  // scratch per four-step chunk
+  const bool fourstep_fuse = num("OFFT_FOURSTEP_FUSE", 1) != 0;          // four-step twiddles on the first sub-pass's stores
+  const bool bluestein_long = num("OFFT_BLUESTEIN_LONG", 1) != 0;        // Bluestein lines through scratch for lengths without a split
+  const bool bluestein_long_pow2 = num("OFFT_BLUESTEIN_LONG_POW2", 0) != 0;  // ... on M = 2^k only, not the shortest (64 | 32) x L
+  const bool r2c_bluestein = num("OFFT_R2C_BLUESTEIN", 1) != 0;          // real lines of a Bluestein length through scratch (0: any-length kernel)
+  const int mix_threads = num("OFFT_MIX_THREADS", 0);                    // workgroup size of the any-length kernel (64 .. 1024), 0 = by LDS footprint
+};
+const Env &env() { static const Env e; return e; }
+
+// LDS of a CU: what the any-length kernel can use, and the budget of the plan-time panel shapes
+constexpr size_t LDS_BYTES = 160 * 1024;
+
 std::once_flag g_reg_once;
 void build_registry() {
   registry().reserve(8192);  // plan-time instances are appended later: no reallocation under a concurrent lookup
@@ -477,7 +502,7 @@ bool rtc_load() {
     const size_t sl = dir.rfind('/');
     if (sl != std::string::npos) cand.push_back(dir.substr(0, sl + 1) + "libhiprtc.so");
   }
-  if (getenv("OFFT_HIPRTC_LIB")) cand.insert(cand.begin(), getenv("OFFT_HIPRTC_LIB"));
+  if (const char *lib = getenv("OFFT_HIPRTC_LIB")) cand.insert(cand.begin(), lib);
   cand.push_back("libhiprtc.so");
   cand.push_back("/opt/rocm/lib/libhiprtc.so");
   for (auto &c : cand) {
@@ -532,8 +557,8 @@ bool choose_shapes(int N, int prec, int want, std::vector<Shape> *out) {
         const size_t ex = nst > 1 ? (size_t)cols * lstride * esz : 0;
         const size_t qt = N % 4 == 0 ? N / 4 + 1 : N;
         const size_t lds = nst > 1 ? (ex + 15) / 16 * 16 + qt * 2 * esz : 0;
-        if (emax > emax_cap || emax < 6 || lds > 160 * 1024 || eff < 0.74) continue;
-        size_t wg = lds ? (160 * 1024) / lds : 4;
+        if (emax > emax_cap || emax < 6 || lds > LDS_BYTES || eff < 0.74) continue;
+        size_t wg = lds ? LDS_BYTES / lds : 4;
         wg = wg < 1 ? 1 : (wg > 4 ? 4 : wg);
         const int waves = (int)wg * cdiv_i(nt, 64);
         if (waves < 4) continue;
@@ -576,11 +601,6 @@ bool choose_shapes(int N, int prec, int want, std::vector<Shape> *out) {
   return !out->empty();
 }
 
-bool rtc_enabled() {
-  static const bool on = !(getenv("OFFT_RTC") && atoi(getenv("OFFT_RTC")) == 0);
-  return on;
-}
-
 // compile and register fft_panelx_k<T, n, shape> for the four flavours; 0 on success.  c2r: the two real-output flavours
 // of the default shape instead (the complex instances exist already)
 int rtc_build(int n, int prec, bool c2r = false) {
@@ -594,7 +614,7 @@ int rtc_build(int n, int prec, bool c2r = false) {
     return -1;
   };
   if (!rtc_load()) return fail("hipRTC library not found", "");
-  static const int nshapes = getenv("OFFT_RTC_SHAPES") ? atoi(getenv("OFFT_RTC_SHAPES")) : 1;
+  const int nshapes = env().rtc_shapes;
   std::vector<Shape> shapes;
   if (!choose_shapes(n, prec, c2r || nshapes < 1 ? 1 : (nshapes > 8 ? 8 : nshapes), &shapes)) return fail("no panel shape fits", "");
   const char *T = prec == OFFT_PREC_F64 ? "double" : "float";
@@ -739,10 +759,6 @@ struct BlueTab { void *chirp = nullptr, *bhat = nullptr; int m = 0; };
 std::mutex g_blue_mu;
 std::map<std::pair<int, int>, BlueTab> g_blue;
 
-bool blue_enabled() {
-  static const bool on = !(getenv("OFFT_BLUESTEIN") && atoi(getenv("OFFT_BLUESTEIN")) == 0);
-  return on;
-}
 int blue_m(int n) {
   int m = 256;
   while (m < 2 * n - 1) m <<= 1;
@@ -760,6 +776,24 @@ bool blue_lookup(int n, int prec, BlueTab *out) {
   if (it == g_blue.end()) return false;
   *out = it->second;
   return true;
+}
+
+// ---- length facts: what a length can run on, as far as the registry and the switches say (no device state) ----
+size_t elem_size(int prec) { return prec == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2); }
+// two images of a line fit the LDS of the any-length kernel (5120 double / 10240 single points)
+bool fits_any_length(int n, int prec) { return 2 * (size_t)n * elem_size(prec) <= LDS_BYTES; }
+bool has_panel(int n, int prec) { return find_variant(n, prec, true, true, -1) != nullptr; }
+int max_prime_factor(int n) {
+  int maxp = 1;
+  for (int p = 2; p * p <= n; ++p) while (n % p == 0) { maxp = p > maxp ? p : maxp; n /= p; }
+  return n > maxp ? n : maxp;
+}
+// a 31-smooth length of 256 .. 4096 points can get a panel kernel compiled at plan time
+bool rtc_candidate(int n) { return env().rtc && n >= 256 && n <= 4096 && smooth13(n); }
+// a length with a prime factor > 13 runs as a Bluestein convolution on a power-of-two panel kernel when 2n - 1 <= 4096
+// (lengths built from primes <= 13 stay on the any-length kernel, whose small-radix stages are whole butterflies)
+bool blue_panel_candidate(int n, int prec, bool inc, bool outc) {
+  return env().bluestein && n >= 32 && n <= 2048 && max_prime_factor(n) > 13 && find_blue(blue_m(n), prec, inc, outc) != nullptr;
 }
 
 // convolution length of a Bluestein line through scratch (long_pass): not the next power of two -- up to twice 2n - 1 -- but
@@ -813,11 +847,11 @@ int blue_build(int n, int prec, BlueTab &tb, int m_override = 0) {
 // XCD-aware panel order (panel_of_block): runs of G = 32 neighbouring panels per XCD by default,
 // OFFT_XCD_REMAP=0 turns it off, OFFT_XCD_REMAP=<power of two> sets G
 void xcd_order(long long nblk, unsigned *lim, unsigned *gshift) {
-  static const int env = getenv("OFFT_XCD_REMAP") ? atoi(getenv("OFFT_XCD_REMAP")) : 32;
+  const int g = env().xcd_remap;
   unsigned gs = 0;
-  while (env > 1 && (2 << gs) <= env) ++gs;
+  while (g > 1 && (2 << gs) <= g) ++gs;
   *gshift = gs;
-  *lim = env > 0 ? (unsigned)((nblk >> (gs + 3)) << (gs + 3)) : 0u;
+  *lim = g > 0 ? (unsigned)((nblk >> (gs + 3)) << (gs + 3)) : 0u;
 }
 
 // Column-pair kernels (T = f32x2, offt_panel.hpp) take a descriptor with an even column count whose strided sides put the
@@ -844,9 +878,8 @@ Variant *pick_variant0(const offt_pass_desc *d, bool allow_pair) {
   const bool inc = d->in_contig != 0, outc = d->out_contig != 0, r2c = d->real_input == 1, c2r = d->real_input == 2;
   const bool uneven = d->in_split_nfloor > 0 || d->out_split_nfloor > 0;
   const bool odd_split = (d->in_split && !is_pow2(d->in_split)) || (d->out_split && !is_pow2(d->out_split));
-  static const bool pairs_on = !(getenv("OFFT_F32_PAIRS") && atoi(getenv("OFFT_F32_PAIRS")) == 0);
   int want = d->variant;
-  if (want >= VARIANT_PAIR0 || (want < 0 && pairs_on && !d->no_pairs)) {
+  if (want >= VARIANT_PAIR0 || (want < 0 && env().f32_pairs && !d->no_pairs)) {
     if (allow_pair && !uneven && !odd_split && pair_ok(d)) {
       Variant *p = find_variant(d->n, OFFT_PREC_F32_PAIR, inc, outc, want < 0 ? -1 : want - VARIANT_PAIR0);
       if (p && (want >= 0 ? p->id == want - VARIANT_PAIR0 : p->is_default)) return p;
@@ -869,15 +902,12 @@ Variant *pick_variant(const offt_pass_desc *d, bool allow_pair = true) {
     return find_variant(d->n, d->precision, false, false, -1, false, false, true);
   }
   Variant *v = pick_variant0(d, allow_pair);
-  static const bool keep_on = !(getenv("OFFT_KEEP_STORES") && atoi(getenv("OFFT_KEEP_STORES")) == 0);
-  if (v && d->out_keep && keep_on && !v->mixed && !v->r2c && !v->c2r) {
+  if (v && d->out_keep && env().keep_stores && !v->mixed && !v->r2c && !v->c2r) {
     Variant *k = find_variant(v->n, v->prec, v->inc, v->outc, v->id, false, true);
     if (k && k->keep && k->id == v->id) return k;
   }
   return v;
 }
-
-bool fast_ok(const offt_pass_desc *d) { return pick_variant(d) != nullptr; }
 
 // 1 if the descriptor, with out_keep set, runs on a kernel whose stores stay cached (a KEEP twin exists for its shape)
 extern "C" int offt_hipk_keeps_output(const offt_pass_desc *d) {
@@ -886,8 +916,6 @@ extern "C" int offt_hipk_keeps_output(const offt_pass_desc *d) {
   const Variant *v = pick_variant(&k);
   return v && v->keep;
 }
-
-int log2i(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 
 // ---------------------------------------------------------------------------
 // Four-step decomposition: lines no single kernel takes.
@@ -930,11 +958,8 @@ bool four_lookup(int n, int prec, FourStep *out) {
 
 // a single launch can transform lines of n points: a panel kernel, the Bluestein kernel, or the any-length kernel
 bool direct_ok(int n, int prec) {
-  if (find_variant(n, prec, true, true, -1)) return true;
   BlueTab bt;
-  if (blue_lookup(n, prec, &bt)) return true;
-  const size_t esz = prec == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
-  return 2 * (size_t)n * esz <= (size_t)160 * 1024;
+  return has_panel(n, prec) || blue_lookup(n, prec, &bt) || fits_any_length(n, prec);
 }
 
 void *four_scratch(void *stream, int which, size_t bytes) {
@@ -995,7 +1020,6 @@ __global__ void __launch_bounds__(256) four_twiddle_t_k(const V2 *sp, V2 *s, con
   }
 }
 
-int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const FourStep &fs);
 // ---------------------------------------------------------------------------
 // Lines through a dense scratch: the last net under "FFTW plans any length".
 //   * a line no single launch takes and no four-step split fits (a prime beyond the any-length kernel, or a prime factor
@@ -1078,368 +1102,207 @@ long_scatter_k(GenArgs a, const typename vec2<T>::type *U, typename vec2<T>::typ
   else dst[split_off(k, a.out_split, a.out_nfloor, a.out_blk, a.out_axis, a.out_tab)] = o;
 }
 
-int long_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const LongTab &lt);
-
-}  // namespace
-
-extern "C" {
-
-const char *offt_hipk_last_error(void) { return g_err; }
-
-int offt_hipk_has_fast_path(int n, int precision) {
-  return find_variant(n, precision, true, true, -1) != nullptr;
-}
-
-/* 1 if lines of n points run as a four-step decomposition (no single launch takes them): complex input only */
-int offt_hipk_is_four_step(int n, int precision) {
-  const size_t esz = precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
-  return four_lookup(n, precision, nullptr) && !find_variant(n, precision, true, true, -1) && 2 * (size_t)n * esz > (size_t)160 * 1024;
-}
-
-int offt_hipk_variant_count(int n, int precision) {
-  std::call_once(g_reg_once, build_registry);
-  int c = 0;
-  for (auto &v : registry())
-    if (v.n == n && v.prec == precision && v.inc && v.outc && !v.r2c && !v.c2r && !v.conv && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
-  return c;
-}
-
-const char *offt_hipk_variant_name(int n, int precision, int variant) {
-  Variant *v = find_variant(n, precision, true, true, variant);
-  return v ? v->name.c_str() : "mixed-radix any-length";
-}
-
-int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thread, int *cols) {
-  Variant *v = find_variant(n, precision, true, true, variant);
-  if (!v || (variant >= 0 && v->id != variant)) return -1;
-  if (elems_per_thread) *elems_per_thread = v->e;
-  if (cols) *cols = v->cols;
-  return v->id;
-}
-
-const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
-  const Variant *v = pick_variant(d);
+// ---------------------------------------------------------------------------
+// Which kernel runs a pass.  resolve() is the one place that decides it, and its body IS the order of precedence; the
+// launchers below only pack arguments.  Two layers: the decomposing routes (four-step, lines through scratch) launch
+// sub-passes that come back through offt_hipk_fft_pass, the direct routes are one launch.
+// ---------------------------------------------------------------------------
+enum class Via { FourStep, ScratchLines, Panel, BluePanel, AnyLength };
+struct Route {
+  Via via = Via::AnyLength;
+  Variant *v = nullptr;       // Panel
+  BlueVariant *bv = nullptr;  // BluePanel, on the tables bt
   BlueTab bt;
-  if (!v) return (!d->real_input && blue_lookup(d->n, d->precision, &bt) && find_blue(bt.m, d->precision, d->in_contig != 0, d->out_contig != 0)) ? "fft_bluestein_k" : "fft_mixed_k";
-  if (v->c2r) return v->mixed ? "fft_c2r_panelx_k" : "fft_c2r_panel_k";
-  return v->mixed ? "fft_panelx_k" : (v->prec == OFFT_PREC_F32_PAIR ? "fft_panel_k<pairs>" : "fft_panel_k");
-}
+  FourStep fs;                // FourStep
+  LongTab lt;                 // ScratchLines; lt.m == 0: plain complex lines of n points, no Bluestein convolution
+};
 
-int offt_hipk_prepare(int n, int precision) {
-  const bool c2r = (precision & OFFT_HIPK_PREP_C2R) != 0;
-  precision &= ~OFFT_HIPK_PREP_C2R;
-  if (n < 1) { snprintf(g_err, sizeof g_err, "offt_hipk_prepare: bad n=%d", n); return -1; }
-  if (c2r) {
-    if (offt_hipk_prepare(n, precision)) return -1;
-    // real-output instances for a length whose panel kernel was compiled at plan time (the precompiled lengths have theirs);
-    // best effort like the complex ones: without them the real-output pass runs on the any-length kernel
-    const Variant *v = find_variant(n, precision, true, true, -1);
-    if (v && v->modfn && rtc_enabled()) (void)rtc_build(n, precision, true);
-    return 0;
-  }
-  Tables tb;
-  if (get_tables(n, precision, tb, true)) return -1;
-  // a 31-smooth length of 256 .. 4096 points without a precompiled panel kernel gets one now (best effort)
-  if (rtc_enabled() && n >= 256 && n <= 4096 && smooth13(n) && !find_variant(n, precision, true, true, -1)) (void)rtc_build(n, precision);
-  // a length without any register kernel (a prime factor > 31, or outside 256 .. 4096 and not precompiled) runs as a
-  // Bluestein convolution on a power-of-two panel kernel when 2n - 1 <= 4096
-  // (lengths built from primes <= 13 stay on the any-length kernel, whose small-radix stages are whole butterflies)
-  int maxp = 1;
-  { int m = n; for (int p = 2; p * p <= m; ++p) while (m % p == 0) { maxp = p > maxp ? p : maxp; m /= p; } if (m > 1 && m > maxp) maxp = m; }
-  if (blue_enabled() && n >= 32 && n <= 2048 && maxp > 13 && !find_variant(n, precision, true, true, -1) && find_blue(blue_m(n), precision, true, true)) {
-    std::lock_guard<std::mutex> lk(g_blue_mu);
-    if (!g_blue.count(std::make_pair(n, precision))) {
-      BlueTab bt;
-      const int rc = precision == OFFT_PREC_F64 ? blue_build<double>(n, precision, bt) : blue_build<float>(n, precision, bt);
-      if (rc) return -1;
-      g_blue[std::make_pair(n, precision)] = bt;
-    }
-  }
-  // a length no single launch takes (no panel kernel, and two images of a line do not fit the LDS of the any-length
-  // kernel) is split n = n1 n2 for the four-step path above; 8192 has a register kernel, but with one column per
-  // workgroup: its strided flavours go the four-step way as well.  Only a length without such a split -- a prime, or a
-  // prime factor too large itself -- is refused, HERE, at plan time: offt_3d_init returns NULL instead of every execute failing
-  const size_t esz = precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
-  const bool no_direct = !find_variant(n, precision, true, true, -1) && 2 * (size_t)n * esz > (size_t)160 * 1024;
-  static const bool four_on = !(getenv("OFFT_FOURSTEP") && atoi(getenv("OFFT_FOURSTEP")) == 0);
-  // ... and so does a length that would otherwise run on the any-length kernel -- above the plan-time kernels' range (4800,
-  // 5000; in single precision up to 10240 points: 10000 at 15 % of the roofline there) or above the Bluestein panel kernel's with
-  // a large prime factor (4076 = 4 x 1019) -- if it has a FUSED split (score < 0 below)
-  BlueTab bt_any;
-  const bool any_only = !no_direct && n > 2048 && !find_variant(n, precision, true, true, -1) && !blue_lookup(n, precision, &bt_any);
-  if ((no_direct || n == 8192 || any_only) && four_on && !four_lookup(n, precision, nullptr)) {
-    int best1 = 0;
-    double best_score = 1e30;
-    const int forced_n1 = getenv("OFFT_FOURSTEP_N1") ? atoi(getenv("OFFT_FOURSTEP_N1")) : 0;
-    for (int n1 = 2; (long long)n1 * n1 <= n; ++n1) {
-      if (n % n1) continue;
-      const int n2 = n / n1;
-      // both factors need a kernel of their own: prefer precompiled register kernels and a balanced split (candidates are
-      // only looked up here, not prepared -- preparing may compile a plan-time kernel, seconds each)
-      const bool f1 = find_variant(n1, precision, true, true, -1) != nullptr, f2 = find_variant(n2, precision, true, true, -1) != nullptr;
-      if ((!f1 && 2 * (size_t)n1 * esz > (size_t)160 * 1024) || (!f2 && 2 * (size_t)n2 * esz > (size_t)160 * 1024)) continue;
-      double score = std::log((double)n2 / (double)n1);
-      if (!f1) score += 4.0;
-      if (!f2) score += 4.0;
-      // ... except that a SHORT first sub-pass with the twiddles on its stores wins when the other factor still has a register
-      // kernel: few points per line, one thread per line on 64 unit-stride columns (8 columns at 64 points).  Order of
-      // preference, from sweeps over 8192 / 16384 / 32768 / 6000 / 10000 / 12000 points (profiles/r03_four_step.txt):
-      //   double  64 (8192 = 64 x 128: 37.3 % of the roofline, 36.4 % for 32 x 256), then 16, 8, 4 (6000 = 16 x 375: 31.5 %, 10000 =
-      //           16 x 625: 31.6 %, both 17-18 % as balanced unfused splits; 12000 = 16 x 750: 26.7 %, 20.1 % for 32 x 375), 32, 2
-      //   single  32 (8192 = 32 x 256: 37.5 %, 31.9 % for 64 x 128), then 16, 8, 4, 2
-      static const int pref64[] = {64, 16, 8, 4, 32, 2, 0}, pref32[] = {32, 16, 8, 4, 2, 0};
-      const int *pref = precision == OFFT_PREC_F64 ? pref64 : pref32;
-      // (second choice, behind every split whose long factor is precompiled: a long factor that gets its kernel compiled NOW --
-      //  seconds of plan time for 10000 = 16 x 625 at 32 % instead of 100 x 100 at 18 %)
-      const bool rtc2 = !f2 && rtc_enabled() && n2 >= 256 && n2 <= 4096 && smooth13(n2);
-      // (third: a long factor with a prime factor > 13 that runs on the Bluestein panel kernel -- 4076 = 4 x 1019)
-      int maxp2 = 1;
-      { int m = n2; for (int p = 2; p * p <= m; ++p) while (m % p == 0) { maxp2 = p > maxp2 ? p : maxp2; m /= p; } if (m > maxp2) maxp2 = m; }
-      const bool blue2 = !f2 && !rtc2 && blue_enabled() && n2 >= 32 && n2 <= 2048 && maxp2 > 13 && find_blue(blue_m(n2), precision, true, false) != nullptr &&
-                         find_blue(blue_m(n2), precision, false, false) != nullptr;
-      for (int r = 0; pref[r]; ++r)
-        if (n1 == pref[r] && (f2 || rtc2 || blue2) && find_variant(n1, precision, false, false, -1, false, false, true))
-          score = (f2 ? -10.0 : rtc2 ? -5.0 : -3.0) + 0.1 * r;
-      // a factor that would itself go through scratch lines (or the any-length kernel with a radix of hundreds) is a last resort
-      { int mp1 = 1, m = n1; for (int p = 2; p * p <= m; ++p) while (m % p == 0) { mp1 = p > mp1 ? p : mp1; m /= p; } if (m > mp1) mp1 = m;
-        if (!f1 && mp1 > 61 && !(n1 <= 2048 && blue_enabled())) score += 8.0; }
-      if (!f2 && !rtc2 && !blue2 && maxp2 > 61 && !(n2 <= 2048 && blue_enabled())) score += 8.0;
-      if (forced_n1 == n1) score = -100.0;  // (OFFT_FOURSTEP_N1, for sweeps: only among the splits that are possible at all)
-      if (score < best_score) { best_score = score; best1 = n1; }
-    }
-    if (any_only && best_score >= 0.0) best1 = 0;  // (unfused, three sweeps: the any-length kernel is no worse)
-    if (best1 && (offt_hipk_prepare(best1, precision) || offt_hipk_prepare(n / best1, precision) ||
-                  !direct_ok(best1, precision) || !direct_ok(n / best1, precision)))
-      best1 = 0;
-    if (best1) {
-      FourStep fs; fs.n1 = best1; fs.n2 = n / best1;
-      fs.all = !find_variant(n, precision, true, true, -1);
-      HIPK_CHECK(hipMalloc(&fs.t4, (size_t)n * esz));
-      (void)hipGetLastError();
-      if (precision == OFFT_PREC_F64) hipLaunchKernelGGL(four_table_k<double2>, dim3((n + 255) / 256), dim3(256), 0, nullptr, (double2 *)fs.t4, (const double2 *)tb.full, n, fs.n2);
-      else hipLaunchKernelGGL(four_table_k<float2>, dim3((n + 255) / 256), dim3(256), 0, nullptr, (float2 *)fs.t4, (const float2 *)tb.full, n, fs.n2);
-      HIPK_CHECK(hipGetLastError());
-      HIPK_CHECK(hipStreamSynchronize(nullptr));
-      std::lock_guard<std::mutex> lk(g_four_mu);
-      g_four[std::make_pair(n, precision)] = fs;
-    }
-  }
-  // ... and a length without a split becomes a Bluestein convolution on lines of M = 2^k >= 2n - 1 points through scratch
-  static const bool long_on = !(getenv("OFFT_BLUESTEIN_LONG") && atoi(getenv("OFFT_BLUESTEIN_LONG")) == 0);
-  // (also a length the any-length kernel COULD take, but only with a radix of hundreds -- r multiply-adds per output: 3057 =
-  //  3 x 1019 points ran at 0.6 % of the roofline there)
-  if ((no_direct || (any_only && maxp > 61)) && !four_lookup(n, precision, nullptr) && long_on && four_on /* (its M-point lines need the four-step path) */ && blue_enabled() && n < (1 << 24) && !long_lookup(n, precision, nullptr)) {
-    BlueTab bt;
-    static const bool short_m = !(getenv("OFFT_BLUESTEIN_LONG_POW2") && atoi(getenv("OFFT_BLUESTEIN_LONG_POW2")) != 0);
-    const int mlong = short_m ? blue_m_long(n, precision) : 0;
-    const int rc = precision == OFFT_PREC_F64 ? blue_build<double>(n, precision, bt, mlong) : blue_build<float>(n, precision, bt, mlong);
-    if (!rc) {
-      std::lock_guard<std::mutex> lk(g_long_mu);
-      LongTab lt; lt.chirp = bt.chirp; lt.bhat = bt.bhat; lt.m = bt.m;
-      g_long[std::make_pair(n, precision)] = lt;
-    }
-  }
-  if (no_direct && !four_lookup(n, precision, nullptr) && !long_lookup(n, precision, nullptr)) {
-    snprintf(g_err, sizeof g_err, "no kernel for lines of %d %s points: no register kernel, the any-length kernel holds at most %zu, and %d has no "
-             "factorisation n1 n2 into lengths that have one", n, precision == OFFT_PREC_F64 ? "double-complex" : "single-complex",
-             (size_t)160 * 1024 / (2 * esz), n);
-    return -1;
-  }
-  return 0;
-}
-
-int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (d->n < 1 || d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;  // empty batch: nothing to do
-  if (d->n == 1 && d->scale == 1.0 && in == out && d->in_axis_stride == d->out_axis_stride &&
-      d->in_col_stride == d->out_col_stride && d->in_b1_stride == d->out_b1_stride &&
-      d->in_b2_stride == d->out_b2_stride)
-    return 0;
-  Tables tb;
-  if (get_tables(d->n, d->precision, tb, false)) return -1;
-  {
-    FourStep fs;
-    if (four_lookup(d->n, d->precision, &fs)) {
-      const size_t esz4 = d->precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
-      const bool no_direct = !find_variant(d->n, d->precision, true, true, -1) && 2 * (size_t)d->n * esz4 > (size_t)160 * 1024;
-      // a length the any-length kernel could take as well stays there for what the decomposition does not follow: real
-      // input, per-peer blocks that are not whole runs of n2 inputs / n1 outputs
-      const bool follows = !d->real_input && !(d->in_split && (d->in_split_nfloor || d->in_split % fs.n2)) &&
-                           !(d->out_split && (d->out_split_nfloor || d->out_split % fs.n1));
-      if (no_direct || (fs.all ? follows : !(d->in_contig && d->out_contig))) return four_pass(d, in, out, stream, fs);
-    }
-    LongTab lt;
-    if (long_lookup(d->n, d->precision, &lt)) return long_pass(d, in, out, stream, lt);
-  }
-  Variant *v = pick_variant(d);
-  if (v && v->prec == OFFT_PREC_F32_PAIR &&
+// the direct layer: the single launch that takes the descriptor (what offt_hipk_kernel_name names)
+void resolve_direct(const offt_pass_desc *d, const void *in, const void *out, Route *r) {
+  // 1. a panel kernel (column pairs, any-split instance, cache-keeping twin, plan-time instance: pick_variant)
+  r->v = pick_variant(d);
+  if (r->v && r->v->prec == OFFT_PREC_F32_PAIR &&
       ((!d->in_contig && ((uintptr_t)in & 15)) || (!d->out_contig && ((uintptr_t)out & 15))))
-    v = pick_variant(d, false);  // a strided side off the 16-B grid: the one-column kernels
-  BlueTab bt;
-  BlueVariant *bv = nullptr;
-  if (!v && !d->real_input && blue_lookup(d->n, d->precision, &bt)) bv = find_blue(bt.m, d->precision, d->in_contig != 0, d->out_contig != 0);
-  // a REAL-input (or real-output) line of a Bluestein length: gathered as complex lines into scratch, transformed there by
-  // the Bluestein panel kernel, the first n/2 + 1 outputs (the n real parts) scattered -- three sweeps, against a radix of the size of its largest prime
-  // factor on the any-length kernel (OFFT_R2C_BLUESTEIN=0: that kernel, as in rounds 1-2)
-  static const bool r2c_blue = !(getenv("OFFT_R2C_BLUESTEIN") && atoi(getenv("OFFT_R2C_BLUESTEIN")) == 0);
-  if (!v && d->real_input && r2c_blue && blue_lookup(d->n, d->precision, &bt) && find_blue(bt.m, d->precision, true, true)) {
-    LongTab plain;
-    return long_pass(d, in, out, stream, plain);
+    r->v = pick_variant(d, false);  // a strided side off the 16-B grid: the one-column kernels
+  if (r->v) { r->via = Via::Panel; return; }
+  // 2. Bluestein: the M-point panel machinery on a complex line of n points (offt_bluestein.hpp)
+  if (!d->real_input && blue_lookup(d->n, d->precision, &r->bt) &&
+      (r->bv = find_blue(r->bt.m, d->precision, d->in_contig != 0, d->out_contig != 0)) != nullptr) {
+    r->via = Via::BluePanel;
+    return;
   }
-  // a real-output line of a length beyond the any-length kernel whose descriptor no panel kernel takes (8192 points with
-  // blocks fft_panel_k cannot address): through scratch lines, like the four-step route of such a line
-  if (!v && d->real_input == 2 && 2 * (size_t)d->n * (d->precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2)) > (size_t)160 * 1024) {
-    LongTab plain;
-    return long_pass(d, in, out, stream, plain);
+  // 3. the any-length kernel
+  r->via = Via::AnyLength;
+}
+
+Route resolve(const offt_pass_desc *d, const void *in, const void *out) {
+  Route r;
+  // 1. four-step: a length no single launch takes (no panel kernel, and two images of a line do not fit the LDS) always;
+  //    8192 points (a register kernel with one column per workgroup) for its strided flavours; a length the any-length
+  //    kernel could take as well stays there for what the decomposition does not follow
+  if (four_lookup(d->n, d->precision, &r.fs)) {
+    const bool no_direct = !has_panel(d->n, d->precision) && !fits_any_length(d->n, d->precision);
+    // the decomposition follows complex lines whose per-peer split cuts the axis into whole runs of n2 inputs / n1 outputs
+    const bool follows = !d->real_input && !(d->in_split && (d->in_split_nfloor || d->in_split % r.fs.n2)) &&
+                         !(d->out_split && (d->out_split_nfloor || d->out_split % r.fs.n1));
+    if (no_direct || (r.fs.all ? follows : !(d->in_contig && d->out_contig))) {
+      // 2. ... and what it does not follow (real input or output: gathered as complex lines; uneven blocks: gathered with
+      //    the split) goes through scratch as plain contiguous lines of the same length
+      r.via = follows ? Via::FourStep : Via::ScratchLines;
+      return r;
+    }
   }
-  if (v || bv) {
-    PassArgs a;
-    const int cols = v ? v->cols : bv->cols;
-    a.in_axis = d->in_axis_stride; a.in_col = d->in_col_stride; a.in_b1 = d->in_b1_stride; a.in_b2 = d->in_b2_stride;
-    a.out_axis = d->out_axis_stride; a.out_col = d->out_col_stride; a.out_b1 = d->out_b1_stride; a.out_b2 = d->out_b2_stride;
-    a.in_blk = d->in_block_stride; a.out_blk = d->out_block_stride;
-    a.in_shift = d->in_split ? log2i(d->in_split) : 31;
-    a.out_shift = d->out_split ? log2i(d->out_split) : 31;
-    a.in_split = d->in_split; a.out_split = d->out_split;
-    a.in_inv = d->in_split ? 1.0f / (float)d->in_split : 0.0f;
-    a.out_inv = d->out_split ? 1.0f / (float)d->out_split : 0.0f;
-    a.in_nfloor = d->in_split_nfloor; a.out_nfloor = d->out_split_nfloor;
-    a.in_lim = d->in_split_nfloor ? d->in_split * d->in_split_nfloor : d->n;   // even split: every index below lim
-    a.out_lim = d->out_split_nfloor ? d->out_split * d->out_split_nfloor : d->n;
-    a.in_inv1 = 1.0f / (float)(d->in_split + 1);
-    a.out_inv1 = 1.0f / (float)(d->out_split + 1);
-    a.ncols = d->ncols;
-    a.ncp = (d->ncols + cols - 1) / cols;
-    a.nb1 = d->nb1;
-    a.conj = d->direction > 0;
-    a.scale = d->scale;
-    a.in_tab = d->in_split ? d->in_block_tab : nullptr;
-    a.out_tab = d->out_split ? d->out_block_tab : nullptr;
-    a.tw4 = d->tw4; a.tw4_b1 = d->tw4_b1; a.tw4_n2 = d->tw4_n2;
-    if (d->tw4 && !(v && v->tw4)) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no kernel with four-step twiddles for n=%d", d->n); return -1; }
-    long long nblk = (long long)a.ncp * d->nb1 * d->nb2;
-    if (nblk > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: grid too large"); return -1; }
-    xcd_order(nblk, &a.xcd_lim, &a.xcd_gshift);
-    if (bv) {  // Bluestein: the M-point panel machinery on a line of n points (offt_bluestein.hpp)
-      Tables tm;
-      if (get_tables(bt.m, d->precision, tm, false)) return -1;
-      int nlen = d->n;
-      void *args[] = {(void *)&a, (void *)&in, (void *)&out, (void *)&tm.full, (void *)&bt.chirp, (void *)&bt.bhat, (void *)&nlen};
-      if (!bv->attr_set) {
-        if (bv->lds > 48 * 1024)
-          HIPK_CHECK(hipFuncSetAttribute(bv->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bv->lds));
-        bv->attr_set = true;
-      }
-      HIPK_CHECK(hipLaunchKernel(bv->fn, dim3((unsigned)nblk), dim3(bv->threads), args, bv->lds, st));
-      return 0;
-    }
-    // every panel kernel stages its twiddles from the exact full-wave table w^m, m < n (the quarter- and half-wave
-    // tables they keep in LDS are prefixes of it)
-    void *args[] = {(void *)&a, (void *)&in, (void *)&out, (void *)&tb.full};
-    if (v->modfn) {  // plan-time instance: a module function
-      HIPK_CHECK(hipModuleLaunchKernel((hipFunction_t)v->modfn, (unsigned)nblk, 1, 1, v->threads, 1, 1, (unsigned)v->lds, st, args, nullptr));
-      return 0;
-    }
-    if (!v->attr_set) {
-      if (v->lds > 48 * 1024)
-        HIPK_CHECK(hipFuncSetAttribute(v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
-      v->attr_set = true;
-    }
-    HIPK_CHECK(hipLaunchKernel(v->fn, dim3((unsigned)nblk), dim3(v->threads), args, v->lds, st));
-    return 0;
-  }
-  // any-length path
+  // 3. a length without a split: a Bluestein convolution on M-point lines through scratch
+  if (long_lookup(d->n, d->precision, &r.lt)) { r.via = Via::ScratchLines; return r; }
+  // 4. one launch: panel kernel, Bluestein panel kernel, any-length kernel
+  resolve_direct(d, in, out, &r);
+  if (r.via != Via::AnyLength || !d->real_input) return r;
+  // 5. a REAL-input (or real-output) line of a Bluestein length: gathered as complex lines into scratch, transformed there by
+  //    the Bluestein panel kernel, the first n/2 + 1 outputs (the n real parts) scattered -- three sweeps, against a radix of the
+  //    size of its largest prime factor on the any-length kernel (OFFT_R2C_BLUESTEIN=0: that kernel, as in rounds 1-2)
+  if (env().r2c_bluestein && blue_lookup(d->n, d->precision, &r.bt) && find_blue(r.bt.m, d->precision, true, true)) r.via = Via::ScratchLines;
+  // 6. a real-output line of a length beyond the any-length kernel whose descriptor no panel kernel takes (8192 points with
+  //    blocks fft_panel_k cannot address): through scratch lines, like the four-step route of such a line
+  else if (d->real_input == 2 && !fits_any_length(d->n, d->precision)) r.via = Via::ScratchLines;
+  return r;
+}
+
+// ---- packing and launching ----
+int log2i(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
+
+// conv: fft_conv_panel_k works in place through the load side of contiguous lines without a split -- everything else stays zero
+PassArgs pass_args(const offt_pass_desc *d, int cols, bool conv = false) {
+  PassArgs a;
+  memset(&a, 0, sizeof a);
+  a.in_axis = d->in_axis_stride; a.in_col = d->in_col_stride; a.in_b1 = d->in_b1_stride; a.in_b2 = d->in_b2_stride;
+  a.in_shift = a.out_shift = 31;
+  a.ncols = d->ncols; a.ncp = (d->ncols + cols - 1) / cols; a.nb1 = d->nb1;
+  a.scale = d->scale;
+  if (conv) return a;
+  a.out_axis = d->out_axis_stride; a.out_col = d->out_col_stride; a.out_b1 = d->out_b1_stride; a.out_b2 = d->out_b2_stride;
+  a.in_blk = d->in_block_stride; a.out_blk = d->out_block_stride;
+  if (d->in_split) a.in_shift = log2i(d->in_split);
+  if (d->out_split) a.out_shift = log2i(d->out_split);
+  a.in_split = d->in_split; a.out_split = d->out_split;
+  a.in_inv = d->in_split ? 1.0f / (float)d->in_split : 0.0f;
+  a.out_inv = d->out_split ? 1.0f / (float)d->out_split : 0.0f;
+  a.in_nfloor = d->in_split_nfloor; a.out_nfloor = d->out_split_nfloor;
+  a.in_lim = d->in_split_nfloor ? d->in_split * d->in_split_nfloor : d->n;   // even split: every index below lim
+  a.out_lim = d->out_split_nfloor ? d->out_split * d->out_split_nfloor : d->n;
+  a.in_inv1 = 1.0f / (float)(d->in_split + 1);
+  a.out_inv1 = 1.0f / (float)(d->out_split + 1);
+  a.conj = d->direction > 0;
+  a.in_tab = d->in_split ? d->in_block_tab : nullptr;
+  a.out_tab = d->out_split ? d->out_block_tab : nullptr;
+  a.tw4 = d->tw4; a.tw4_b1 = d->tw4_b1; a.tw4_n2 = d->tw4_n2;
+  return a;
+}
+
+// the addressing of a descriptor for the any-length kernel and the gather / scatter sweeps of the scratch lines
+GenArgs gen_args(const offt_pass_desc *d) {
   GenArgs g;
+  memset(&g, 0, sizeof g);
   g.in_axis = d->in_axis_stride; g.in_col = d->in_col_stride; g.in_b1 = d->in_b1_stride; g.in_b2 = d->in_b2_stride;
   g.out_axis = d->out_axis_stride; g.out_col = d->out_col_stride; g.out_b1 = d->out_b1_stride; g.out_b2 = d->out_b2_stride;
   g.in_blk = d->in_block_stride; g.out_blk = d->out_block_stride;
   g.in_split = d->in_split; g.in_nfloor = d->in_split_nfloor;
   g.out_split = d->out_split; g.out_nfloor = d->out_split_nfloor;
   g.n = d->n; g.ncols = d->ncols; g.nb1 = d->nb1;
-  g.in_contig = d->in_contig; g.out_contig = d->out_contig;
   g.conj = d->direction > 0;
   g.real_in = d->real_input;
   g.scale = d->scale;
   g.in_tab = d->in_split ? d->in_block_tab : nullptr;
   g.out_tab = d->out_split ? d->out_block_tab : nullptr;
-  // radices: prime factors, pairs of 2 merged into 4 (fewer LDS round trips at equal cost)
-  g.nfac = 0;
-  {
-    int m = d->n, twos = 0;
-    while (m % 2 == 0) { twos++; m /= 2; }
-    for (; twos >= 2; twos -= 2) g.fac[g.nfac++] = 4;
-    if (twos) g.fac[g.nfac++] = 2;
-    for (int f = 3; f * f <= m; f += 2)
-      while (m % f == 0) {
-        if (g.nfac >= OFFT_MIX_MAXFAC) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d has too many factors", d->n); return -1; }
-        g.fac[g.nfac++] = f; m /= f;
-      }
-    if (m > 1) g.fac[g.nfac++] = m;
-    if (d->n == 1) { g.nfac = 0; }
-    if (g.nfac > OFFT_MIX_MAXFAC) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d has too many factors", d->n); return -1; }
+  return g;
+}
+
+// One launch of a kernel with dynamic LDS on a grid of nblk panels in XCD-aware order: the dynamic-LDS attribute is set
+// once per kernel (lds_attr: the largest footprint it will be launched with), a plan-time instance is a module function
+int launch(const char *who, const void *fn, void *modfn, bool *attr_set, size_t lds_attr, size_t lds, unsigned threads, long long nblk,
+           unsigned *xcd_lim, unsigned *xcd_gshift, void **args, hipStream_t st) {
+  if (nblk > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "%s: grid too large", who); return -1; }
+  xcd_order(nblk, xcd_lim, xcd_gshift);
+  if (modfn) {
+    HIPK_CHECK(hipModuleLaunchKernel((hipFunction_t)modfn, (unsigned)nblk, 1, 1, threads, 1, 1, (unsigned)lds, st, args, nullptr));
+    return 0;
   }
-  const size_t esz = d->precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
-  const size_t lds_cap = 160 * 1024;
-  if (2 * (size_t)d->n * esz > lds_cap) {
-    snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d too long for the any-length kernel", d->n);
-    return -1;
+  if (!*attr_set) {
+    if (lds_attr > 48 * 1024) HIPK_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr));
+    *attr_set = true;
   }
-  int cols = 8;
-  while (cols > 1 && (2 * (size_t)cols + 1) * d->n * esz > lds_cap) cols >>= 1;
-  g.tw_in_lds = (2 * (size_t)cols + 1) * d->n * esz <= lds_cap;
-  g.cols = cols;
-  g.ncp = (d->ncols + cols - 1) / cols;
-  size_t lds = (2 * (size_t)cols + (g.tw_in_lds ? 1 : 0)) * d->n * esz;
-  long long nblk = (long long)g.ncp * d->nb1 * d->nb2;
-  if (nblk > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: grid too large"); return -1; }
-  xcd_order(nblk, &g.xcd_lim, &g.xcd_gshift);
-  // the panel's LDS footprint allows one or two workgroups per CU: size the workgroup so that the CU still
-  // holds 8-16 waves to cover the LDS round trips between stages
-  static const int mix_nt_env = getenv("OFFT_MIX_THREADS") ? atoi(getenv("OFFT_MIX_THREADS")) : 0;
-  unsigned nt = lds > 80 * 1024 ? 1024 : lds > 40 * 1024 ? 512 : 256;
-  while (nt > 64 && (long long)nt * 2 > (long long)cols * d->n) nt >>= 1;  // at least two elements per thread
-  if (mix_nt_env >= 64 && mix_nt_env <= 1024) nt = (unsigned)mix_nt_env;
-  (void)hipGetLastError();  // start from a clean slate: the check below must see only this launch
-  if (d->precision == OFFT_PREC_F64) {
-    static bool set64 = false;
-    if (lds > 48 * 1024 && !set64) {
-      HIPK_CHECK(hipFuncSetAttribute((const void *)fft_mixed_k<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-      set64 = true;
-    }
-    hipLaunchKernelGGL(fft_mixed_k<double>, dim3((unsigned)nblk), dim3(nt), lds, st, g, (const double2 *)in,
-                       (double2 *)out, (const double2 *)tb.full);
-  } else {
-    static bool set32 = false;
-    if (lds > 48 * 1024 && !set32) {
-      HIPK_CHECK(hipFuncSetAttribute((const void *)fft_mixed_k<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-      set32 = true;
-    }
-    hipLaunchKernelGGL(fft_mixed_k<float>, dim3((unsigned)nblk), dim3(nt), lds, st, g, (const float2 *)in,
-                       (float2 *)out, (const float2 *)tb.full);
-  }
-  HIPK_CHECK(hipGetLastError());
+  HIPK_CHECK(hipLaunchKernel(fn, dim3((unsigned)nblk), dim3(threads), args, lds, st));
   return 0;
 }
 
-}  // extern "C"
+// the small kernels exist once per precision: run a statement with T = double / float and V2 = double2 / float2
+template <typename F>
+void by_precision(int prec, F &&f) { if (prec == OFFT_PREC_F64) f(double{}); else f(float{}); }
+#define FOR_PREC(prec, ...) \
+  by_precision(prec, [&](auto t_) { using T = decltype(t_); using V2 = typename vec2<T>::type; (void)sizeof(V2); __VA_ARGS__; })
 
-namespace {
-int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const FourStep &fs) {
+int launch_panel(const offt_pass_desc *d, const void *in, void *out, const Tables &tb, hipStream_t st, Variant *v) {
+  if (d->tw4 && !v->tw4) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no kernel with four-step twiddles for n=%d", d->n); return -1; }
+  PassArgs a = pass_args(d, v->cols);
+  // every panel kernel stages its twiddles from the exact full-wave table w^m, m < n (the quarter- and half-wave
+  // tables they keep in LDS are prefixes of it)
+  void *args[] = {(void *)&a, (void *)&in, (void *)&out, (void *)&tb.full};
+  return launch("offt_hipk_fft_pass", v->fn, v->modfn, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2,
+                &a.xcd_lim, &a.xcd_gshift, args, st);
+}
+
+int launch_blue_panel(const offt_pass_desc *d, const void *in, void *out, hipStream_t st, BlueVariant *bv, const BlueTab &bt) {
+  if (d->tw4) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no kernel with four-step twiddles for n=%d", d->n); return -1; }
+  PassArgs a = pass_args(d, bv->cols);
+  Tables tm;
+  if (get_tables(bt.m, d->precision, tm, false)) return -1;
+  int nlen = d->n;
+  void *args[] = {(void *)&a, (void *)&in, (void *)&out, (void *)&tm.full, (void *)&bt.chirp, (void *)&bt.bhat, (void *)&nlen};
+  return launch("offt_hipk_fft_pass", bv->fn, nullptr, &bv->attr_set, bv->lds, bv->lds, bv->threads, (long long)a.ncp * d->nb1 * d->nb2,
+                &a.xcd_lim, &a.xcd_gshift, args, st);
+}
+
+int launch_any_length(const offt_pass_desc *d, const void *in, void *out, const Tables &tb, hipStream_t st) {
+  GenArgs g = gen_args(d);
+  g.in_contig = d->in_contig; g.out_contig = d->out_contig;
+  // radices: prime factors, pairs of 2 merged into 4 (fewer LDS round trips at equal cost)
+  int m = d->n, twos = 0;
+  while (m % 2 == 0) { twos++; m /= 2; }
+  for (; twos >= 2; twos -= 2) g.fac[g.nfac++] = 4;
+  if (twos) g.fac[g.nfac++] = 2;
+  for (int f = 3; f * f <= m; f += 2)
+    while (m % f == 0) {
+      if (g.nfac >= OFFT_MIX_MAXFAC) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d has too many factors", d->n); return -1; }
+      g.fac[g.nfac++] = f; m /= f;
+    }
+  if (m > 1) g.fac[g.nfac++] = m;
+  if (d->n == 1) { g.nfac = 0; }
+  if (g.nfac > OFFT_MIX_MAXFAC) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d has too many factors", d->n); return -1; }
+  if (!fits_any_length(d->n, d->precision)) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d too long for the any-length kernel", d->n); return -1; }
+  const size_t line = d->n * elem_size(d->precision);
+  int cols = 8;
+  while (cols > 1 && (2 * (size_t)cols + 1) * line > LDS_BYTES) cols >>= 1;
+  g.tw_in_lds = (2 * (size_t)cols + 1) * line <= LDS_BYTES;
+  g.cols = cols;
+  g.ncp = (d->ncols + cols - 1) / cols;
+  const size_t lds = (2 * (size_t)cols + (g.tw_in_lds ? 1 : 0)) * line;
+  // the panel's LDS footprint allows one or two workgroups per CU: size the workgroup so that the CU still
+  // holds 8-16 waves to cover the LDS round trips between stages
+  unsigned nt = lds > 80 * 1024 ? 1024 : lds > 40 * 1024 ? 512 : 256;
+  while (nt > 64 && (long long)nt * 2 > (long long)cols * d->n) nt >>= 1;  // at least two elements per thread
+  if (env().mix_threads >= 64 && env().mix_threads <= 1024) nt = (unsigned)env().mix_threads;
+  static bool attr_set[2] = {false, false};
+  const bool f64 = d->precision == OFFT_PREC_F64;
+  void *args[] = {(void *)&g, (void *)&in, (void *)&out, (void *)&tb.full};
+  return launch("offt_hipk_fft_pass", f64 ? (const void *)fft_mixed_k<double> : (const void *)fft_mixed_k<float>, nullptr, &attr_set[f64 ? 0 : 1],
+                LDS_BYTES, lds, nt, (long long)g.ncp * d->nb1 * d->nb2, &g.xcd_lim, &g.xcd_gshift, args, st);
+}
+
+int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const FourStep &fs, const Tables &tb) {
   const int N = d->n, N1 = fs.n1, N2 = fs.n2;
-  const size_t esz = d->precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
-  if (d->real_input) { LongTab plain; return long_pass(d, in, out, stream, plain); }  // gathered as complex lines (see long_pass)
-  // a per-peer split must cut the axis where the decomposition can follow it: whole runs of n2 inputs / n1 outputs.  One that
-  // does not (uneven blocks) sends the lines through scratch: gathered with the split, transformed as contiguous lines
-  if ((d->in_split && (d->in_split_nfloor || d->in_split % N2)) || (d->out_split && (d->out_split_nfloor || d->out_split % N1))) {
-    LongTab plain;
-    return long_pass(d, in, out, stream, plain);
-  }
-  Tables tb;
-  if (get_tables(N, d->precision, tb, false)) return -1;
+  const size_t esz = elem_size(d->precision);
   const bool inL = d->in_contig != 0, outL = d->out_contig != 0;
-  // columns per chunk: whole rows of the caller's column dimension, as many b1 entries as fit 256 MiB of scratch
-  static const int chunk_mib = getenv("OFFT_FOURSTEP_CHUNK_MIB") && atoi(getenv("OFFT_FOURSTEP_CHUNK_MIB")) > 0 ? atoi(getenv("OFFT_FOURSTEP_CHUNK_MIB")) : 192;
-  const size_t cap = ((size_t)chunk_mib << 20) / esz;
+  // columns per chunk: whole rows of the caller's column dimension, as many b1 entries as fit the chunk's share of scratch
+  const size_t cap = ((size_t)env().fourstep_chunk_mib << 20) / esz;
   int cc = d->ncols, cb1 = d->nb1;
   if ((size_t)cc * N > cap) { cc = (int)(cap / N); if (cc < 1) cc = 1; cb1 = 1; }
   else { const size_t fit = cap / ((size_t)cc * N); if ((size_t)cb1 > fit) cb1 = (int)(fit < 1 ? 1 : fit); }
@@ -1465,8 +1328,7 @@ int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, 
         // twiddles fused into A's stores when the n1-point kernel has such a twin: two sweeps instead of three.  A strided-in
         // pass then leaves S'[k1][j2][c] as it is and C reads it with the caller's columns as its columns -- which needs a
         // strided-out pass as well; strided-in / contig-out keeps the transposing twiddle sweep.
-        static const bool fuse_on = !(getenv("OFFT_FOURSTEP_FUSE") && atoi(getenv("OFFT_FOURSTEP_FUSE")) == 0);
-        const bool fused = fuse_on && (inL || !outL) && (!d->in_split || is_pow2(d->in_split / N2)) &&
+        const bool fused = env().fourstep_fuse && (inL || !outL) && (!d->in_split || is_pow2(d->in_split / N2)) &&
                            find_variant(N1, d->precision, false, false, -1, false, false, true) != nullptr;
         if (fused) { a.tw4 = fs.t4; a.tw4_b1 = inL ? 0 : 1; a.tw4_n2 = N2; }
         if (inL) {  // the axis is the unit-stride dimension: j2 becomes the column dimension
@@ -1490,16 +1352,10 @@ int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, 
         } else if (inL) {
           const long long total = (long long)nc * nb * N;
           const unsigned blocks = (unsigned)((total + 255) / 256);
-          if (d->precision == OFFT_PREC_F64)
-            hipLaunchKernelGGL(four_twiddle_k<double2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (double2 *)S, (const double2 *)tb.full, total, N1, N2, conj);
-          else
-            hipLaunchKernelGGL(four_twiddle_k<float2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float2 *)S, (const float2 *)tb.full, total, N1, N2, conj);
+          FOR_PREC(d->precision, hipLaunchKernelGGL(four_twiddle_k<V2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (V2 *)S, (const V2 *)tb.full, total, N1, N2, conj));
         } else {
           const dim3 grid((unsigned)((nc + 31) / 32), (unsigned)((N + 31) / 32), (unsigned)nb);
-          if (d->precision == OFFT_PREC_F64)
-            hipLaunchKernelGGL(four_twiddle_t_k<double2>, grid, dim3(256), 0, (hipStream_t)stream, (const double2 *)Sp, (double2 *)S, (const double2 *)tb.full, N, nc, N2, conj);
-          else
-            hipLaunchKernelGGL(four_twiddle_t_k<float2>, grid, dim3(256), 0, (hipStream_t)stream, (const float2 *)Sp, (float2 *)S, (const float2 *)tb.full, N, nc, N2, conj);
+          FOR_PREC(d->precision, hipLaunchKernelGGL(four_twiddle_t_k<V2>, grid, dim3(256), 0, (hipStream_t)stream, (const V2 *)Sp, (V2 *)S, (const V2 *)tb.full, N, nc, N2, conj));
         }
         HIPK_CHECK(hipGetLastError());
         // ---- C: n2-point transforms over j2, output index k1 + n1 k2 ----
@@ -1531,21 +1387,9 @@ int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, 
 
 int long_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const LongTab &lt) {
   const int N = d->n, M = lt.m ? lt.m : N;   // (lt.m == 0: plain complex lines of N points, the long real-input case)
-  const size_t esz = d->precision == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2);
+  const size_t esz = elem_size(d->precision);
   const hipStream_t st = (hipStream_t)stream;
-  GenArgs g;
-  memset(&g, 0, sizeof g);
-  g.in_axis = d->in_axis_stride; g.in_col = d->in_col_stride; g.in_b1 = d->in_b1_stride; g.in_b2 = d->in_b2_stride;
-  g.out_axis = d->out_axis_stride; g.out_col = d->out_col_stride; g.out_b1 = d->out_b1_stride; g.out_b2 = d->out_b2_stride;
-  g.in_blk = d->in_block_stride; g.out_blk = d->out_block_stride;
-  g.in_split = d->in_split; g.in_nfloor = d->in_split_nfloor;
-  g.out_split = d->out_split; g.out_nfloor = d->out_split_nfloor;
-  g.n = N; g.ncols = d->ncols; g.nb1 = d->nb1;
-  g.conj = d->direction > 0;
-  g.real_in = d->real_input;
-  g.scale = d->scale;
-  g.in_tab = d->in_split ? d->in_block_tab : nullptr;
-  g.out_tab = d->out_split ? d->out_block_tab : nullptr;
+  const GenArgs g = gen_args(d);
   const int kend = d->real_input == 1 ? N / 2 + 1 : N;
   const long long nlines = (long long)d->ncols * d->nb1 * d->nb2;
   long long per = (long long)(((size_t)256 << 20) / ((size_t)M * esz));
@@ -1568,31 +1412,214 @@ int long_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, 
     const unsigned blocks = (unsigned)((tot + 255) / 256), blockse = (unsigned)((tote + 255) / 256);
     f.ncols = (int)nl;
     (void)hipGetLastError();
-    if (d->precision == OFFT_PREC_F64)
-      hipLaunchKernelGGL(long_gather_k<double>, dim3(blocks), dim3(256), 0, st, g, (const double2 *)in, (double2 *)U, (const double2 *)lt.chirp, M, l0, tot);
-    else
-      hipLaunchKernelGGL(long_gather_k<float>, dim3(blocks), dim3(256), 0, st, g, (const float2 *)in, (float2 *)U, (const float2 *)lt.chirp, M, l0, tot);
+    FOR_PREC(d->precision, hipLaunchKernelGGL(long_gather_k<T>, dim3(blocks), dim3(256), 0, st, g, (const V2 *)in, (V2 *)U, (const V2 *)lt.chirp, M, l0, tot));
     HIPK_CHECK(hipGetLastError());
     f.direction = -1;
     if (offt_hipk_fft_pass(&f, U, U, stream)) return -1;
     if (lt.m) {
-      if (d->precision == OFFT_PREC_F64)
-        hipLaunchKernelGGL(long_mul_k<double2>, dim3(blocks), dim3(256), 0, st, (double2 *)U, (const double2 *)lt.bhat, M, tot);
-      else
-        hipLaunchKernelGGL(long_mul_k<float2>, dim3(blocks), dim3(256), 0, st, (float2 *)U, (const float2 *)lt.bhat, M, tot);
+      FOR_PREC(d->precision, hipLaunchKernelGGL(long_mul_k<V2>, dim3(blocks), dim3(256), 0, st, (V2 *)U, (const V2 *)lt.bhat, M, tot));
       HIPK_CHECK(hipGetLastError());
       f.direction = +1;
       if (offt_hipk_fft_pass(&f, U, U, stream)) return -1;
     }
-    if (d->precision == OFFT_PREC_F64)
-      hipLaunchKernelGGL(long_scatter_k<double>, dim3(blockse), dim3(256), 0, st, g, (const double2 *)U, (double2 *)out, (const double2 *)lt.chirp, M, kend, l0, tote);
-    else
-      hipLaunchKernelGGL(long_scatter_k<float>, dim3(blockse), dim3(256), 0, st, g, (const float2 *)U, (float2 *)out, (const float2 *)lt.chirp, M, kend, l0, tote);
+    FOR_PREC(d->precision, hipLaunchKernelGGL(long_scatter_k<T>, dim3(blockse), dim3(256), 0, st, g, (const V2 *)U, (V2 *)out, (const V2 *)lt.chirp, M, kend, l0, tote));
     HIPK_CHECK(hipGetLastError());
   }
   return 0;
 }
+
+// ---- plan time: the steps of offt_hipk_prepare ----
+int blue_build_for(int n, int prec, BlueTab &bt, int m_override = 0) {
+  return prec == OFFT_PREC_F64 ? blue_build<double>(n, prec, bt, m_override) : blue_build<float>(n, prec, bt, m_override);
+}
+
+// chirp and B^ of a length that runs on the Bluestein panel kernel
+int blue_panel_build(int n, int prec) {
+  std::lock_guard<std::mutex> lk(g_blue_mu);
+  if (g_blue.count(std::make_pair(n, prec))) return 0;
+  BlueTab bt;
+  if (blue_build_for(n, prec, bt)) return -1;
+  g_blue[std::make_pair(n, prec)] = bt;
+  return 0;
+}
+
+// The first factor n1 of the four-step split n = n1 n2, or 0: a function of the registry and the switches only
+// (candidates are looked up, not prepared).  fused_only: the length has the any-length kernel to fall back on and takes
+// nothing but a FUSED split (score < 0)
+int choose_four_split(int n, int precision, bool fused_only) {
+  int best1 = 0;
+  double best_score = 1e30;
+  for (int n1 = 2; (long long)n1 * n1 <= n; ++n1) {
+    if (n % n1) continue;
+    const int n2 = n / n1;
+    // both factors need a kernel of their own: prefer precompiled register kernels and a balanced split (candidates are
+    // only looked up here, not prepared -- preparing may compile a plan-time kernel, seconds each)
+    const bool f1 = has_panel(n1, precision), f2 = has_panel(n2, precision);
+    if ((!f1 && !fits_any_length(n1, precision)) || (!f2 && !fits_any_length(n2, precision))) continue;
+    double score = std::log((double)n2 / (double)n1);
+    if (!f1) score += 4.0;
+    if (!f2) score += 4.0;
+    // ... except that a SHORT first sub-pass with the twiddles on its stores wins when the other factor still has a register
+    // kernel: few points per line, one thread per line on 64 unit-stride columns (8 columns at 64 points).  Order of
+    // preference, from sweeps over 8192 / 16384 / 32768 / 6000 / 10000 / 12000 points (profiles/r03_four_step.txt):
+    //   double  64 (8192 = 64 x 128: 37.3 % of the roofline, 36.4 % for 32 x 256), then 16, 8, 4 (6000 = 16 x 375: 31.5 %, 10000 =
+    //           16 x 625: 31.6 %, both 17-18 % as balanced unfused splits; 12000 = 16 x 750: 26.7 %, 20.1 % for 32 x 375), 32, 2
+    //   single  32 (8192 = 32 x 256: 37.5 %, 31.9 % for 64 x 128), then 16, 8, 4, 2
+    static const int pref64[] = {64, 16, 8, 4, 32, 2, 0}, pref32[] = {32, 16, 8, 4, 2, 0};
+    const int *pref = precision == OFFT_PREC_F64 ? pref64 : pref32;
+    // (second choice, behind every split whose long factor is precompiled: a long factor that gets its kernel compiled NOW --
+    //  seconds of plan time for 10000 = 16 x 625 at 32 % instead of 100 x 100 at 18 %)
+    const bool rtc2 = !f2 && rtc_candidate(n2);
+    // (third: a long factor with a prime factor > 13 that runs on the Bluestein panel kernel -- 4076 = 4 x 1019)
+    const bool blue2 = !f2 && !rtc2 && blue_panel_candidate(n2, precision, true, false) && blue_panel_candidate(n2, precision, false, false);
+    for (int r = 0; pref[r]; ++r)
+      if (n1 == pref[r] && (f2 || rtc2 || blue2) && find_variant(n1, precision, false, false, -1, false, false, true))
+        score = (f2 ? -10.0 : rtc2 ? -5.0 : -3.0) + 0.1 * r;
+    // a factor that would itself go through scratch lines (or the any-length kernel with a radix of hundreds) is a last resort
+    if (!f1 && max_prime_factor(n1) > 61 && !(n1 <= 2048 && env().bluestein)) score += 8.0;
+    if (!f2 && !rtc2 && !blue2 && max_prime_factor(n2) > 61 && !(n2 <= 2048 && env().bluestein)) score += 8.0;
+    if (env().fourstep_n1 == n1) score = -100.0;  // (OFFT_FOURSTEP_N1, for sweeps: only among the splits that are possible at all)
+    if (score < best_score) { best_score = score; best1 = n1; }
+  }
+  if (fused_only && best_score >= 0.0) best1 = 0;  // (unfused, three sweeps: the any-length kernel is no worse)
+  return best1;
+}
+
+// prepare both factors and build t4[k1][j2] = w_n^(k1 j2); a split whose factors turn out to have no kernel is dropped (0)
+int four_build(int n, int precision, int n1, const Tables &tb) {
+  if (offt_hipk_prepare(n1, precision) || offt_hipk_prepare(n / n1, precision) || !direct_ok(n1, precision) || !direct_ok(n / n1, precision))
+    return 0;
+  FourStep fs; fs.n1 = n1; fs.n2 = n / n1;
+  fs.all = !has_panel(n, precision);
+  HIPK_CHECK(hipMalloc(&fs.t4, (size_t)n * elem_size(precision)));
+  (void)hipGetLastError();
+  FOR_PREC(precision, hipLaunchKernelGGL(four_table_k<V2>, dim3((n + 255) / 256), dim3(256), 0, nullptr, (V2 *)fs.t4, (const V2 *)tb.full, n, fs.n2));
+  HIPK_CHECK(hipGetLastError());
+  HIPK_CHECK(hipStreamSynchronize(nullptr));
+  std::lock_guard<std::mutex> lk(g_four_mu);
+  g_four[std::make_pair(n, precision)] = fs;
+  return 0;
+}
+
+// chirp and B^ of a length that runs as a Bluestein convolution on lines of M >= 2n - 1 points through scratch (best effort)
+void long_build(int n, int precision) {
+  BlueTab bt;
+  const int mlong = env().bluestein_long_pow2 ? 0 : blue_m_long(n, precision);
+  if (blue_build_for(n, precision, bt, mlong)) return;
+  std::lock_guard<std::mutex> lk(g_long_mu);
+  LongTab lt; lt.chirp = bt.chirp; lt.bhat = bt.bhat; lt.m = bt.m;
+  g_long[std::make_pair(n, precision)] = lt;
+}
+
 }  // namespace
+
+extern "C" {
+
+const char *offt_hipk_last_error(void) { return g_err; }
+
+int offt_hipk_has_fast_path(int n, int precision) { return has_panel(n, precision); }
+
+int offt_hipk_variant_count(int n, int precision) {
+  std::call_once(g_reg_once, build_registry);
+  int c = 0;
+  for (auto &v : registry())
+    if (v.n == n && v.prec == precision && v.inc && v.outc && !v.r2c && !v.c2r && !v.conv && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
+  return c;
+}
+
+const char *offt_hipk_variant_name(int n, int precision, int variant) {
+  Variant *v = find_variant(n, precision, true, true, variant);
+  return v ? v->name.c_str() : "mixed-radix any-length";
+}
+
+int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thread, int *cols) {
+  Variant *v = find_variant(n, precision, true, true, variant);
+  if (!v || (variant >= 0 && v->id != variant)) return -1;
+  if (elems_per_thread) *elems_per_thread = v->e;
+  if (cols) *cols = v->cols;
+  return v->id;
+}
+
+// the direct layer of resolve(): a pass that is decomposed (four-step, scratch lines) is named by what would launch it alone
+const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
+  Route r;
+  resolve_direct(d, nullptr, nullptr, &r);
+  if (r.via == Via::BluePanel) return "fft_bluestein_k";
+  if (r.via == Via::AnyLength) return "fft_mixed_k";
+  if (r.v->c2r) return r.v->mixed ? "fft_c2r_panelx_k" : "fft_c2r_panel_k";
+  return r.v->mixed ? "fft_panelx_k" : (r.v->prec == OFFT_PREC_F32_PAIR ? "fft_panel_k<pairs>" : "fft_panel_k");
+}
+
+int offt_hipk_prepare(int n, int precision) {
+  const bool c2r = (precision & OFFT_HIPK_PREP_C2R) != 0;
+  precision &= ~OFFT_HIPK_PREP_C2R;
+  if (n < 1) { snprintf(g_err, sizeof g_err, "offt_hipk_prepare: bad n=%d", n); return -1; }
+  if (c2r) {
+    if (offt_hipk_prepare(n, precision)) return -1;
+    // real-output instances for a length whose panel kernel was compiled at plan time (the precompiled lengths have theirs);
+    // best effort like the complex ones: without them the real-output pass runs on the any-length kernel
+    const Variant *v = find_variant(n, precision, true, true, -1);
+    if (v && v->modfn && env().rtc) (void)rtc_build(n, precision, true);
+    return 0;
+  }
+  // 1. twiddle tables
+  Tables tb;
+  if (get_tables(n, precision, tb, true)) return -1;
+  // 2. a plan-time panel kernel for a candidate length without a precompiled one (best effort)
+  if (rtc_candidate(n) && !has_panel(n, precision)) (void)rtc_build(n, precision);
+  // 3. a length without any register kernel (a prime factor > 31, or outside 256 .. 4096 and not precompiled): the
+  //    Bluestein panel kernel's tables
+  if (!has_panel(n, precision) && blue_panel_candidate(n, precision, true, true) && blue_panel_build(n, precision)) return -1;
+  // 4. a length no single launch takes (no panel kernel, and two images of a line do not fit the LDS of the any-length
+  //    kernel) is split n = n1 n2 for the four-step path; 8192 has a register kernel, but with one column per
+  //    workgroup: its strided flavours go the four-step way as well ...
+  const bool no_direct = !has_panel(n, precision) && !fits_any_length(n, precision);
+  // ... and so does a length that would otherwise run on the any-length kernel -- above the plan-time kernels' range (4800,
+  // 5000; in single precision up to 10240 points: 10000 at 15 % of the roofline there) or above the Bluestein panel kernel's with
+  // a large prime factor (4076 = 4 x 1019) -- if it has a FUSED split
+  BlueTab bt_any;
+  const bool any_only = !no_direct && n > 2048 && !has_panel(n, precision) && !blue_lookup(n, precision, &bt_any);
+  if ((no_direct || n == 8192 || any_only) && env().fourstep && !four_lookup(n, precision, nullptr)) {
+    const int n1 = choose_four_split(n, precision, any_only);
+    if (n1 && four_build(n, precision, n1, tb)) return -1;
+  }
+  // 5. ... and a length without a split becomes a Bluestein convolution on lines of M >= 2n - 1 points through scratch
+  //    (also a length the any-length kernel COULD take, but only with a radix of hundreds -- r multiply-adds per output: 3057 =
+  //     3 x 1019 points ran at 0.6 % of the roofline there)
+  if ((no_direct || (any_only && max_prime_factor(n) > 61)) && !four_lookup(n, precision, nullptr) && env().bluestein_long &&
+      env().fourstep /* (its M-point lines need the four-step path) */ && env().bluestein && n < (1 << 24) && !long_lookup(n, precision, nullptr))
+    long_build(n, precision);
+  // 6. only a length without any of these -- a prime, or a prime factor too large itself, with the nets switched off -- is
+  //    refused, HERE, at plan time: offt_3d_init returns NULL instead of every execute failing
+  if (no_direct && !four_lookup(n, precision, nullptr) && !long_lookup(n, precision, nullptr)) {
+    snprintf(g_err, sizeof g_err, "no kernel for lines of %d %s points: no register kernel, the any-length kernel holds at most %zu, and %d has no "
+             "factorisation n1 n2 into lengths that have one", n, precision == OFFT_PREC_F64 ? "double-complex" : "single-complex",
+             LDS_BYTES / (2 * elem_size(precision)), n);
+    return -1;
+  }
+  return 0;
+}
+
+int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void *stream) {
+  if (d->n < 1 || d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;  // empty batch: nothing to do
+  if (d->n == 1 && d->scale == 1.0 && in == out && d->in_axis_stride == d->out_axis_stride &&
+      d->in_col_stride == d->out_col_stride && d->in_b1_stride == d->out_b1_stride &&
+      d->in_b2_stride == d->out_b2_stride)
+    return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  const Route r = resolve(d, in, out);
+  switch (r.via) {
+    case Via::FourStep: return four_pass(d, in, out, stream, r.fs, tb);
+    case Via::ScratchLines: return long_pass(d, in, out, stream, r.lt);
+    case Via::Panel: return launch_panel(d, in, out, tb, (hipStream_t)stream, r.v);
+    case Via::BluePanel: return launch_blue_panel(d, in, out, (hipStream_t)stream, r.bv, r.bt);
+    case Via::AnyLength: return launch_any_length(d, in, out, tb, (hipStream_t)stream);
+  }
+  return -1;
+}
+
+}  // extern "C"
 
 extern "C" {
 
@@ -1639,9 +1666,6 @@ int flag_launch(bool wait, int n, unsigned long long *const *addr, unsigned long
   HIPK_CHECK(hipGetLastError());
   return 0;
 }
-}  // namespace
-
-namespace {
 __global__ void __launch_bounds__(64) delay_k(long long ticks) {
   const long long t0 = wall_clock64();
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
@@ -1692,27 +1716,13 @@ int offt_hipk_conv_pass(const offt_pass_desc *d, const offt_filter_desc *f, cons
   if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
   Tables tb;
   if (get_tables(d->n, d->precision, tb, false)) return -1;
-  PassArgs a;
-  memset(&a, 0, sizeof a);
-  a.in_axis = d->in_axis_stride; a.in_col = d->in_col_stride; a.in_b1 = d->in_b1_stride; a.in_b2 = d->in_b2_stride;
-  a.in_shift = a.out_shift = 31;
-  a.ncols = d->ncols;
-  a.ncp = (d->ncols + v->cols - 1) / v->cols;
-  a.nb1 = d->nb1;
-  a.scale = d->scale;
+  PassArgs a = pass_args(d, v->cols, true);
   ConvArgs fa;
   fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
   fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
-  const long long nblk = (long long)a.ncp * d->nb1 * d->nb2;
-  if (nblk > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass: grid too large"); return -1; }
-  xcd_order(nblk, &a.xcd_lim, &a.xcd_gshift);
   void *args[] = {(void *)&a, (void *)&fa, (void *)&data, (void *)&filter, (void *)&tb.full};
-  if (!v->attr_set) {
-    if (v->lds > 48 * 1024) HIPK_CHECK(hipFuncSetAttribute(v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v->lds));
-    v->attr_set = true;
-  }
-  HIPK_CHECK(hipLaunchKernel(v->fn, dim3((unsigned)nblk), dim3(v->threads), args, v->lds, (hipStream_t)stream));
-  return 0;
+  return launch("offt_hipk_conv_pass", v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2,
+                &a.xcd_lim, &a.xcd_gshift, args, (hipStream_t)stream);
 }
 
 int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0, long long s1,
@@ -1736,16 +1746,12 @@ int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind,
   hipStream_t sm = (hipStream_t)stream;
   (void)hipGetLastError();
   const bool cx = kind == OFFT_FILTER_COMPLEX;
-  if (!f32) {
-    if (cx) hipLaunchKernelGGL((pointwise_k<double, true, 1>), dim3(gx, gy), dim3(256), 0, sm, (double2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
-    else hipLaunchKernelGGL((pointwise_k<double, false, 1>), dim3(gx, gy), dim3(256), 0, sm, (double2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
-  } else if (pair) {
-    if (cx) hipLaunchKernelGGL((pointwise_k<float, true, 2>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
-    else hipLaunchKernelGGL((pointwise_k<float, false, 2>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
-  } else {
-    if (cx) hipLaunchKernelGGL((pointwise_k<float, true, 1>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
-    else hipLaunchKernelGGL((pointwise_k<float, false, 1>), dim3(gx, gy), dim3(256), 0, sm, (float2 *)data, filter, n[1], n[2], st[0], st[1], st[2], rows);
-  }
+#define POINTWISE(T, CPLX, EPL) \
+  hipLaunchKernelGGL((pointwise_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, (typename vec2<T>::type *)data, filter, n[1], n[2], st[0], st[1], st[2], rows)
+  if (pair) { if (cx) POINTWISE(float, true, 2); else POINTWISE(float, false, 2); }
+  else if (cx) FOR_PREC(precision, POINTWISE(T, true, 1));
+  else FOR_PREC(precision, POINTWISE(T, false, 1));
+#undef POINTWISE
   HIPK_CHECK(hipGetLastError());
   return 0;
 }
@@ -1756,12 +1762,8 @@ int offt_hipk_copy3d(const void *in, void *out, int precision, int n0, int n1, i
   if (total <= 0) return 0;
   long long nb = (total + 255) / 256;
   if (nb > 256 * 64) nb = 256 * 64;
-  if (precision == OFFT_PREC_F64)
-    hipLaunchKernelGGL(copy3d_k<double2>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const double2 *)in,
-                       (double2 *)out, n0, n1, n2, is0, is1, is2, os0, os1, os2);
-  else
-    hipLaunchKernelGGL(copy3d_k<float2>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const float2 *)in,
-                       (float2 *)out, n0, n1, n2, is0, is1, is2, os0, os1, os2);
+  FOR_PREC(precision, hipLaunchKernelGGL(copy3d_k<V2>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const V2 *)in, (V2 *)out, n0, n1, n2,
+                                         is0, is1, is2, os0, os1, os2));
   HIPK_CHECK(hipGetLastError());
   return 0;
 }
@@ -1772,22 +1774,12 @@ int offt_hipk_fill(void *buf, int precision, int kind, int n0, int n1, int n2, i
   if (total <= 0) return 0;
   long long nb = (total + 255) / 256;
   if (nb > 256 * 64) nb = 256 * 64;
-  if (precision & 0x100) {  // real-valued field (r2c input), strides in scalars
-    if ((precision & 0xff) == OFFT_PREC_F64)
-      hipLaunchKernelGGL(fill_real_k<double>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (double *)buf, kind,
-                         n0, n1, n2, s0, s1, s2, st0, st1, st2);
-    else
-      hipLaunchKernelGGL(fill_real_k<float>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (float *)buf, kind,
-                         n0, n1, n2, s0, s1, s2, st0, st1, st2);
-    HIPK_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (precision == OFFT_PREC_F64)
-    hipLaunchKernelGGL(fill_k<double2>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (double2 *)buf, kind,
-                       n0, n1, n2, s0, s1, s2, st0, st1, st2);
+  if (precision & 0x100)  // real-valued field (r2c input), strides in scalars
+    FOR_PREC(precision & 0xff, hipLaunchKernelGGL(fill_real_k<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (T *)buf, kind, n0, n1, n2,
+                                                  s0, s1, s2, st0, st1, st2));
   else
-    hipLaunchKernelGGL(fill_k<float2>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (float2 *)buf, kind, n0,
-                       n1, n2, s0, s1, s2, st0, st1, st2);
+    FOR_PREC(precision, hipLaunchKernelGGL(fill_k<V2>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (V2 *)buf, kind, n0, n1, n2,
+                                           s0, s1, s2, st0, st1, st2));
   HIPK_CHECK(hipGetLastError());
   return 0;
 }
