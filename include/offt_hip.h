@@ -76,6 +76,16 @@ void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int directi
 int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *filter, int filter_kind);
 /* 1 if this plan's convolve runs the fused route (one launch for forward-pass . filter . inverse-pass), 0 otherwise */
 int offt_hip_convolve_fused(const struct _offt_plan *po);
+/* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
+ * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
+ *   full spectrum of the zero-padded field, in the usual output layout.
+ * Inverse: only the box of the result is defined afterwards; the rest of the block is undefined.
+ * Convolve: box in, box out -- the aperiodic convolution when the kernel's support fits.
+ * -1 (plan unchanged, text in offt_hip_last_error) if an extent is odd.  Collective on several ranks. */
+int offt_hip_set_half_box(struct _offt_plan *po, int on);
+/* 1: every pass of this plan skips the padding (half-line kernels); 0: the library clears the padding and runs the
+ * ordinary schedule.  The results are the same. */
+int offt_hip_half_box_pruned(const struct _offt_plan *po);
 /* run on a caller-owned hipStream_t (NULL = the plan's own stream)             */
 void offt_hip_set_stream(struct _offt_plan *po, void *stream);
 /* 0: offt_3d_execute returns after the GPU finished (timers valid, reference

@@ -96,6 +96,10 @@ def bind(L):
     L.offt_hip_execute_convolve.argtypes = [PP, C.c_void_p, C.c_void_p, i]
     L.offt_hip_convolve_fused.restype = i
     L.offt_hip_convolve_fused.argtypes = [PP]
+    L.offt_hip_set_half_box.restype = i
+    L.offt_hip_set_half_box.argtypes = [PP, i]
+    L.offt_hip_half_box_pruned.restype = i
+    L.offt_hip_half_box_pruned.argtypes = [PP]
     L.print_params.restype = None
     L.print_params.argtypes = [C.POINTER(C.c_int)]
     L.offt_print_time.restype = None
@@ -194,6 +198,19 @@ def offt_hip_execute_convolve(po, data, filt, filter_kind=FILTER_REAL):
 def offt_hip_convolve_fused(po):
     """True if the plan's convolve runs the fused route (one launch for forward pass . filter . inverse pass)"""
     return lib().offt_hip_convolve_fused(po) == 1
+
+
+def offt_hip_set_half_box(po, on=True):
+    """the data lives in the low half of every axis of the input block and the rest counts as zero (include/offt_hip.h):
+    forward = spectrum of the zero-padded field, inverse = the box only, convolve = box in, box out"""
+    L = lib()
+    if L.offt_hip_set_half_box(po, 1 if on else 0) != 0:
+        raise ValueError("offt_hip_set_half_box failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_half_box_pruned(po):
+    """True if every pass of the half-box plan skips the padding; False: the library clears it and runs the ordinary schedule"""
+    return lib().offt_hip_half_box_pruned(po) == 1
 
 
 def offt_3d_fin(po):

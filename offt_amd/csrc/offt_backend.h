@@ -57,6 +57,11 @@ typedef struct offt_backend {
   int (*conv_pass)(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, void *data, void *stream);
   int (*pointwise)(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0, long long s1,
                    long long s2, void *stream);
+  /* ---- half box (offt_hip_set_half_box) ----
+   * zero_outside: offt_hipk_zero_outside -- clear a strided block outside a kept sub-box (the fallback route: every plan
+   * whose passes cannot skip the padding themselves); NULL: half-box is refused on this backend. */
+  int (*zero_outside)(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1, long long s2,
+                      void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);

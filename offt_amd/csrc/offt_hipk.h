@@ -67,6 +67,11 @@ typedef struct offt_pass_desc {
   int out_keep;
   /* single precision: 1 = do not use the column-pair kernels for this pass (plan option OFFT_HIP_OPT_F32_PAIRS) */
   int no_pairs;
+  /* zero-padded half lines (n even).  Bit 1: axis indices >= n/2 of the INPUT line are zero and are not read.  Bit 2: only
+   * output indices < n/2 are stored, the others are not written.  Kernels: power-of-two lines of 64 ... 1024 points,
+   * complex, no split, in the four flavours of offt_hipk_has_half; a pass that asks for a bit no kernel implements
+   * fails, it never runs the full line.  (The field sits in what used to be alignment padding: no other offset moves.) */
+  int half;
   /* first sub-pass of a four-step line (set by the launcher itself, offt_kernels.hip): multiply output index k1 of column
    * j2 (tw4_b1 = 0) or of batch entry b1 = j2 (tw4_b1 = 1) by tw4[k1 * tw4_n2 + j2] = w_n^(k1 j2), a table of the long
    * length n = n1 n2 laid out [k1][j2] (the lanes of a wave are neighbouring columns j2: one 128-B line per 8 lanes, where
@@ -76,6 +81,12 @@ typedef struct offt_pass_desc {
   int tw4_b1;
   int tw4_n2;
 } offt_pass_desc;
+/* `half` took the four bytes of padding in front of tw4: the size and every older offset are what they were */
+#ifdef __cplusplus
+static_assert(sizeof(offt_pass_desc) == 192 && __builtin_offsetof(offt_pass_desc, tw4) == 176, "offt_pass_desc layout");
+#else
+_Static_assert(sizeof(offt_pass_desc) == 192 && __builtin_offsetof(offt_pass_desc, tw4) == 176, "offt_pass_desc layout");
+#endif
 
 /* Build device twiddle tables etc. for length n; call at plan time (allocates).  precision | OFFT_HIPK_PREP_C2R: also
  * the real-output (real_input = 2) kernels of a length whose panel kernel is compiled at plan time (the z length of a
@@ -100,6 +111,10 @@ int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thr
  * launcher's resolve().  A pass that is decomposed (four-step, lines through scratch) launches several kernels and is
  * named by the kernel that would take its descriptor alone.                      */
 const char *offt_hipk_kernel_name(const offt_pass_desc *d);
+/* 1 if a half-line kernel exists for the descriptor (d->half = 1 or 2): power-of-two lines of 64 ... 1024 points, complex,
+ * no split, no four-step twiddles, and one of the flavours contiguous-in / strided-out with bit 1, contiguous / contiguous
+ * with bit 1 or bit 2, strided-in / contiguous-out with bit 2.  A registry lookup: needs no device. */
+int offt_hipk_has_half(const offt_pass_desc *d);
 /* ---- spectral convolution (offt_hip_execute_convolve) ------------------------------------------------------------------
  * A filter H laid out like a forward pass's OUTPUT: kind 0 = one real scalar of the pass's precision per complex slot
  * (scalar index = element index), 1 = one complex value per element.  Strides in complex elements. */
@@ -112,16 +127,24 @@ typedef struct offt_filter_desc {
 /* One fused launch on the lines of `fwd` (the last pass of a forward transform): load through its in_* side, forward FFT,
  * times H read where the pass would store (f), inverse FFT (unnormalised), times fwd->scale, store through the same in_*
  * addressing -- in place on `data`.  fwd->out_keep: stores with the default cache policy.  -1 if no fused kernel exists. */
+/* fwd->half: 0, or 3 = zero-padded half lines: only indices < n/2 of every line are loaded and only those are stored
+ * (the filter is read over the full line); any other non-zero value has no fused kernel. */
 int offt_hipk_conv_pass(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, void *data, void *stream);
 /* 1 if offt_hipk_conv_pass has a fused kernel for (fwd, f): power-of-two lines of 64 ... 1024 points, contiguous lines
  * (in_contig, no split, complex input) and a unit-stride filter axis; the registry lookup needs no device */
 int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f);
-/* "fft_conv_panel_k", or "no fused kernel" (rocprof matching, tests) */
+/* "fft_conv_panel_k", "fft_conv_half_panel_k" (fwd->half = 3), or "no fused kernel" (rocprof matching, tests) */
 const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f);
 /* data[i0 s0 + i1 s1 + i2 s2] *= H at the same element index, over the box n0 x n1 x n2 (complex elements, in place);
  * kind as offt_filter_desc::kind.  Non-temporal, 16 B per lane along the smallest stride. */
 int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2,
                         long long s0, long long s1, long long s2, void *stream);
+/* zero a strided 3-D block n0 x n1 x n2 OUTSIDE the kept sub-box [0,k0) x [0,k1) x [0,k2) (0 <= k <= n); the kept part is
+ * not touched.  Elements are complex values of `precision`, or, with OFFT_HIPK_ZERO_REAL or-ed into it, real scalars (the
+ * rows of an r2c plan; strides and extents then count scalars).  Vector stores, 16 B per lane along a unit stride s2. */
+#define OFFT_HIPK_ZERO_REAL 0x100
+int offt_hipk_zero_outside(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1,
+                           long long s2, void *stream);
 /* strided complex copy / permutation (used for layouts no FFT pass can fold)   */
 int offt_hipk_copy3d(const void *in, void *out, int precision,
                      int n0, int n1, int n2,

@@ -402,6 +402,9 @@ typedef struct hip_state {
   void **ev_t2;          /* per x-tile (mirrored pencil schedule): the tile's mirrored exchange 2 has landed */
   int uses_rccl;         /* this plan exchanges over RCCL communicators (watched while waiting) */
   int skip_mask;         /* diagnostics (offt_hip_set_debug_skip): 1 = no FFT passes, 2 = no exchanges */
+  int half_box;          /* offt_hip_set_half_box: the data lives in the low half-octant of the input block, the rest counts as zero */
+  int half_pruned;       /* ... and every pass of the single-rank z-y-x schedule skips the padding (offt_pass_desc::half);
+                            0 with half_box set: the padding is cleared (zero_outside) ahead of the ordinary schedule */
   void **send1, **recv1; /* ring */
   void **ev_k1, **ev_a1, **ev_k2;
   void *send2, *recv2;
@@ -657,10 +660,16 @@ static int hb_pointwise(void *data, const void *filter, int precision, int kind,
   if (rc) SET_ERR("pointwise multiply failed: %s", offt_hipk_last_error());
   return rc;
 }
+static int hb_zero_outside(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1, long long s2,
+                           void *stream) {
+  const int rc = offt_hipk_zero_outside(buf, precision, n0, n1, n2, k0, k1, k2, s0, s1, s2, stream);
+  if (rc) SET_ERR("clearing the padding failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
-    hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise};
+    hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside};
 
 /* ------------------------------------------------------------------------- */
 /* helpers                                                                    */
@@ -1667,8 +1676,8 @@ typedef struct single_sched {
 } single_sched;
 
 /* a pass descriptor turned into its mirror image: input and output sides exchanged, the sign of the exponent flipped, the
- * real-input pass become the real-output one.  `scale` and `out_keep` stay as they are: the callers set them, each by its
- * own rule. */
+ * real-input pass become the real-output one, a half line that is not loaded become one that is not stored.  `scale` and
+ * `out_keep` stay as they are: the callers set them, each by its own rule. */
 static void desc_mirror(offt_pass_desc *d) {
   const offt_pass_desc f = *d;
   d->direction = +1;
@@ -1679,6 +1688,7 @@ static void desc_mirror(offt_pass_desc *d) {
   d->in_block_tab = f.out_block_tab; d->out_block_tab = f.in_block_tab;
   d->in_contig = f.out_contig; d->out_contig = f.in_contig;
   if (f.real_input == 1) d->real_input = 2; /* real input -> real output: the complex-to-real inverse's z pass */
+  d->half = ((f.half & 1) << 1) | ((f.half >> 1) & 1);
 }
 
 static void single_schedule(struct _offt_plan *po, void *data, int dir, single_sched *ss) {
@@ -1778,6 +1788,18 @@ static void single_schedule(struct _offt_plan *po, void *data, int dir, single_s
     src[0] = data; dst[0] = W; src[1] = W; dst[1] = data; src[2] = data; dst[2] = data;
     slot[0] = 0; slot[1] = 1; slot[2] = 2;
     ss->pair = 1; ss->planes = Nz; ss->plane_elems = (double)Nx * Ny; /* y writes z-planes of out, x transforms them */
+    if (st->half_pruned) {
+      /* half box (offt_hip_set_half_box): the data sits in x < Nx/2, y < Ny/2, z < Nz/2 and the rest counts as zero.  No pass
+       * loads the padding along its axis (half = 1), and no pass transforms a line that is zero end to end:
+       *   P1  lines x < Nx/2, y < Ny/2    loads z < Nz/2, stores every z
+       *   P2  columns x < Nx/2            loads y < Ny/2, stores every y
+       *   P3  every line                  loads x < Nx/2, stores every x
+       * 1/8 + 1/4 + 1/4 + 1/2 + 1/2 + 1 = 2.625 sweeps over the volume instead of 6.  What P2 does not store (x >= Nx/2 of
+       * the caller's array) P3 does not load.  Mirrored, the inverse stores the box only (half = 2). */
+      d[0].ncols = Ny / 2; d[0].nb1 = Nx / 2;
+      d[1].ncols = Nx / 2;
+      d[0].half = d[1].half = d[2].half = 1;
+    }
   } else if (st->work2) {
     /* y-z-x output (is_equalxy) as a variation of the z-y-x schedule: the same two rotations, the second one into a second
      * scratch volume V[z][y][x], and the x pass -- whole contiguous lines on both sides -- puts every line where the
@@ -2744,6 +2766,66 @@ static int wait_compute(hip_state *st) {
   return rc;
 }
 
+/* ------------------------------------------------------------------------- */
+/* half box (offt_hip_set_half_box)                                           */
+/* ------------------------------------------------------------------------- */
+/* 1 if every launch of this plan's forward and inverse can skip the padding: one rank, complex, the z-y-x layout, a
+ * half-line kernel for each of the six descriptors (a registry lookup that needs no device: a test backend gets the
+ * same answer as the HIP one, and has to interpret offt_pass_desc::half) */
+static int half_can_prune(struct _offt_plan *po) {
+  hip_state *st = (hip_state *)po->hip_state;
+  if (st->use_pipeline || po->is_r2c) return 0;
+  single_sched fw, iv;
+  const int was = st->half_pruned;
+  st->half_pruned = 1;
+  single_schedule(po, NULL, -1, &fw);
+  single_schedule(po, NULL, +1, &iv);
+  st->half_pruned = was;
+  if (!fw.zyx) return 0;
+  for (int i = 0; i < 3; i++)
+    if (!(offt_hipk_has_half(&fw.d[i]) && offt_hipk_has_half(&iv.d[i]))) return 0;
+  return 1;
+}
+
+int offt_hip_set_half_box(struct _offt_plan *po, int on) {
+  hip_state *st = (hip_state *)po->hip_state;
+  if (on && ((po->Nx | po->Ny | po->Nz) & 1)) {
+    SET_ERR("offt_hip_set_half_box: the half box needs even extents (%d x %d x %d)", po->Nx, po->Ny, po->Nz);
+    return -1;
+  }
+  if (on && !st->be->zero_outside) {
+    SET_ERR("offt_hip_set_half_box: this backend cannot clear the padding");
+    return -1;
+  }
+  inv_cache_drop(st);
+  st->half_box = on != 0;
+  st->half_pruned = st->half_box ? half_can_prune(po) : 0;
+  return 0;
+}
+
+int offt_hip_half_box_pruned(const struct _offt_plan *po) {
+  return po && po->hip_state ? ((const hip_state *)po->hip_state)->half_pruned : 0;
+}
+
+/* the fallback route of a half-box plan, ahead of a forward transform or a convolve: clear the part of this rank's input
+ * block that lies outside the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices), on the compute stream */
+static int half_box_clear(struct _offt_plan *po, void *data) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const struct _offt_comm *c = po->comm;
+  if (!st->half_box || st->half_pruned) return 0;
+  const int N[3] = {po->Nx, po->Ny, po->Nz};
+  int k[3];
+  for (int i = 0; i < 3; i++) {
+    const int left = N[i] / 2 - c->istart[i];
+    k[i] = left < 0 ? 0 : (left > c->isize[i] ? c->isize[i] : left);
+  }
+  if (po->is_r2c) /* real rows: scalar strides (offt_hip_fill_input) */
+    return st->be->zero_outside(data, st->prec | OFFT_HIPK_ZERO_REAL, c->isize[0], c->isize[1], c->isize[2], k[0], k[1], k[2],
+                                2LL * c->istride[0], 2LL * c->istride[1], 1, st->s_compute) ? -1 : 0;
+  return st->be->zero_outside(data, st->prec, c->isize[0], c->isize[1], c->isize[2], k[0], k[1], k[2], c->istride[0], c->istride[1],
+                              c->istride[2], st->s_compute) ? -1 : 0;
+}
+
 void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int direction) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
@@ -2776,7 +2858,8 @@ void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int directi
   const int timed = st->timed = !(st->async && !staged);
   if (timed) be->event_record(st->ev0, st->s_compute);
   int rc;
-  if (!st->use_pipeline) rc = execute_single(po, data, direction);
+  if (direction < 0 && half_box_clear(po, data)) rc = -1;
+  else if (!st->use_pipeline) rc = execute_single(po, data, direction);
   else if (direction > 0) rc = execute_inverse_multi(po, data);
   else rc = st->slab_zyx ? execute_slab(po, data) : execute_pipeline(po, data, direction);
   if (timed) be->event_record(st->ev1, st->s_compute);
@@ -2826,6 +2909,7 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
   *fd = *l;
   fd->scale = 1.0;
   fd->out_keep = 0;
+  if (l->half) fd->half = 3; /* half box: the fused launch loads the lower half of every x line and stores only that */
   memset(fl, 0, sizeof *fl);
   fl->kind = kind;
   fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
@@ -2941,7 +3025,8 @@ int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *fil
   st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros after a convolve */
   if (timed) be->event_record(st->ev0, st->s_compute);
   const double scale = st->out_scale;
-  int rc = st->use_pipeline ? 1 : execute_convolve_single(po, data, filter, filter_kind);
+  int rc = half_box_clear(po, data);
+  if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_single(po, data, filter, filter_kind);
   if (rc > 0) {
     /* unfused: forward (unscaled), multiply on the stream the forward ends on, inverse (the output scale on its last store) */
     st->out_scale = 1.0;

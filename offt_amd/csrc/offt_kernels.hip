@@ -335,6 +335,38 @@ pointwise_k(typename vec2<T>::type *data, const void *filter, int n1, int n2, lo
   }
 }
 
+// zero a strided 3-D block outside the kept sub-box [0,k0) x [0,k1) x [0,k2) (offt_hipk_zero_outside): rows along i2, one
+// workgroup row per (i0, i1).  W = scalars of type S per 16-B store; VEC: the rows are unit-stride and 16-B aligned, a lane
+// clears 16 B at W-scalar boundaries (the first store of a row that starts inside the kept part is split into scalars)
+template <typename S, int SPE, bool VEC>
+__global__ void __launch_bounds__(256)
+zero_outside_k(S *buf, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1, long long s2, long long rows) {
+  constexpr int W = VEC ? 16 / (int)sizeof(S) : SPE;  // scalars per lane
+  typedef S vt __attribute__((ext_vector_type(W)));
+  // extents, strides and the kept length along i2 count elements of SPE scalars
+  const long long len = (long long)n2 * SPE, keep = (long long)k2 * SPE;
+  for (long long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const long long i1 = r % n1, i0 = r / n1;
+    const bool inside = i0 < k0 && i1 < k1;   // rows of the kept slab: only their tail [k2, n2) goes
+    const long long from = inside ? keep : 0;
+    S *row = buf + (i0 * s0 + i1 * s1) * SPE;
+    if constexpr (VEC) {
+      const long long a = ((long long)blockIdx.x * 256 + threadIdx.x) * W;
+      if (a + W <= from || a >= len) continue;
+      if (a >= from && a + W <= len) {
+        vt z = {};
+        __builtin_nontemporal_store(z, reinterpret_cast<vt *>(row + a));
+      } else {
+        for (long long i = a < from ? from : a; i < a + W && i < len; ++i) row[i] = (S)0;
+      }
+    } else {
+      const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+      if (e * SPE < from || e >= n2) continue;
+      for (int q = 0; q < SPE; ++q) row[e * s2 * SPE + q] = (S)0;
+    }
+  }
+}
+
 __device__ __forceinline__ double hash_val(int x, int y, int z, int c) {
   unsigned h = (unsigned)x * 73856093u ^ (unsigned)y * 19349663u ^ (unsigned)z * 83492791u ^
                (unsigned)c * 2654435761u;
@@ -429,6 +461,8 @@ void build_registry() {
   reg_mixed_f32_b();
   reg_conv_f64();
   reg_conv_f32();
+  reg_half_f64();
+  reg_half_f32();
   reg_bluestein_all();
 #endif
 }
@@ -439,22 +473,22 @@ std::mutex g_idx_mu;
 std::unordered_map<unsigned long long, std::vector<int>> g_idx;
 size_t g_idx_size = 0;
 unsigned long long variant_key(int n, int prec, bool inc, bool outc, bool r2c, bool keep = false, bool tw4 = false, bool c2r = false,
-                               bool conv = false) {
-  return ((unsigned long long)n << 9) | (conv ? 256u : 0u) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
+                               bool conv = false, int half = 0) {
+  return ((unsigned long long)n << 11) | ((unsigned long long)(half & 3) << 9) | (conv ? 256u : 0u) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
 }
 
 Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = false, bool keep = false, bool tw4 = false, bool c2r = false,
-                      bool conv = false) {
+                      bool conv = false, int half = 0) {
   std::call_once(g_reg_once, build_registry);
   std::lock_guard<std::mutex> lk(g_idx_mu);
   auto &reg = registry();
   if (g_idx_size != reg.size()) {
     g_idx.clear();
     for (size_t i = 0; i < reg.size(); ++i)
-      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r, reg[i].conv)].push_back((int)i);
+      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r, reg[i].conv, reg[i].half)].push_back((int)i);
     g_idx_size = reg.size();
   }
-  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r, conv));
+  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r, conv, half));
   if (it == g_idx.end()) return nullptr;
   Variant *def = nullptr;
   for (int i : it->second) {
@@ -909,8 +943,28 @@ Variant *pick_variant(const offt_pass_desc *d, bool allow_pair = true) {
   return v;
 }
 
+// Zero-padded half lines (offt_pass_desc::half = 1 or 2): the fft_half_panel_k instance that takes the descriptor, or
+// nullptr -- there is no other route for such a pass.  Complex lines without a split or four-step twiddles, in the forms
+// the z-y-x half-box schedule and its mirror launch: bit 1 on a contiguous load side, bit 2 on a contiguous store side,
+// never strided on both sides.  Single precision: the column-pair instance where the descriptor is eligible (pair_ok)
+// and one is registered, else the one-column one.  No cache-keeping twins: out_keep is ignored.
+Variant *pick_half(const offt_pass_desc *d, bool allow_pair = true) {
+  if (!d || (d->half != 1 && d->half != 2) || d->n < 2 || (d->n & 1)) return nullptr;
+  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
+  if (d->real_input || d->tw4 || d->in_split || d->in_split_nfloor || d->out_split || d->out_split_nfloor) return nullptr;
+  const bool inc = d->in_contig != 0, outc = d->out_contig != 0;
+  if (d->half == 1 ? !inc : !outc) return nullptr;
+  if (allow_pair && env().f32_pairs && !d->no_pairs && pair_ok(d)) {
+    Variant *p = find_variant(d->n, OFFT_PREC_F32_PAIR, inc, outc, -1, false, false, false, false, false, d->half);
+    if (p && p->half == d->half) return p;
+  }
+  Variant *v = find_variant(d->n, d->precision, inc, outc, -1, false, false, false, false, false, d->half);
+  return v && v->half == d->half && !v->conv ? v : nullptr;
+}
+
 // 1 if the descriptor, with out_keep set, runs on a kernel whose stores stay cached (a KEEP twin exists for its shape)
 extern "C" int offt_hipk_keeps_output(const offt_pass_desc *d) {
+  if (d->half) return 0;  // the half-line kernels have no cache-keeping twins
   offt_pass_desc k = *d;
   k.out_keep = 1;
   const Variant *v = pick_variant(&k);
@@ -1542,6 +1596,10 @@ int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thr
 
 // the direct layer of resolve(): a pass that is decomposed (four-step, scratch lines) is named by what would launch it alone
 const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
+  if (d->half) {
+    const Variant *h = pick_half(d);
+    return !h ? "no half-line kernel" : (h->prec == OFFT_PREC_F32_PAIR ? "fft_half_panel_k<pairs>" : "fft_half_panel_k");
+  }
   Route r;
   resolve_direct(d, nullptr, nullptr, &r);
   if (r.via == Via::BluePanel) return "fft_bluestein_k";
@@ -1549,6 +1607,8 @@ const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
   if (r.v->c2r) return r.v->mixed ? "fft_c2r_panelx_k" : "fft_c2r_panel_k";
   return r.v->mixed ? "fft_panelx_k" : (r.v->prec == OFFT_PREC_F32_PAIR ? "fft_panel_k<pairs>" : "fft_panel_k");
 }
+
+int offt_hipk_has_half(const offt_pass_desc *d) { return pick_half(d) != nullptr; }
 
 int offt_hipk_prepare(int n, int precision) {
   const bool c2r = (precision & OFFT_HIPK_PREP_C2R) != 0;
@@ -1608,6 +1668,18 @@ int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void 
     return 0;
   Tables tb;
   if (get_tables(d->n, d->precision, tb, false)) return -1;
+  if (d->half) {
+    // half lines run on their own kernels or not at all: no other route knows the bits, and none may run the full line
+    Variant *h = pick_half(d);
+    if (h && h->prec == OFFT_PREC_F32_PAIR && ((!d->in_contig && ((uintptr_t)in & 15)) || (!d->out_contig && ((uintptr_t)out & 15))))
+      h = pick_half(d, false);  // a strided side off the 16-B grid: the one-column kernel
+    if (!h) {
+      snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no half-line kernel for this descriptor (n=%d, half=%d, in_contig=%d, out_contig=%d)",
+               d->n, d->half, d->in_contig, d->out_contig);
+      return -1;
+    }
+    return launch_panel(d, in, out, tb, (hipStream_t)stream, h);
+  }
   const Route r = resolve(d, in, out);
   switch (r.via) {
     case Via::FourStep: return four_pass(d, in, out, stream, r.fs, tb);
@@ -1698,15 +1770,17 @@ Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep
   if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
   if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || f->axis_stride != 1)
     return nullptr;
-  Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true);
-  return v && v->conv && v->keep == keep ? v : nullptr;
+  if (d->half && d->half != 3) return nullptr;  // half lines: loads and stores together, or not at all
+  if (d->half && keep) return nullptr;          // (no cache-keeping twin)
+  Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true, d->half);
+  return v && v->conv && v->keep == keep && v->half == d->half ? v : nullptr;
 }
 }  // namespace
 
 int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false) != nullptr; }
 
 const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
-  return pick_conv(fwd, f, false) ? "fft_conv_panel_k" : "no fused kernel";
+  return pick_conv(fwd, f, false) ? (fwd->half ? "fft_conv_half_panel_k" : "fft_conv_panel_k") : "no fused kernel";
 }
 
 int offt_hipk_conv_pass(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream) {
@@ -1752,6 +1826,39 @@ int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind,
   else if (cx) FOR_PREC(precision, POINTWISE(T, true, 1));
   else FOR_PREC(precision, POINTWISE(T, false, 1));
 #undef POINTWISE
+  HIPK_CHECK(hipGetLastError());
+  return 0;
+}
+
+int offt_hipk_zero_outside(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1,
+                           long long s2, void *stream) {
+  const bool real = (precision & OFFT_HIPK_ZERO_REAL) != 0;
+  const int prec = precision & ~OFFT_HIPK_ZERO_REAL;
+  if (prec != OFFT_PREC_F64 && prec != OFFT_PREC_F32) { snprintf(g_err, sizeof g_err, "offt_hipk_zero_outside: bad precision %d", precision); return -1; }
+  if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
+  if (k0 < 0 || k1 < 0 || k2 < 0 || k0 > n0 || k1 > n1 || k2 > n2) { snprintf(g_err, sizeof g_err, "offt_hipk_zero_outside: kept box outside the block"); return -1; }
+  if (k0 == n0 && k1 == n1 && k2 == n2) return 0;
+  const size_t ssz = prec == OFFT_PREC_F64 ? 8 : 4;
+  const int spe = real ? 1 : 2;                      // scalars per element
+  const int w = 16 / (int)ssz;                       // scalars per 16-B store
+  // 16 B per lane: unit-stride rows that start on the 16-B grid (every row: base and the two outer strides)
+  const bool vec = s2 == 1 && !((uintptr_t)buf & 15) && !((s0 * spe) % w) && !((s1 * spe) % w);
+  const long long rows = (long long)n0 * n1;
+  const long long per_row = vec ? ((long long)n2 * spe + w - 1) / w : n2;
+  const unsigned gx = (unsigned)((per_row + 255) / 256);
+  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
+  hipStream_t sm = (hipStream_t)stream;
+  (void)hipGetLastError();
+#define ZERO_OUT(S, SPE, VEC) \
+  hipLaunchKernelGGL((zero_outside_k<S, SPE, VEC>), dim3(gx, gy), dim3(256), 0, sm, (S *)buf, n1, n2, k0, k1, k2, s0, s1, s2, rows)
+  if (prec == OFFT_PREC_F64) {
+    if (real) { if (vec) ZERO_OUT(double, 1, true); else ZERO_OUT(double, 1, false); }
+    else { if (vec) ZERO_OUT(double, 2, true); else ZERO_OUT(double, 2, false); }
+  } else {
+    if (real) { if (vec) ZERO_OUT(float, 1, true); else ZERO_OUT(float, 1, false); }
+    else { if (vec) ZERO_OUT(float, 2, true); else ZERO_OUT(float, 2, false); }
+  }
+#undef ZERO_OUT
   HIPK_CHECK(hipGetLastError());
   return 0;
 }

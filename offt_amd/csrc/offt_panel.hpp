@@ -166,17 +166,23 @@ __device__ __forceinline__ cx<T> mulw32(cx<T> d) {
 // In-register radix-R DFT (R = 2..32), radix-2 decimation in frequency with
 // compile-time twiddles.  Result is left in bit-reversed order:
 // X[k] = v[bitrev(k)].
-template <typename T, int R>
+// UZ: v[R/2 ...] are known zeros (the upper half of a zero-padded line, offt_pass_desc::half): they are not read, and
+// the first butterfly is a copy and a twiddle.
+template <typename T, int R, bool UZ = false>
 __device__ __forceinline__ void dft_reg(cx<T> *v) {
   static_for<0, ilog2(R)>([&](auto st) {
     constexpr int h = R >> (decltype(st)::value + 1);
     static_for<0, R / 2>([&](auto bi) {
       constexpr int b = (decltype(bi)::value / h) * 2 * h;
       constexpr int i = decltype(bi)::value % h;
-      cx<T> p = v[b + i], q = v[b + i + h];
-      v[b + i] = cx<T>{p.x + q.x, p.y + q.y};
-      cx<T> d{p.x - q.x, p.y - q.y};
-      v[b + i + h] = mulw32<T, i * (16 / h)>(d);
+      if constexpr (UZ && decltype(st)::value == 0) {
+        v[b + i + h] = mulw32<T, i * (16 / h)>(v[b + i]);
+      } else {
+        cx<T> p = v[b + i], q = v[b + i + h];
+        v[b + i] = cx<T>{p.x + q.x, p.y + q.y};
+        cx<T> d{p.x - q.x, p.y - q.y};
+        v[b + i + h] = mulw32<T, i * (16 / h)>(d);
+      }
     });
   });
 }
@@ -271,8 +277,12 @@ __device__ __forceinline__ int padidx(int i) {
 //   KEEP stores with the default cache policy: the next launch re-reads the output (out_keep)
 //   TW4  four-step lines (offt_kernels.hip): the twiddles w_n^(j2 k1) of the long length ride on the stores
 //   C2R  real-output z pass (offt_pass_desc::real_input = 2): n/2+1 complex inputs, n real outputs
+//   HALF zero-padded half lines (offt_pass_desc::half, fft_half_panel_k): bit 1 = axis indices >= N/2 of the input are
+//        zero and not loaded, bit 2 = output indices >= N/2 are not stored.  An element's axis index is j + cn with
+//        j < TPL and cn a compile-time multiple of TPL, and TPL divides N/2: which half an element is in is known at
+//        compile time on either side -- no predicate, no address arithmetic for the skipped half
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool KEEP, bool TW4,
-          bool C2R>
+          bool C2R, int HALF = 0>
 __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
                                            const typename vec2<T>::type *twq) {
   using V2 = typename vec2<T>::type;
@@ -290,6 +300,7 @@ __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::t
   static_assert(!(PAIR && R2C), "column pairs: complex input only");
   static_assert(!(PAIR && TW4), "four-step twiddles: one column per lane");
   static_assert(!(PAIR && C2R) && !(R2C && C2R) && !(TW4 && C2R) && (!C2R || OUTC), "real output: one column per lane, contiguous rows");
+  static_assert(HALF == 0 || (!R2C && !C2R && !TW4 && NSTAGE > 1 && (N / 2) % TPL == 0), "half lines: complex, no four-step twiddles");
 
   extern __shared__ __align__(16) unsigned char smem[];
   T *exs = reinterpret_cast<T *>(smem);
@@ -375,6 +386,8 @@ __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::t
             if (valid) val.x = reinterpret_cast<const T *>(src)[n];
             v[decltype(ii)::value] = cx<T>{val.x, (T)0};
           }
+        } else if constexpr ((HALF & 1) != 0 && cn >= N / 2) {
+          v[decltype(ii)::value] = cx<T>{T{}, T{}};  // the padding: a literal zero (and the first butterfly knows it)
         } else {
           long long off = (long long)(cn & mask) * a.in_axis;  // uniform
           if constexpr (TAB) off += a.in_tab[jb + (cn >> a.in_shift)];
@@ -452,7 +465,7 @@ __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::t
       });
     }
 
-    static_for<0, NB>([&](auto uu) { dft_reg<T, R>(&v[decltype(uu)::value * R]); });
+    static_for<0, NB>([&](auto uu) { dft_reg<T, R, s == 0 && (HALF & 1) != 0>(&v[decltype(uu)::value * R]); });
 
     if constexpr (s < NSTAGE - 1) {
       // ---- exchange through LDS: write Stockham-ordered, read strided --------
@@ -543,6 +556,7 @@ __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::t
         static_for<0, E>([&](auto ii) {
           constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
           constexpr int cn = u * TPL + t * (N / R);
+          if constexpr ((HALF & 2) != 0 && cn >= N / 2) return;  // the upper half of the output is not wanted
           const int n = j + cn;
           cx<T> x = v[u * R + bitrev(t, LR)];
           if constexpr (TW4) {
@@ -599,6 +613,13 @@ fft_c2r_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::
   panel_body<T, N, E, R0, R1, R2, COLS, INC, true, SPLIT, false, false, false, true>(a, in, out, twq);
 }
 
+// zero-padded half lines (offt_pass_desc::half = HALF, 1 or 2): a kernel of its own name, so that no older symbol changes
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, int HALF>
+__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_half_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twq) {
+  panel_body<T, N, E, R0, R1, R2, COLS, INC, OUTC, SPLIT, false, false, false, false, HALF>(a, in, out, twq);
+}
+
 // ---------------------------------------------------------------------------
 // Spectral convolution of whole lines (offt_hipk_conv_pass): load a panel, forward stages, multiply every output by the
 // filter, conjugate, one LDS round trip back into the load distribution, the stages again (an inverse by conj-in /
@@ -613,7 +634,10 @@ struct ConvArgs {
   int cplx;                     // 1: one complex value per element, 0: one real scalar per complex slot (same element index)
 };
 
-template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP>
+// HALF (fft_conv_half_panel_k, offt_pass_desc::half = 3): the lines are zero above N/2 going in and only their lower half
+// is wanted coming out -- the upper half is neither loaded nor stored (compile-time, as in panel_body); the filter and
+// everything between the two is the full line
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP, bool HALF = false>
 __device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter,
                                           const typename vec2<T>::type *twq) {
   using V2 = typename vec2<T>::type;
@@ -673,13 +697,15 @@ __device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<
     constexpr int cn = u * TPL + t * (N / R0);
     V2 val;
     val.x = 0; val.y = 0;
-    if (valid) val = gload(line + (long long)cn * a.in_axis);
+    if constexpr (!(HALF && cn >= N / 2)) {
+      if (valid) val = gload(line + (long long)cn * a.in_axis);
+    }
     v[decltype(ii)::value] = cx<T>{val.x, val.y};
   });
 
   // the forward stages of panel_body (contiguous / contiguous), ending in the last stage's register order:
   // v[u RL + bitrev(t)] holds line index j + u TPL + t N/RL
-  auto stages = [&]() {
+  auto stages = [&](auto upper_zero) {
     static_for<0, NSTAGE>([&](auto sidx) {
       constexpr int s = decltype(sidx)::value;
       constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
@@ -717,7 +743,7 @@ __device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<
           });
         });
       }
-      static_for<0, NB>([&](auto uu) { dft_reg<T, R>(&v[decltype(uu)::value * R]); });
+      static_for<0, NB>([&](auto uu) { dft_reg<T, R, s == 0 && decltype(upper_zero)::value>(&v[decltype(uu)::value * R]); });
       if constexpr (s < NSTAGE - 1) {
         constexpr int Rn = (s == 0) ? R1 : R2;
         auto wr_idx = [&](int u, int t) {
@@ -766,7 +792,7 @@ __device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<
     });
   };
 
-  stages();
+  stages(std::integral_constant<bool, HALF>{});
 
   // times H[n], then conjugated (the inverse as conj(F(conj(.)))); filter values are read once: non-temporal
   auto filt = [&](auto complex_filter) {
@@ -830,12 +856,13 @@ __device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<
   }
   xsync();  // the round trip's reads done before the first exchange of the second half writes
 
-  stages();
+  stages(std::false_type{});
 
   const T sc = (T)a.scale;
   static_for<0, E>([&](auto ii) {
     constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
     constexpr int cn = u * TPL + t * (N / RL);
+    if constexpr (HALF && cn >= N / 2) return;
     const cx<T> x = v[u * RL + bitrev(t, LRL)];
     V2 w;
     w.x = x.x * sc;
@@ -853,6 +880,12 @@ template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT
 __global__ void __launch_bounds__((N / E) * COLS, (conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
 fft_conv_panel_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twq) {
   conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP>(a, f, data, filter, twq);
+}
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_half_panel_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twq) {
+  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP, true>(a, f, data, filter, twq);
 }
 
 // ---------------------------------------------------------------------------
@@ -1236,6 +1269,7 @@ struct Variant {
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
   bool conv = false;  // fft_conv_panel_k instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
+  int half = 0;       // fft_half_panel_k / fft_conv_half_panel_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3)
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
 // (uneven, or not a power of two: grids split over 3, 6, ... ranks)
@@ -1347,6 +1381,41 @@ void reg_variant_conv() {
   add(true, (const void *)fft_conv_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
 }
 
+// half-line instances (fft_half_panel_k, offt_reg_half_*.hip).  FLAV says which of the four (flavour, bit) forms of the
+// z-y-x half-box schedule and its mirror this shape is instantiated for; T = f32x2 registers column-pair instances.
+enum { H_CS1 = 1, H_CC1 = 2, H_CC2 = 4, H_SC2 = 8, H_ALL = 15 };
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, int FLAV = H_ALL>
+void reg_variant_half() {
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int NL = lanes<T>::n;
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : (NL == 2 ? OFFT_PREC_F32_PAIR : OFFT_PREC_F32);
+  char nm[160];
+  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d%s %s half lines lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2, NL * COLS,
+           NL == 2 ? " (column pairs)" : "", SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  auto add = [&](bool inc, bool outc, int half, const void *fn) {
+    registry().push_back(Variant{N, prec, inc, outc, 0, true, false, NL * COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
+    registry().back().half = half;
+  };
+  if constexpr ((FLAV & H_CS1) != 0) add(true, false, 1, (const void *)fft_half_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, 1>);
+  if constexpr ((FLAV & H_CC1) != 0) add(true, true, 1, (const void *)fft_half_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, 1>);
+  if constexpr ((FLAV & H_CC2) != 0) add(true, true, 2, (const void *)fft_half_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, 2>);
+  if constexpr ((FLAV & H_SC2) != 0) add(false, true, 2, (const void *)fft_half_panel_k<T, N, E, R0, R1, R2, COLS, false, true, SPLIT, 2>);
+}
+
+// fused convolution on half lines (fft_conv_half_panel_k): the shapes of reg_variant_conv
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variant_conv_half() {
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  char nm[160];
+  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s convolution on half lines lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2,
+           COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES,
+                               (const void *)fft_conv_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>, nm, false, false, false, nullptr});
+  registry().back().conv = true;
+  registry().back().half = 3;
+}
+
 // mixed-radix (2^a 3^b 5^c) panel kernel: TPL threads per line instead of elements per thread.
 // FLAV limits which (in_contig, out_contig) flavours are instantiated at all (compile time), defmask says for
 // which of them this variant is the default.
@@ -1404,6 +1473,8 @@ void reg_mixed_f32_a();
 void reg_mixed_f32_b();
 void reg_conv_f64();
 void reg_conv_f32();
+void reg_half_f64();
+void reg_half_f32();
 void reg_dev();
 
 }  // namespace offtk
