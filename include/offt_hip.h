@@ -81,6 +81,10 @@ int offt_hip_convolve_fused(const struct _offt_plan *po);
  *   full spectrum of the zero-padded field, in the usual output layout.
  * Inverse: only the box of the result is defined afterwards; the rest of the block is undefined.
  * Convolve: box in, box out -- the aperiodic convolution when the kernel's support fits.
+ * Real-input (r2c) plans: the box is the reals z < Nz/2 of the rows x < Nx/2, y < Ny/2; the forward's output is the usual
+ *   Nz/2+1 half spectrum, and the inverse defines the reals of the box only (the scalars behind a row's reals stay
+ *   undefined, as after any c2r inverse).  Such a plan clears the padding and runs the ordinary schedule unless
+ *   OFFT_HIP_OPT_HALF_R2C is set: then its passes skip the padding like a complex plan's.
  * -1 (plan unchanged, text in offt_hip_last_error) if an extent is odd.  Collective on several ranks. */
 int offt_hip_set_half_box(struct _offt_plan *po, int on);
 /* 1: every pass of this plan skips the padding (half-line kernels); 0: the library clears the padding and runs the
@@ -110,6 +114,9 @@ int offt_hip_wait(struct _offt_plan *po);
 #define OFFT_HIP_OPT_MIN_MSG 7         /* (collective) bytes a per-peer message is merged up to (OFFT_MIN_MSG) */
 #define OFFT_HIP_OPT_EXEC_TIMEOUT_S 8  /* bound of the final wait of a multi-rank execute (OFFT_EXEC_TIMEOUT) */
 #define OFFT_HIP_OPT_P2P_TIMEOUT_S 9   /* bound of one flag wait of the direct-store exchange (OFFT_P2P_TIMEOUT) */
+#define OFFT_HIP_OPT_HALF_R2C 10       /* half box on a real-input (r2c) plan: 1 = its passes skip the padding where every pass has a
+                                          half-line kernel, 0 (default) = always clear and run the ordinary schedule.  Set before or
+                                          after offt_hip_set_half_box: a half box that is on changes route at once (OFFT_HALF_R2C) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

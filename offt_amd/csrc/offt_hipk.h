@@ -70,7 +70,10 @@ typedef struct offt_pass_desc {
   /* zero-padded half lines (n even).  Bit 1: axis indices >= n/2 of the INPUT line are zero and are not read.  Bit 2: only
    * output indices < n/2 are stored, the others are not written.  Kernels: power-of-two lines of 64 ... 1024 points,
    * complex, no split, in the four flavours of offt_hipk_has_half; a pass that asks for a bit no kernel implements
-   * fails, it never runs the full line.  (The field sits in what used to be alignment padding: no other offset moves.) */
+   * fails, it never runs the full line.  Together with real_input, two forms: real_input = 1 with bit 1 (the reals
+   * n >= n/2 of a row are zero and not read; contiguous in, strided out) and real_input = 2 with bit 2 (the reals n >= n/2
+   * of a row are not written; strided in, contiguous out).  (The field sits in what used to be alignment padding: no
+   * other offset moves.) */
   int half;
   /* first sub-pass of a four-step line (set by the launcher itself, offt_kernels.hip): multiply output index k1 of column
    * j2 (tw4_b1 = 0) or of batch entry b1 = j2 (tw4_b1 = 1) by tw4[k1 * tw4_n2 + j2] = w_n^(k1 j2), a table of the long
@@ -113,7 +116,9 @@ int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thr
 const char *offt_hipk_kernel_name(const offt_pass_desc *d);
 /* 1 if a half-line kernel exists for the descriptor (d->half = 1 or 2): power-of-two lines of 64 ... 1024 points, complex,
  * no split, no four-step twiddles, and one of the flavours contiguous-in / strided-out with bit 1, contiguous / contiguous
- * with bit 1 or bit 2, strided-in / contiguous-out with bit 2.  A registry lookup: needs no device. */
+ * with bit 1 or bit 2, strided-in / contiguous-out with bit 2.  Real rows: real_input = 1 with bit 1 on contiguous-in /
+ * strided-out and real_input = 2 with bit 2 on strided-in / contiguous-out, nothing else.  A registry lookup: needs no
+ * device. */
 int offt_hipk_has_half(const offt_pass_desc *d);
 /* ---- spectral convolution (offt_hip_execute_convolve) ------------------------------------------------------------------
  * A filter H laid out like a forward pass's OUTPUT: kind 0 = one real scalar of the pass's precision per complex slot

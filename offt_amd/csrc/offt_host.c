@@ -439,6 +439,7 @@ typedef struct hip_state {
     int comm_streams;    /* pencil schedule: 2 = row and column exchanges on separate streams */
     long long min_msg;   /* tiles are merged upwards until a per-peer message has this many bytes */
     int f32_pairs;       /* single precision: 0 = never use the column-pair kernels */
+    int half_r2c;        /* half box on a real-input plan: 1 = its passes may skip the padding (half_can_prune), 0 = always the fallback */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -1123,6 +1124,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.comm_streams = getenv("OFFT_COMM_STREAMS") ? atoi(getenv("OFFT_COMM_STREAMS")) : 1;
   st->opt.min_msg = getenv("OFFT_MIN_MSG") ? atoll(getenv("OFFT_MIN_MSG")) : 4LL << 20;
   st->opt.f32_pairs = !(getenv("OFFT_F32_PAIRS") && atoi(getenv("OFFT_F32_PAIRS")) == 0);
+  st->opt.half_r2c = getenv("OFFT_HALF_R2C") && atoi(getenv("OFFT_HALF_R2C")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
   st->opt.block_pad = getenv("OFFT_BLOCK_PAD") && atoi(getenv("OFFT_BLOCK_PAD")) != 0;
@@ -1583,11 +1585,16 @@ int offt_hip_set_exchange(struct _offt_plan *po, int mode) {
 }
 /* plan-level options (offt_hip.h).  Options that shape buffers (slab chunk, comm streams, minimum message, self bypass)
  * rebuild the mesh like offt_hip_set_exchange and are therefore collective. */
+static int half_can_prune(struct _offt_plan *po);
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
   hip_state *st = (hip_state *)po->hip_state;
   int rebuild = 0;
   inv_cache_drop(st);
   switch (option) {
+    case OFFT_HIP_OPT_HALF_R2C: /* a half box that is already on takes the other route from the next call on */
+      st->opt.half_r2c = value != 0;
+      if (st->half_box) st->half_pruned = half_can_prune(po);
+      break;
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
@@ -1622,6 +1629,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_ZGROUP_MIB: return st->opt.zgroup_mib;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: return st->opt.zgroup_streams;
     case OFFT_HIP_OPT_F32_PAIRS: return st->opt.f32_pairs;
+    case OFFT_HIP_OPT_HALF_R2C: return st->opt.half_r2c;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
     case OFFT_HIP_OPT_P2P_TIMEOUT_S: return (long long)st->opt.p2p_timeout_s;
@@ -1795,7 +1803,11 @@ static void single_schedule(struct _offt_plan *po, void *data, int dir, single_s
        *   P2  columns x < Nx/2            loads y < Ny/2, stores every y
        *   P3  every line                  loads x < Nx/2, stores every x
        * 1/8 + 1/4 + 1/4 + 1/2 + 1/2 + 1 = 2.625 sweeps over the volume instead of 6.  What P2 does not store (x >= Nx/2 of
-       * the caller's array) P3 does not load.  Mirrored, the inverse stores the box only (half = 2). */
+       * the caller's array) P3 does not load.  Mirrored, the inverse stores the box only (half = 2).
+       * A real-input plan (OFFT_HIP_OPT_HALF_R2C) runs the same three launches: P1 is the real-input pass, loads the reals
+       * z < Nzf/2 of its rows and stores the Nzf/2+1 complex values Nz counts here; P2 and P3 work on those planes.  The
+       * real field has the bytes of the half-spectrum volume, so in sweeps over THAT volume the count is the same, 2.625
+       * instead of 6 (and of 6.875 with the clear of the fallback route, which writes 7/8 of the real field). */
       d[0].ncols = Ny / 2; d[0].nb1 = Nx / 2;
       d[1].ncols = Nx / 2;
       d[0].half = d[1].half = d[2].half = 1;
@@ -2769,12 +2781,13 @@ static int wait_compute(hip_state *st) {
 /* ------------------------------------------------------------------------- */
 /* half box (offt_hip_set_half_box)                                           */
 /* ------------------------------------------------------------------------- */
-/* 1 if every launch of this plan's forward and inverse can skip the padding: one rank, complex, the z-y-x layout, a
- * half-line kernel for each of the six descriptors (a registry lookup that needs no device: a test backend gets the
- * same answer as the HIP one, and has to interpret offt_pass_desc::half) */
+/* 1 if every launch of this plan's forward and inverse can skip the padding: one rank, the z-y-x layout, a half-line
+ * kernel for each of the six descriptors (a registry lookup that needs no device: a test backend gets the same answer
+ * as the HIP one, and has to interpret offt_pass_desc::half).  A real-input plan only with OFFT_HIP_OPT_HALF_R2C set:
+ * its two z passes are then the real-input pass with half = 1 and the real-output pass with half = 2. */
 static int half_can_prune(struct _offt_plan *po) {
   hip_state *st = (hip_state *)po->hip_state;
-  if (st->use_pipeline || po->is_r2c) return 0;
+  if (st->use_pipeline || (po->is_r2c && !st->opt.half_r2c)) return 0;
   single_sched fw, iv;
   const int was = st->half_pruned;
   st->half_pruned = 1;

@@ -280,7 +280,9 @@ __device__ __forceinline__ int padidx(int i) {
 //   HALF zero-padded half lines (offt_pass_desc::half, fft_half_panel_k): bit 1 = axis indices >= N/2 of the input are
 //        zero and not loaded, bit 2 = output indices >= N/2 are not stored.  An element's axis index is j + cn with
 //        j < TPL and cn a compile-time multiple of TPL, and TPL divides N/2: which half an element is in is known at
-//        compile time on either side -- no predicate, no address arithmetic for the skipped half
+//        compile time on either side -- no predicate, no address arithmetic for the skipped half.  The two real ends
+//        of a half-box chain (fft_half_r2c_panel_k, fft_half_c2r_panel_k): R2C with bit 1 -- the reals n >= N/2 of a row
+//        are zero and not loaded; C2R with bit 2 -- the reals n >= N/2 of a row are not stored
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool KEEP, bool TW4,
           bool C2R, int HALF = 0>
 __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
@@ -300,7 +302,9 @@ __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::t
   static_assert(!(PAIR && R2C), "column pairs: complex input only");
   static_assert(!(PAIR && TW4), "four-step twiddles: one column per lane");
   static_assert(!(PAIR && C2R) && !(R2C && C2R) && !(TW4 && C2R) && (!C2R || OUTC), "real output: one column per lane, contiguous rows");
-  static_assert(HALF == 0 || (!R2C && !C2R && !TW4 && NSTAGE > 1 && (N / 2) % TPL == 0), "half lines: complex, no four-step twiddles");
+  static_assert(HALF == 0 || (!TW4 && NSTAGE > 1 && (N / 2) % TPL == 0), "half lines: no four-step twiddles");
+  static_assert(HALF == 0 || ((!R2C || (HALF == 1 && INC && !OUTC)) && (!C2R || (HALF == 2 && !INC))),
+                "half lines, real ends: bit 1 on the real-input pass, bit 2 on the real-output pass");
 
   extern __shared__ __align__(16) unsigned char smem[];
   T *exs = reinterpret_cast<T *>(smem);
@@ -380,6 +384,8 @@ __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::t
           }
           if (valid) val = *p;
           v[decltype(ii)::value] = cx<T>{val.x, xor_sign(val.y, lo ? conj_mask : conj_mask ^ 0x80000000u)};
+        } else if constexpr (R2C && (HALF & 1) != 0 && cn >= N / 2) {
+          v[decltype(ii)::value] = cx<T>{T{}, T{}};  // the padding of a real row: a literal zero, as on a complex line below
         } else if constexpr (R2C) {
           // n real values at the head of the row: element n is the n-th T of the row
           if constexpr (!PAIR) {
@@ -618,6 +624,20 @@ template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, 
 __global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
 fft_half_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twq) {
   panel_body<T, N, E, R0, R1, R2, COLS, INC, OUTC, SPLIT, false, false, false, false, HALF>(a, in, out, twq);
+}
+
+// the real ends of a half-box chain on a real-input plan (offt_pass_desc::real_input with ::half), names of their own again:
+// the real-input z pass that does not load the reals n >= N/2 (contiguous rows in, strided out) ...
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_half_r2c_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twq) {
+  panel_body<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, true, false, false, false, 1>(a, in, out, twq);
+}
+// ... and its mirror image, the real-output z pass that does not store them (strided in, contiguous rows out)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_half_c2r_panel_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twq) {
+  panel_body<T, N, E, R0, R1, R2, COLS, false, true, SPLIT, false, false, false, true, 2>(a, in, out, twq);
 }
 
 // ---------------------------------------------------------------------------
@@ -1269,7 +1289,8 @@ struct Variant {
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
   bool conv = false;  // fft_conv_panel_k instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
-  int half = 0;       // fft_half_panel_k / fft_conv_half_panel_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3)
+  int half = 0;       // fft_half_panel_k / fft_conv_half_panel_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
+                      // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2)
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
 // (uneven, or not a power of two: grids split over 3, 6, ... ranks)
@@ -1402,6 +1423,25 @@ void reg_variant_half() {
   if constexpr ((FLAV & H_SC2) != 0) add(false, true, 2, (const void *)fft_half_panel_k<T, N, E, R0, R1, R2, COLS, false, true, SPLIT, 2>);
 }
 
+// the real ends of a half-box chain (fft_half_r2c_panel_k, fft_half_c2r_panel_k; offt_reg_half_real_*.hip): one column per
+// lane, keyed by r2c / c2r together with half, so that no complex or full-line lookup finds them
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variant_half_real() {
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  static_assert(lanes<T>::n == 1, "real rows: one column per lane");
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  char nm[160];
+  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s half lines, real rows lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2, COLS,
+           SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  registry().push_back(Variant{N, prec, true, false, 0, true, true, COLS, Cfg::NT, E, Cfg::LDS_BYTES,
+                               (const void *)fft_half_r2c_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>, nm, false, false, false, nullptr});
+  registry().back().half = 1;
+  registry().push_back(Variant{N, prec, false, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES,
+                               (const void *)fft_half_c2r_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>, nm, false, false, false, nullptr});
+  registry().back().c2r = true;
+  registry().back().half = 2;
+}
+
 // fused convolution on half lines (fft_conv_half_panel_k): the shapes of reg_variant_conv
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant_conv_half() {
@@ -1475,6 +1515,8 @@ void reg_conv_f64();
 void reg_conv_f32();
 void reg_half_f64();
 void reg_half_f32();
+void reg_half_real_f64();
+void reg_half_real_f32();
 void reg_dev();
 
 }  // namespace offtk

@@ -7,7 +7,12 @@ stream; min and median are reported, the baseline's own spread ((median - min) /
 bytes per second of the option-on run against its byte model:
   forward / inverse   (1/8 + 1/4 + 1/4 + 1/2 + 1/2 + 1) = 2.625 sweeps over the complex volume (the full transform makes 6)
   convolve            z 3/8, y 3/4, fused x 1 (half in, half out), y 3/4, z 3/8 = 3.25 sweeps, plus the filter once
-usage: half_box_probe.py [f64|f32:]N ... [--runs R] [--out FILE]   (default: 512 f32:512 1024 f32:1024)"""
+Real-input plans (r2c:): the half box stays on and OFFT_HIP_OPT_HALF_R2C is switched between 1 (the passes skip the
+padding) and 0 (the library clears the padding of the real rows and runs the ordinary schedule: what a caller gets without
+the option).  The models are the same numbers of sweeps, over the half-spectrum volume Nx Ny (Nz/2+1) complex elements --
+the real field has as many bytes, its box is 1/8 of a sweep; the baseline makes 6 sweeps and its clear writes 7/8 of one.
+usage: half_box_probe.py [r2c:][f64|f32:]N ... [--runs R] [--out FILE]
+       (default: 512 f32:512 1024 f32:1024 r2c:512 r2c:f32:512 r2c:1024 r2c:f32:1024)"""
 import os
 import statistics
 import sys
@@ -31,7 +36,7 @@ def main():
         i = args.index("--out")
         out = open(args[i + 1], "a")
         del args[i:i + 2]
-    specs = args or ["512", "f32:512", "1024", "f32:1024"]
+    specs = args or ["512", "f32:512", "1024", "f32:1024", "r2c:512", "r2c:f32:512", "r2c:1024", "r2c:f32:1024"]
     torch.cuda.set_device(0)
 
     def emit(line):
@@ -41,17 +46,21 @@ def main():
             out.flush()
 
     for spec in specs:
-        kind, _, n_s = spec.rpartition(":")
+        *kinds, n_s = spec.split(":")
         n = int(n_s)
-        prec = api.F32 if kind == "f32" else api.F64
+        r2c = "r2c" in kinds
+        prec = api.F32 if "f32" in kinds else api.F64
         td = torch.float32 if prec == api.F32 else torch.float64
         esz = 4 if prec == api.F32 else 8
-        po = api.offt_3d_init(n, n, n, precision=prec)
+        po = api.offt_3d_init(n, n, n, precision=prec, is_r2c=int(r2c))
         c = api.comm_dict(po)
         dev = torch.zeros(api.local_elems(po) * 2, dtype=td, device="cuda")
         H = torch.rand(api.local_elems(po), dtype=td, device="cuda") * (1.0 / float(n) ** 3)
         s = c["istride"]
-        vol = torch.as_strided(dev, (n, n, n, 2), (2 * s[0], 2 * s[1], 2 * s[2], 1))
+        if r2c:   # the real rows: scalar strides
+            vol = torch.as_strided(dev, (n, n, n), (2 * s[0], 2 * s[1], 1))
+        else:
+            vol = torch.as_strided(dev, (n, n, n, 2), (2 * s[0], 2 * s[1], 2 * s[2], 1))
         h = n // 2
         vol[:h, :h, :h].uniform_(-1.0, 1.0)
         torch.cuda.synchronize()
@@ -64,7 +73,7 @@ def main():
             vol[:h, :h, h:].zero_()
 
         def fwd(on):
-            if not on:
+            if not on and not r2c:
                 clear()
             api.offt_3d_execute_dir(po, p, p, -1)
 
@@ -72,24 +81,32 @@ def main():
             api.offt_3d_execute_dir(po, p, p, +1)
 
         def conv(on):
-            if not on:
+            if not on and not r2c:
                 clear()
             api.offt_hip_execute_convolve(po, p, H.data_ptr(), api.FILTER_REAL)
 
+        def route(on):
+            if r2c:
+                assert L.offt_hip_set_option(po, api.OPT_HALF_R2C, 1 if on else 0) == 0
+            else:
+                api.offt_hip_set_half_box(po, on)
+
         def timed(fn, on):
-            api.offt_hip_set_half_box(po, on)
+            route(on)
             ev[0].record()
             fn(on)
             ev[1].record()
             torch.cuda.synchronize()
             return ev[0].elapsed_time(ev[1]) * 1e-3
 
-        V = 2.0 * esz * float(n) ** 3
-        models = {"forward": 2.625 * V, "inverse": 2.625 * V, "convolve": 3.25 * V + esz * float(n) ** 3}
+        V = 2.0 * esz * float(n) ** 2 * (n // 2 + 1 if r2c else n)
+        models = {"forward": 2.625 * V, "inverse": 2.625 * V, "convolve": 3.25 * V + 0.5 * V}
         api.offt_hip_set_half_box(po, True)
+        route(True)
         pruned = api.offt_hip_half_box_pruned(po)
         fused = api.offt_hip_convolve_fused(po)
-        tag = f"{'f32' if prec == api.F32 else 'f64'} {n}^3"
+        tag = f"{'r2c ' if r2c else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3"
+        base = "option off: library clear + ordinary" if r2c else "clear + ordinary"
         for name, fn in (("forward", fwd), ("inverse", inv), ("convolve", conv)):
             t = {True: [], False: []}
             for _ in range(3):
@@ -103,7 +120,7 @@ def main():
             off_min, off_med = min(t[False]), statistics.median(t[False])
             emit(f"{tag} {name}: half box [{'pruned' if pruned else 'fallback'}{', fused' if name == 'convolve' and fused else ''}] "
                  f"min {on_min * 1e3:.3f} median {on_med * 1e3:.3f} ms ({models[name] / on_min / 1e12:.2f} TB/s of the {models[name] / V:.3f}-sweep model)  "
-                 f"baseline (clear + ordinary) min {off_min * 1e3:.3f} median {off_med * 1e3:.3f} ms (spread {(off_med - off_min) / off_min * 100:.1f} %)  "
+                 f"baseline ({base}) min {off_min * 1e3:.3f} median {off_med * 1e3:.3f} ms (spread {(off_med - off_min) / off_min * 100:.1f} %)  "
                  f"ratio min {off_min / on_min:.2f}x median {off_med / on_med:.2f}x  runs {runs}")
         api.offt_3d_fin(po)
         del dev, H, vol
