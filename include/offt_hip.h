@@ -85,6 +85,8 @@ int offt_hip_convolve_fused(const struct _offt_plan *po);
  *   Nz/2+1 half spectrum, and the inverse defines the reals of the box only (the scalars behind a row's reals stay
  *   undefined, as after any c2r inverse).  Such a plan clears the padding and runs the ordinary schedule unless
  *   OFFT_HIP_OPT_HALF_R2C is set: then its passes skip the padding like a complex plan's.
+ * Extents that are no powers of two: such a plan clears the padding and runs the ordinary schedule unless
+ *   OFFT_HIP_OPT_HALF_MIXED is set and every extent has a half-line kernel (complex plans only).
  * -1 (plan unchanged, text in offt_hip_last_error) if an extent is odd.  Collective on several ranks. */
 int offt_hip_set_half_box(struct _offt_plan *po, int on);
 /* 1: every pass of this plan skips the padding (half-line kernels); 0: the library clears the padding and runs the
@@ -117,6 +119,11 @@ int offt_hip_wait(struct _offt_plan *po);
 #define OFFT_HIP_OPT_HALF_R2C 10       /* half box on a real-input (r2c) plan: 1 = its passes skip the padding where every pass has a
                                           half-line kernel, 0 (default) = always clear and run the ordinary schedule.  Set before or
                                           after offt_hip_set_half_box: a half box that is on changes route at once (OFFT_HALF_R2C) */
+#define OFFT_HIP_OPT_HALF_MIXED 11     /* half box on a plan with an extent that is no power of two: 1 = its passes skip the padding where
+                                          every pass has a half-line kernel (96, 192, 320, 384, 640, 768, 1000 points in double, 384,
+                                          640, 768, 1000 in single precision, next to the powers of two from 64 to 1024; complex plans),
+                                          0 (default) = always clear and run the ordinary schedule.  Set before or after
+                                          offt_hip_set_half_box, like OFFT_HIP_OPT_HALF_R2C (OFFT_HALF_MIXED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

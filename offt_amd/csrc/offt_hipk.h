@@ -68,11 +68,13 @@ typedef struct offt_pass_desc {
   /* single precision: 1 = do not use the column-pair kernels for this pass (plan option OFFT_HIP_OPT_F32_PAIRS) */
   int no_pairs;
   /* zero-padded half lines (n even).  Bit 1: axis indices >= n/2 of the INPUT line are zero and are not read.  Bit 2: only
-   * output indices < n/2 are stored, the others are not written.  Kernels: power-of-two lines of 64 ... 1024 points,
-   * complex, no split, in the four flavours of offt_hipk_has_half; a pass that asks for a bit no kernel implements
-   * fails, it never runs the full line.  Together with real_input, two forms: real_input = 1 with bit 1 (the reals
-   * n >= n/2 of a row are zero and not read; contiguous in, strided out) and real_input = 2 with bit 2 (the reals n >= n/2
-   * of a row are not written; strided in, contiguous out).  (The field sits in what used to be alignment padding: no
+   * output indices < n/2 are stored, the others are not written.  Kernels: power-of-two lines of 64 ... 1024 points
+   * (fft_half_panel_k) and the mixed-radix lengths 96, 192, 320, 384, 640, 768, 1000 in double and 384, 640, 768, 1000 in
+   * single precision (fft_half_panelx_k), complex, no split, in the four flavours of offt_hipk_has_half; a pass that asks
+   * for a bit no kernel implements fails, it never runs the full line.  Together with real_input, two forms, at the
+   * power-of-two lengths only: real_input = 1 with bit 1 (the reals n >= n/2 of a row are zero and not read; contiguous
+   * in, strided out) and real_input = 2 with bit 2 (the reals n >= n/2 of a row are not written; strided in, contiguous
+   * out).  (The field sits in what used to be alignment padding: no
    * other offset moves.) */
   int half;
   /* first sub-pass of a four-step line (set by the launcher itself, offt_kernels.hip): multiply output index k1 of column
@@ -114,10 +116,11 @@ int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thr
  * launcher's resolve().  A pass that is decomposed (four-step, lines through scratch) launches several kernels and is
  * named by the kernel that would take its descriptor alone.                      */
 const char *offt_hipk_kernel_name(const offt_pass_desc *d);
-/* 1 if a half-line kernel exists for the descriptor (d->half = 1 or 2): power-of-two lines of 64 ... 1024 points, complex,
+/* 1 if a half-line kernel exists for the descriptor (d->half = 1 or 2): power-of-two lines of 64 ... 1024 points or one of
+ * the mixed-radix lengths listed at offt_pass_desc::half (offt_hipk_kernel_name: "fft_half_panelx_k"), complex,
  * no split, no four-step twiddles, and one of the flavours contiguous-in / strided-out with bit 1, contiguous / contiguous
- * with bit 1 or bit 2, strided-in / contiguous-out with bit 2.  Real rows: real_input = 1 with bit 1 on contiguous-in /
- * strided-out and real_input = 2 with bit 2 on strided-in / contiguous-out, nothing else.  A registry lookup: needs no
+ * with bit 1 or bit 2, strided-in / contiguous-out with bit 2.  Real rows, power-of-two lengths only: real_input = 1 with
+ * bit 1 on contiguous-in / strided-out and real_input = 2 with bit 2 on strided-in / contiguous-out, nothing else.  A registry lookup: needs no
  * device. */
 int offt_hipk_has_half(const offt_pass_desc *d);
 /* ---- spectral convolution (offt_hip_execute_convolve) ------------------------------------------------------------------

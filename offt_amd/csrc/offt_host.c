@@ -440,6 +440,8 @@ typedef struct hip_state {
     long long min_msg;   /* tiles are merged upwards until a per-peer message has this many bytes */
     int f32_pairs;       /* single precision: 0 = never use the column-pair kernels */
     int half_r2c;        /* half box on a real-input plan: 1 = its passes may skip the padding (half_can_prune), 0 = always the fallback */
+    int half_mixed;      /* half box with a length that is no power of two: 1 = its passes may skip the padding where every pass has a
+                            half-line kernel (half_can_prune), 0 = always the fallback */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -1125,6 +1127,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.min_msg = getenv("OFFT_MIN_MSG") ? atoll(getenv("OFFT_MIN_MSG")) : 4LL << 20;
   st->opt.f32_pairs = !(getenv("OFFT_F32_PAIRS") && atoi(getenv("OFFT_F32_PAIRS")) == 0);
   st->opt.half_r2c = getenv("OFFT_HALF_R2C") && atoi(getenv("OFFT_HALF_R2C")) != 0;
+  st->opt.half_mixed = getenv("OFFT_HALF_MIXED") && atoi(getenv("OFFT_HALF_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
   st->opt.block_pad = getenv("OFFT_BLOCK_PAD") && atoi(getenv("OFFT_BLOCK_PAD")) != 0;
@@ -1595,6 +1598,10 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
       st->opt.half_r2c = value != 0;
       if (st->half_box) st->half_pruned = half_can_prune(po);
       break;
+    case OFFT_HIP_OPT_HALF_MIXED: /* likewise */
+      st->opt.half_mixed = value != 0;
+      if (st->half_box) st->half_pruned = half_can_prune(po);
+      break;
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
@@ -1630,6 +1637,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_ZGROUP_STREAMS: return st->opt.zgroup_streams;
     case OFFT_HIP_OPT_F32_PAIRS: return st->opt.f32_pairs;
     case OFFT_HIP_OPT_HALF_R2C: return st->opt.half_r2c;
+    case OFFT_HIP_OPT_HALF_MIXED: return st->opt.half_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
     case OFFT_HIP_OPT_P2P_TIMEOUT_S: return (long long)st->opt.p2p_timeout_s;
@@ -2784,10 +2792,16 @@ static int wait_compute(hip_state *st) {
 /* 1 if every launch of this plan's forward and inverse can skip the padding: one rank, the z-y-x layout, a half-line
  * kernel for each of the six descriptors (a registry lookup that needs no device: a test backend gets the same answer
  * as the HIP one, and has to interpret offt_pass_desc::half).  A real-input plan only with OFFT_HIP_OPT_HALF_R2C set:
- * its two z passes are then the real-input pass with half = 1 and the real-output pass with half = 2. */
+ * its two z passes are then the real-input pass with half = 1 and the real-output pass with half = 2.  A plan with a
+ * length that is no power of two only with OFFT_HIP_OPT_HALF_MIXED set: the six descriptors are asked about then as for
+ * any other plan.  The mixed-radix lengths have complex half-line kernels only: a real-input plan with such a length
+ * falls back whatever the two options say (also where only its x or y extent is one: that chain has not been run). */
 static int half_can_prune(struct _offt_plan *po) {
   hip_state *st = (hip_state *)po->hip_state;
   if (st->use_pipeline || (po->is_r2c && !st->opt.half_r2c)) return 0;
+  const int N[3] = {po->Nx, po->Ny, po->Nz};
+  for (int i = 0; i < 3; i++)
+    if ((!st->opt.half_mixed || po->is_r2c) && (N[i] & (N[i] - 1))) return 0;
   single_sched fw, iv;
   const int was = st->half_pruned;
   st->half_pruned = 1;

@@ -465,6 +465,8 @@ void build_registry() {
   reg_half_f32();
   reg_half_real_f64();
   reg_half_real_f32();
+  reg_half_mixed_f64();
+  reg_half_mixed_f32();
   reg_bluestein_all();
 #endif
 }
@@ -945,7 +947,9 @@ Variant *pick_variant(const offt_pass_desc *d, bool allow_pair = true) {
   return v;
 }
 
-// Zero-padded half lines (offt_pass_desc::half = 1 or 2): the fft_half_panel_k instance that takes the descriptor, or
+// Zero-padded half lines (offt_pass_desc::half = 1 or 2): the fft_half_panel_k instance (a power of two from 64 to 1024
+// points) or the fft_half_panelx_k instance (the mixed-radix lengths of offt_reg_half_mixed_*.hip, one column per lane,
+// complex lines only) that takes the descriptor, or
 // nullptr -- there is no other route for such a pass.  Complex lines without a split or four-step twiddles, in the forms
 // the z-y-x half-box schedule and its mirror launch: bit 1 on a contiguous load side, bit 2 on a contiguous store side,
 // never strided on both sides.  Single precision: the column-pair instance where the descriptor is eligible (pair_ok)
@@ -1611,6 +1615,7 @@ const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
   if (d->half) {
     const Variant *h = pick_half(d);
     if (h && (h->r2c || h->c2r)) return h->r2c ? "fft_half_r2c_panel_k" : "fft_half_c2r_panel_k";
+    if (h && h->mixed) return "fft_half_panelx_k";
     return !h ? "no half-line kernel" : (h->prec == OFFT_PREC_F32_PAIR ? "fft_half_panel_k<pairs>" : "fft_half_panel_k");
   }
   Route r;

@@ -958,15 +958,20 @@ __device__ __forceinline__ cx<T> mulwr(cx<T> d) {
 // In-register DFT of R = 2^a 3^b 5^c points, decimation in frequency by the smallest prime p
 // (R = p m):  y_d[b] = w_R^(b d) * sum_a x[m a + b] w_p^(a d)  stored at v[m d + b], then a
 // DFT of length m on every block d.  X[d + p c] ends in v[m d + perm_mixed(m, c)].
-template <typename T, int R>
+// UZ (R even, so p = 2): v[R/2 ...] are known zeros (the upper half of a zero-padded line, offt_pass_desc::half): they are
+// not read, and the first butterfly is a copy and a twiddle (see dft_reg).
+template <typename T, int R, bool UZ = false>
 __device__ __forceinline__ void dft_mixed(cx<T> *v) {
   if constexpr (R > 1) {
     constexpr int p = first_factor(R), m = R / p;
+    static_assert(!UZ || p == 2, "known-zero upper half: even radix");
     static_assert(p == 2 || p == 3 || p == 5 || p == 7 || p == 11 || p == 13 || p == 17 || p == 19 || p == 23 || p == 29 || p == 31,
                   "register radix must be a product of primes <= 13 or a prime <= 31");
     static_for<0, m>([&](auto bb) {
       constexpr int b = decltype(bb)::value;
-      if constexpr (p == 2) {
+      if constexpr (UZ) {
+        v[m + b] = mulwr<T, R, b>(v[b]);
+      } else if constexpr (p == 2) {
         const cx<T> x0 = v[b], x1 = v[m + b];
         v[b] = cx<T>{x0.x + x1.x, x0.y + x1.y};
         v[m + b] = mulwr<T, R, b>(cx<T>{x0.x - x1.x, x0.y - x1.y});
@@ -1058,8 +1063,13 @@ struct PanelXCfg {
   static constexpr int WPS_E = WPS < WPS_REG ? (WPS < WPS_MIN ? WPS_MIN : WPS) : (WPS_REG < WPS_MIN ? WPS_MIN : WPS_REG);
 };
 
-// the body of fft_panelx_k and fft_c2r_panelx_k (thin wrappers below, see panel_body)
-template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool C2R>
+// the body of fft_panelx_k, fft_c2r_panelx_k and fft_half_panelx_k (thin wrappers below, see panel_body)
+//   HALF zero-padded half lines (offt_pass_desc::half), with the meaning it has in panel_body.  A load index is
+//        n = q + t N/R0 with q < N/R0 and t a compile-time constant: with R0 even, n >= N/2 exactly when t >= R0/2, whatever
+//        TPL is and whether or not the butterfly is a predicated one.  The same holds for a store index n = q + t N/R of the
+//        last stage's radix R.  So the skipped half costs no load, no predicate and no address on either side; the first
+//        and the last radix of a half instance are even.
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool C2R, int HALF = 0>
 __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
                                             const typename vec2<T>::type *twt) {
   using V2 = typename vec2<T>::type;
@@ -1070,6 +1080,8 @@ __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::
   static_assert(smooth235(R0) && smooth235(R1) && smooth235(R2), "radices must be products of primes <= 13, or primes <= 31");
   static_assert(R0 <= 32 && R1 <= 32 && R2 <= 32, "register radix <= 32");
   static_assert(!(R2C && C2R) && (!C2R || OUTC), "real output: contiguous rows");
+  constexpr int RLAST = NSTAGE == 3 ? R2 : (NSTAGE == 2 ? R1 : R0);
+  static_assert(HALF == 0 || (R0 % 2 == 0 && RLAST % 2 == 0 && !R2C && !C2R), "half lines: complex, first and last radix even");
 
   extern __shared__ __align__(16) unsigned char smem[];
   T *exs = reinterpret_cast<T *>(smem);
@@ -1107,6 +1119,10 @@ __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::
     auto load_all = [&](auto has_split) {
       static_for<0, Cfg::NB0 * R0>([&](auto ii) {
         constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+        if constexpr ((HALF & 1) != 0 && 2 * t >= R0) {
+          v[decltype(ii)::value] = cx<T>{T{}, T{}};  // the padding: a literal zero (and the first butterfly knows it)
+          return;
+        }
         const int q = j + u * TPL;
         const int n = q + t * NBF;
         const bool live = valid && ((u + 1) * TPL <= NBF || q < NBF);
@@ -1167,7 +1183,7 @@ __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::
       });
     }
 
-    static_for<0, NB>([&](auto uu) { dft_mixed<T, R>(&v[decltype(uu)::value * R]); });
+    static_for<0, NB>([&](auto uu) { dft_mixed<T, R, s == 0 && (HALF & 1) != 0>(&v[decltype(uu)::value * R]); });
 
     if constexpr (s < NSTAGE - 1) {
       // ---- exchange through LDS: write Stockham-ordered, read strided --------
@@ -1236,6 +1252,7 @@ __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::
       auto store_all = [&](auto has_split) {
         static_for<0, NB * R>([&](auto ii) {
           constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+          if constexpr ((HALF & 2) != 0 && 2 * t >= R) return;  // the upper half of the output is not wanted
           const int q = j + u * TPL;
           const int n = q + t * NBF;
           constexpr int src = u * R + perm_mixed(R, t);
@@ -1268,6 +1285,14 @@ fft_c2r_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>:
   panelx_body<T, N, TPL, R0, R1, R2, COLS, INC, true, SPLIT, false, true>(a, in, out, twt);
 }
 
+// zero-padded half lines of a mixed-radix length (offt_pass_desc::half = HALF, 1 or 2): a kernel of its own name, as
+// fft_half_panel_k is for the power-of-two body -- fft_panelx_k and fft_c2r_panelx_k keep their symbols
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, int HALF>
+__global__ void __launch_bounds__(TPL * COLS, (PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_half_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twt) {
+  panelx_body<T, N, TPL, R0, R1, R2, COLS, INC, OUTC, SPLIT, false, false, HALF>(a, in, out, twt);
+}
+
 // ---------------------------------------------------------------------------
 // variant registry: every instantiation registers itself under (n, precision, flavour, id)
 // ---------------------------------------------------------------------------
@@ -1289,7 +1314,7 @@ struct Variant {
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
   bool conv = false;  // fft_conv_panel_k instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
-  int half = 0;       // fft_half_panel_k / fft_conv_half_panel_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
+  int half = 0;       // fft_half_panel_k / fft_half_panelx_k / fft_conv_half_panel_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
                       // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2)
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
@@ -1495,6 +1520,27 @@ void reg_variantx(int id, int defmask = -1) {
   }
 }
 
+// half-line instances of the mixed-radix kernel (fft_half_panelx_k, offt_reg_half_mixed_*.hip): the four forms of
+// reg_variant_half, one column per lane.  FLAV as there: a length whose full-line kernel has a narrow contiguous /
+// contiguous shape registers that shape for H_CC1 | H_CC2 and the wide one for H_CS1 | H_SC2.
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT, int FLAV = H_ALL>
+void reg_variantx_half() {
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  static_assert(Cfg::QUARTER, "half lines: N is a multiple of 4");
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  char nm[176];
+  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s half lines lds=%zuB", prec ? "f32" : "f64", N,
+           R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  auto add = [&](bool inc, bool outc, int half, const void *fn) {
+    registry().push_back(Variant{N, prec, inc, outc, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES, fn, nm, false, true, false, nullptr});
+    registry().back().half = half;
+  };
+  if constexpr ((FLAV & H_CS1) != 0) add(true, false, 1, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT, 1>);
+  if constexpr ((FLAV & H_CC1) != 0) add(true, true, 1, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT, 1>);
+  if constexpr ((FLAV & H_CC2) != 0) add(true, true, 2, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT, 2>);
+  if constexpr ((FLAV & H_SC2) != 0) add(false, true, 2, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, true, SPLIT, 2>);
+}
+
 // instantiation groups (offt_reg_*.hip)
 void reg_pow2_f64();
 void reg_pow2_f64_1024();
@@ -1517,6 +1563,8 @@ void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();
 void reg_half_real_f32();
+void reg_half_mixed_f64();
+void reg_half_mixed_f32();
 void reg_dev();
 
 }  // namespace offtk

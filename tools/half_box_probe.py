@@ -11,7 +11,10 @@ Real-input plans (r2c:): the half box stays on and OFFT_HIP_OPT_HALF_R2C is swit
 padding) and 0 (the library clears the padding of the real rows and runs the ordinary schedule: what a caller gets without
 the option).  The models are the same numbers of sweeps, over the half-spectrum volume Nx Ny (Nz/2+1) complex elements --
 the real field has as many bytes, its box is 1/8 of a sweep; the baseline makes 6 sweeps and its clear writes 7/8 of one.
-usage: half_box_probe.py [r2c:][f64|f32:]N ... [--runs R] [--out FILE]
+Mixed-radix lengths (mixed:): likewise the half box stays on and OFFT_HIP_OPT_HALF_MIXED is switched between 1 and 0.
+Their x pass has no fused convolve kernel: the convolve is the pruned forward, a multiply (the spectrum read and written,
+the filter read) and the pruned inverse, 2.625 + 2 + 2.625 = 7.25 sweeps plus the filter.
+usage: half_box_probe.py [r2c:|mixed:][f64|f32:]N ... [--runs R] [--out FILE]
        (default: 512 f32:512 1024 f32:1024 r2c:512 r2c:f32:512 r2c:1024 r2c:f32:1024)"""
 import os
 import statistics
@@ -49,6 +52,8 @@ def main():
         *kinds, n_s = spec.split(":")
         n = int(n_s)
         r2c = "r2c" in kinds
+        mixed = "mixed" in kinds
+        opt = r2c or mixed   # the baseline is the library's own fallback: the half box on, the route's option off
         prec = api.F32 if "f32" in kinds else api.F64
         td = torch.float32 if prec == api.F32 else torch.float64
         esz = 4 if prec == api.F32 else 8
@@ -73,7 +78,7 @@ def main():
             vol[:h, :h, h:].zero_()
 
         def fwd(on):
-            if not on and not r2c:
+            if not on and not opt:
                 clear()
             api.offt_3d_execute_dir(po, p, p, -1)
 
@@ -81,13 +86,15 @@ def main():
             api.offt_3d_execute_dir(po, p, p, +1)
 
         def conv(on):
-            if not on and not r2c:
+            if not on and not opt:
                 clear()
             api.offt_hip_execute_convolve(po, p, H.data_ptr(), api.FILTER_REAL)
 
         def route(on):
             if r2c:
                 assert L.offt_hip_set_option(po, api.OPT_HALF_R2C, 1 if on else 0) == 0
+            elif mixed:
+                assert L.offt_hip_set_option(po, api.OPT_HALF_MIXED, 1 if on else 0) == 0
             else:
                 api.offt_hip_set_half_box(po, on)
 
@@ -100,13 +107,13 @@ def main():
             return ev[0].elapsed_time(ev[1]) * 1e-3
 
         V = 2.0 * esz * float(n) ** 2 * (n // 2 + 1 if r2c else n)
-        models = {"forward": 2.625 * V, "inverse": 2.625 * V, "convolve": 3.25 * V + 0.5 * V}
         api.offt_hip_set_half_box(po, True)
         route(True)
         pruned = api.offt_hip_half_box_pruned(po)
         fused = api.offt_hip_convolve_fused(po)
-        tag = f"{'r2c ' if r2c else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3"
-        base = "option off: library clear + ordinary" if r2c else "clear + ordinary"
+        models = {"forward": 2.625 * V, "inverse": 2.625 * V, "convolve": (3.25 if fused else 7.25) * V + 0.5 * V}
+        tag = f"{'r2c ' if r2c else 'mixed ' if mixed else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3"
+        base = "option off: library clear + ordinary" if opt else "clear + ordinary"
         for name, fn in (("forward", fwd), ("inverse", inv), ("convolve", conv)):
             t = {True: [], False: []}
             for _ in range(3):
