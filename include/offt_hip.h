@@ -74,7 +74,9 @@ void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int directi
 #define OFFT_HIP_FILTER_REAL    0   /* one scalar of the plan's precision per spectrum element */
 #define OFFT_HIP_FILTER_COMPLEX 1   /* one complex value per spectrum element                  */
 int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *filter, int filter_kind);
-/* 1 if this plan's convolve runs the fused route (one launch for forward-pass . filter . inverse-pass), 0 otherwise */
+/* 1 if this plan's convolve runs the fused route (one launch for forward-pass . filter . inverse-pass), 0 otherwise: one
+ * rank, an x extent that is a power of two from 64 to 1024 or, with OFFT_HIP_OPT_CONV_MIXED, one of the mixed-radix lengths
+ * listed there */
 int offt_hip_convolve_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
@@ -124,6 +126,12 @@ int offt_hip_wait(struct _offt_plan *po);
                                           640, 768, 1000 in single precision, next to the powers of two from 64 to 1024; complex plans),
                                           0 (default) = always clear and run the ordinary schedule.  Set before or after
                                           offt_hip_set_half_box, like OFFT_HIP_OPT_HALF_R2C (OFFT_HALF_MIXED) */
+#define OFFT_HIP_OPT_CONV_MIXED 12     /* convolve on a plan whose x extent is no power of two: 1 = the fused route (one launch for the
+                                          forward's last pass, the filter and the inverse's first pass) where that extent has a fused
+                                          mixed-radix kernel (96, 192, 320, 384, 640, 768, 1000 points in double, 384, 640, 768, 1000 in
+                                          single precision; complex and r2c plans, one rank; with OFFT_HIP_OPT_HALF_MIXED also a pruned
+                                          half box), 0 (default) = forward, multiply, inverse.  Read by every convolve; the results
+                                          agree to rounding (OFFT_CONV_MIXED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -130,18 +130,31 @@ int offt_hipk_has_half(const offt_pass_desc *d);
 #define OFFT_FILTER_COMPLEX 1
 typedef struct offt_filter_desc {
   int kind;
+  /* 1 = a line length without a power-of-two fused kernel may run on the mixed-radix fused kernels (fft_conv_panelx_k,
+   * fft_conv_half_panelx_k: 96, 192, 320, 384, 640, 768, 1000 points in double and 384, 640, 768, 1000 in single precision),
+   * 0 = such a length has no fused kernel (plan option OFFT_HIP_OPT_CONV_MIXED) */
+  int mixed;
   long long axis_stride, col_stride, b1_stride, b2_stride;
 } offt_filter_desc;
+/* `mixed` took the four bytes of padding behind kind: the size and every older offset are what they were */
+#ifdef __cplusplus
+static_assert(sizeof(offt_filter_desc) == 40 && __builtin_offsetof(offt_filter_desc, axis_stride) == 8, "offt_filter_desc layout");
+#else
+_Static_assert(sizeof(offt_filter_desc) == 40 && __builtin_offsetof(offt_filter_desc, axis_stride) == 8, "offt_filter_desc layout");
+#endif
 /* One fused launch on the lines of `fwd` (the last pass of a forward transform): load through its in_* side, forward FFT,
  * times H read where the pass would store (f), inverse FFT (unnormalised), times fwd->scale, store through the same in_*
- * addressing -- in place on `data`.  fwd->out_keep: stores with the default cache policy.  -1 if no fused kernel exists. */
+ * addressing -- in place on `data`.  fwd->out_keep: stores with the default cache policy where the kernel has a
+ * cache-keeping twin (the power-of-two full-line kernels), ignored otherwise.  -1 if no fused kernel exists. */
 /* fwd->half: 0, or 3 = zero-padded half lines: only indices < n/2 of every line are loaded and only those are stored
  * (the filter is read over the full line); any other non-zero value has no fused kernel. */
 int offt_hipk_conv_pass(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, void *data, void *stream);
-/* 1 if offt_hipk_conv_pass has a fused kernel for (fwd, f): power-of-two lines of 64 ... 1024 points, contiguous lines
- * (in_contig, no split, complex input) and a unit-stride filter axis; the registry lookup needs no device */
+/* 1 if offt_hipk_conv_pass has a fused kernel for (fwd, f): power-of-two lines of 64 ... 1024 points or, with f->mixed,
+ * one of the mixed-radix lengths listed at offt_filter_desc::mixed; contiguous lines (in_contig, no split, complex input)
+ * and a unit-stride filter axis; the registry lookup needs no device */
 int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f);
-/* "fft_conv_panel_k", "fft_conv_half_panel_k" (fwd->half = 3), or "no fused kernel" (rocprof matching, tests) */
+/* "fft_conv_panel_k", "fft_conv_half_panel_k" (fwd->half = 3), with f->mixed at a mixed-radix length "fft_conv_panelx_k",
+ * "fft_conv_half_panelx_k" (fwd->half = 3), or "no fused kernel" (rocprof matching, tests) */
 const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f);
 /* data[i0 s0 + i1 s1 + i2 s2] *= H at the same element index, over the box n0 x n1 x n2 (complex elements, in place);
  * kind as offt_filter_desc::kind.  Non-temporal, 16 B per lane along the smallest stride. */

@@ -442,6 +442,8 @@ typedef struct hip_state {
     int half_r2c;        /* half box on a real-input plan: 1 = its passes may skip the padding (half_can_prune), 0 = always the fallback */
     int half_mixed;      /* half box with a length that is no power of two: 1 = its passes may skip the padding where every pass has a
                             half-line kernel (half_can_prune), 0 = always the fallback */
+    int conv_mixed;      /* convolve: 1 = the fused launch may run on the mixed-radix kernels (offt_filter_desc::mixed), 0 = a
+                            length that is no power of two takes the unfused route */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -1128,6 +1130,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.f32_pairs = !(getenv("OFFT_F32_PAIRS") && atoi(getenv("OFFT_F32_PAIRS")) == 0);
   st->opt.half_r2c = getenv("OFFT_HALF_R2C") && atoi(getenv("OFFT_HALF_R2C")) != 0;
   st->opt.half_mixed = getenv("OFFT_HALF_MIXED") && atoi(getenv("OFFT_HALF_MIXED")) != 0;
+  st->opt.conv_mixed = getenv("OFFT_CONV_MIXED") && atoi(getenv("OFFT_CONV_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
   st->opt.block_pad = getenv("OFFT_BLOCK_PAD") && atoi(getenv("OFFT_BLOCK_PAD")) != 0;
@@ -1602,6 +1605,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
       st->opt.half_mixed = value != 0;
       if (st->half_box) st->half_pruned = half_can_prune(po);
       break;
+    case OFFT_HIP_OPT_CONV_MIXED: st->opt.conv_mixed = value != 0; break; /* read by every convolve (conv_fused_route) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
@@ -1638,6 +1642,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_F32_PAIRS: return st->opt.f32_pairs;
     case OFFT_HIP_OPT_HALF_R2C: return st->opt.half_r2c;
     case OFFT_HIP_OPT_HALF_MIXED: return st->opt.half_mixed;
+    case OFFT_HIP_OPT_CONV_MIXED: return st->opt.conv_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
     case OFFT_HIP_OPT_P2P_TIMEOUT_S: return (long long)st->opt.p2p_timeout_s;
@@ -2939,6 +2944,7 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
   if (l->half) fd->half = 3; /* half box: the fused launch loads the lower half of every x line and stores only that */
   memset(fl, 0, sizeof *fl);
   fl->kind = kind;
+  fl->mixed = st->opt.conv_mixed; /* OFFT_HIP_OPT_CONV_MIXED: a length that is no power of two may have a fused kernel too */
   fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
   fl->b1_stride = l->out_b1_stride; fl->b2_stride = l->out_b2_stride;
   /* the inverse's first pass must store where the forward's last one loads, with the same addressing.  Where the inverse

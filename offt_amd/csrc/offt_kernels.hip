@@ -461,6 +461,8 @@ void build_registry() {
   reg_mixed_f32_b();
   reg_conv_f64();
   reg_conv_f32();
+  reg_conv_mixed_f64();
+  reg_conv_mixed_f32();
   reg_half_f64();
   reg_half_f32();
   reg_half_real_f64();
@@ -1782,7 +1784,8 @@ int offt_hipk_flag_wait(int n, unsigned long long *const *addr, unsigned long lo
 
 // ---- spectral convolution (offt_hipk.h) ----
 namespace {
-// the fused instance for (fwd, f), or nullptr: contiguous complex lines without a split, a unit-stride filter axis
+// the fused instance for (fwd, f), or nullptr: contiguous complex lines without a split, a unit-stride filter axis.  The
+// mixed-radix instances (fft_conv_panelx_k; lengths that have no power-of-two instance) only with f->mixed.
 Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep) {
   if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
   if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
@@ -1791,6 +1794,7 @@ Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep
   if (d->half && d->half != 3) return nullptr;  // half lines: loads and stores together, or not at all
   if (d->half && keep) return nullptr;          // (no cache-keeping twin)
   Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true, d->half);
+  if (v && v->mixed && !f->mixed) return nullptr;
   return v && v->conv && v->keep == keep && v->half == d->half ? v : nullptr;
 }
 }  // namespace
@@ -1798,7 +1802,10 @@ Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep
 int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false) != nullptr; }
 
 const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
-  return pick_conv(fwd, f, false) ? (fwd->half ? "fft_conv_half_panel_k" : "fft_conv_panel_k") : "no fused kernel";
+  const Variant *v = pick_conv(fwd, f, false);
+  if (!v) return "no fused kernel";
+  if (v->mixed) return fwd->half ? "fft_conv_half_panelx_k" : "fft_conv_panelx_k";
+  return fwd->half ? "fft_conv_half_panel_k" : "fft_conv_panel_k";
 }
 
 int offt_hipk_conv_pass(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream) {

@@ -1293,6 +1293,260 @@ fft_half_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>
   panelx_body<T, N, TPL, R0, R1, R2, COLS, INC, OUTC, SPLIT, false, false, HALF>(a, in, out, twt);
 }
 
+// Spectral convolution of whole lines of a mixed-radix length (offt_hipk_conv_pass with offt_filter_desc::mixed): to
+// panelx_body what conv_body is to panel_body.  Contiguous lines only -- line offset j = tid % TPL and column c = tid / TPL in
+// every stage, no split, complex data, in place through the load side.  A thread owns ceil((N/R)/TPL) butterflies of a
+// stage, the last one predicated when TPL does not divide N/R: the filter loads, the round trip and the stores carry the
+// live predicates of the exchanges, and a butterfly that is off holds zeros throughout.
+//   HALF (fft_conv_half_panelx_k, offt_pass_desc::half = 3): the lines are zero above N/2 going in and only their lower
+//        half is wanted coming out; a load index q + t N/R0 is in the upper half exactly when 2t >= R0 and a store index
+//        q + t N/RL exactly when 2t >= RL (see panelx_body), so neither is compiled.  The filter and everything between the
+//        two is the full line.
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT, bool HALF = false>
+__device__ __forceinline__ void convx_body(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter,
+                                           const typename vec2<T>::type *twt) {
+  using V2 = typename vec2<T>::type;
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int NT = Cfg::NT, NSTAGE = Cfg::NSTAGE, LSTRIDE = Cfg::LSTRIDE, EMAX = Cfg::EMAX;
+  constexpr int PADDIV = Cfg::PADDIV;
+  static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
+  static_assert(smooth235(R0) && smooth235(R1) && smooth235(R2), "radices must be products of primes <= 13, or primes <= 31");
+  static_assert(R0 <= 32 && R1 <= 32 && R2 <= 32, "register radix <= 32");
+  static_assert(NSTAGE > 1, "the round trip goes through the exchange image");
+  static_assert(Cfg::QUARTER, "quarter-wave twiddle table: N is a multiple of 4");
+  constexpr int RL = NSTAGE == 3 ? R2 : R1;  // radix of the last stage
+  static_assert(!HALF || (R0 % 2 == 0 && RL % 2 == 0), "half lines: first and last radix even");
+  constexpr int NBF0 = N / R0, NB0 = cdiv(NBF0, TPL);  // butterflies per line / per thread, first stage
+  constexpr int NBFL = N / RL, NBL = cdiv(NBFL, TPL);  // ... last stage
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T *exs = reinterpret_cast<T *>(smem);
+  V2 *exv = reinterpret_cast<V2 *>(smem);
+  V2 *tw = reinterpret_cast<V2 *>(smem + Cfg::TW_OFF);
+
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Cfg::QT; i += NT) tw[i] = twt[i];  // (visible after the first exchange's barrier)
+  auto pad = [](int i) {
+    if constexpr (Cfg::SWZ) return i ^ ((i / R0) & 15);
+    else if constexpr (PADDIV > 0) return i + i / PADDIV;
+    else return i;
+  };
+
+  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const int cp = bid % (unsigned)a.ncp;
+  const unsigned rest = bid / (unsigned)a.ncp;
+  const int b1 = rest % (unsigned)a.nb1;
+  const int b2 = rest / (unsigned)a.nb1;
+  const int c0 = cp * COLS;
+  const int j = tid % TPL, c = tid / TPL;
+  const bool valid = (c0 + c) < a.ncols;
+  V2 *line = data + (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col;
+  const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col;
+  // butterfly u of a stage with NBF butterflies per line is live for this thread (compile-time true but for the last one)
+  auto live0 = [&](int u) { return (u + 1) * TPL <= NBF0 || j + u * TPL < NBF0; };
+  auto liveL = [&](int u) { return (u + 1) * TPL <= NBFL || j + u * TPL < NBFL; };
+  auto at = [&](int i) { return c * LSTRIDE + pad(i); };
+
+  cx<T> v[EMAX];
+
+  static_for<0, NB0 * R0>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+    if constexpr (HALF && 2 * t >= R0) {
+      v[decltype(ii)::value] = cx<T>{T{}, T{}};  // the padding: a literal zero (and the first butterfly knows it)
+      return;
+    }
+    const int n = j + u * TPL + t * NBF0;
+    V2 val;
+    val.x = 0; val.y = 0;
+    if (valid && live0(u)) val = gload(line + (long long)n * a.in_axis);
+    v[decltype(ii)::value] = cx<T>{val.x, val.y};
+  });
+
+  // the forward stages of panelx_body (contiguous / contiguous), ending in the last stage's register order:
+  // v[u RL + perm_mixed(RL, t)] holds line index j + u TPL + t N/RL
+  auto stages = [&](auto upper_zero) {
+    static_for<0, NSTAGE>([&](auto sidx) {
+      constexpr int s = decltype(sidx)::value;
+      constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
+      constexpr int Ns = (s == 0) ? 1 : ((s == 1) ? R0 : R0 * R1);
+      constexpr int NBF = N / R;
+      constexpr int NB = cdiv(NBF, TPL);
+      if constexpr (s > 0) {
+        constexpr int M = N / (Ns * R);
+        static_for<0, NB>([&](auto uu) {
+          constexpr int u = decltype(uu)::value;
+          const int q = j + u * TPL;
+          const int km = (q % Ns) * M;
+          static_for<1, R>([&](auto tt) {
+            constexpr int t = decltype(tt)::value;
+            const int e = km * t;            // <= (Ns-1)(R-1)M < N, also for a predicated-off butterfly
+            const int qd = e / (N / 4);
+            const V2 w = tw[e - qd * (N / 4)];
+            T cr = (qd & 1) ? w.y : w.x;     // times (-i)^qd
+            T ci = (qd & 1) ? -w.x : w.y;
+            if (qd & 2) { cr = -cr; ci = -ci; }
+            const cx<T> x = v[u * R + t];
+            v[u * R + t] = cx<T>{x.x * cr - x.y * ci, x.x * ci + x.y * cr};
+          });
+        });
+      }
+      static_for<0, NB>([&](auto uu) { dft_mixed<T, R, s == 0 && decltype(upper_zero)::value>(&v[decltype(uu)::value * R]); });
+      if constexpr (s < NSTAGE - 1) {
+        constexpr int Rn = (s == 0) ? R1 : R2;
+        constexpr int NBFn = N / Rn, NBn = cdiv(NBFn, TPL);
+        auto wr_idx = [&](int u, int t) {
+          const int q = j + u * TPL;
+          const int k = q % Ns;
+          return at((q - k) * R + k + t * Ns);
+        };
+        auto wr_live = [&](int u) { return (u + 1) * TPL <= NBF || j + u * TPL < NBF; };
+        auto rd_idx = [&](int u, int t) { return at(j + u * TPL + t * NBFn); };
+        auto rd_live = [&](int u) { return (u + 1) * TPL <= NBFn || j + u * TPL < NBFn; };
+        if constexpr (s > 0) __syncthreads();  // previous exchange's reads done
+        if constexpr (SPLIT) {
+          static_for<0, NB * R>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            constexpr int src = u * R + perm_mixed(R, t);
+            if (wr_live(u)) exs[wr_idx(u, t)] = v[src].x;
+          });
+          __syncthreads();
+          T re[NBn * Rn];
+          static_for<0, NBn * Rn>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            re[decltype(ii)::value] = rd_live(u) ? exs[rd_idx(u, t)] : (T)0;
+          });
+          __syncthreads();
+          static_for<0, NB * R>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            constexpr int src = u * R + perm_mixed(R, t);
+            if (wr_live(u)) exs[wr_idx(u, t)] = v[src].y;
+          });
+          __syncthreads();
+          static_for<0, NBn * Rn>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], rd_live(u) ? exs[rd_idx(u, t)] : (T)0};
+          });
+        } else {
+          static_for<0, NB * R>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            constexpr int src = u * R + perm_mixed(R, t);
+            const cx<T> x = v[src];
+            V2 w; w.x = x.x; w.y = x.y;
+            if (wr_live(u)) exv[wr_idx(u, t)] = w;
+          });
+          __syncthreads();
+          static_for<0, NBn * Rn>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            V2 w; w.x = 0; w.y = 0;
+            if (rd_live(u)) w = exv[rd_idx(u, t)];
+            v[decltype(ii)::value] = cx<T>{w.x, w.y};
+          });
+        }
+      }
+    });
+  };
+
+  stages(std::integral_constant<bool, HALF>{});
+
+  // times H[n], then conjugated (the inverse as conj(F(conj(.)))); filter values are read once: non-temporal
+  auto filt = [&](auto complex_filter) {
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int r = u * RL + perm_mixed(RL, t);
+      const int n = j + u * TPL + t * NBFL;
+      const long long off = fb + (long long)n * f.axis;
+      const bool on = valid && liveL(u);
+      const cx<T> x = v[r];
+      if constexpr (decltype(complex_filter)::value) {
+        V2 h;
+        h.x = 0; h.y = 0;
+        if (on) h = gload(reinterpret_cast<const V2 *>(filter) + off);
+        v[r] = cx<T>{x.x * h.x - x.y * h.y, -(x.x * h.y + x.y * h.x)};
+      } else {
+        T h = 0;
+        if (on) h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + off);
+        v[r] = cx<T>{x.x * h, -(x.y * h)};
+      }
+    });
+  };
+  if (f.cplx) filt(std::true_type{});
+  else filt(std::false_type{});
+
+  // round trip through the exchange image: from the last stage's order back into the load distribution
+  __syncthreads();  // the last exchange's reads done
+  if constexpr (SPLIT) {
+    T re[NB0 * R0];
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int src = u * RL + perm_mixed(RL, t);
+      if (liveL(u)) exs[at(j + u * TPL + t * NBFL)] = v[src].x;
+    });
+    __syncthreads();
+    static_for<0, NB0 * R0>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      re[decltype(ii)::value] = live0(u) ? exs[at(j + u * TPL + t * NBF0)] : (T)0;
+    });
+    __syncthreads();
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int src = u * RL + perm_mixed(RL, t);
+      if (liveL(u)) exs[at(j + u * TPL + t * NBFL)] = v[src].y;
+    });
+    __syncthreads();
+    static_for<0, NB0 * R0>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], live0(u) ? exs[at(j + u * TPL + t * NBF0)] : (T)0};
+    });
+  } else {
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int src = u * RL + perm_mixed(RL, t);
+      const cx<T> x = v[src];
+      V2 w; w.x = x.x; w.y = x.y;
+      if (liveL(u)) exv[at(j + u * TPL + t * NBFL)] = w;
+    });
+    __syncthreads();
+    static_for<0, NB0 * R0>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      V2 w; w.x = 0; w.y = 0;
+      if (live0(u)) w = exv[at(j + u * TPL + t * NBF0)];
+      v[decltype(ii)::value] = cx<T>{w.x, w.y};
+    });
+  }
+  __syncthreads();  // the round trip's reads done before the first exchange of the second half writes
+
+  stages(std::false_type{});
+
+  const T sc = (T)a.scale;
+  static_for<0, NBL * RL>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+    if constexpr (HALF && 2 * t >= RL) return;  // the upper half of the output is not wanted
+    const int n = j + u * TPL + t * NBFL;
+    constexpr int src = u * RL + perm_mixed(RL, t);
+    const cx<T> x = v[src];
+    V2 w;
+    w.x = x.x * sc;
+    w.y = -x.y * sc;
+    if (valid && liveL(u)) gstore(line + (long long)n * a.in_axis, w);
+  });
+}
+
+// (at most 2 waves per SIMD, the rule of conv_wps: the filter values and the second half's live ranges cost registers)
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+constexpr int convx_wps() { return PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E < 2 ? PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E : 2; }
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_panelx_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twt) {
+  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT>(a, f, data, filter, twt);
+}
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_half_panelx_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twt) {
+  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, data, filter, twt);
+}
+
 // ---------------------------------------------------------------------------
 // variant registry: every instantiation registers itself under (n, precision, flavour, id)
 // ---------------------------------------------------------------------------
@@ -1313,8 +1567,8 @@ struct Variant {
   bool keep = false;  // KEEP instantiation (offt_pass_desc::out_keep): default-policy stores
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
-  bool conv = false;  // fft_conv_panel_k instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
-  int half = 0;       // fft_half_panel_k / fft_half_panelx_k / fft_conv_half_panel_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
+  bool conv = false;  // fft_conv_panel_k / fft_conv_panelx_k (mixed) instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
+  int half = 0;       // fft_half_panel_k / fft_half_panelx_k / fft_conv_half_panel_k / fft_conv_half_panelx_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
                       // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2)
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
@@ -1541,6 +1795,34 @@ void reg_variantx_half() {
   if constexpr ((FLAV & H_SC2) != 0) add(false, true, 2, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, true, SPLIT, 2>);
 }
 
+// fused convolution instances of the mixed-radix kernel (fft_conv_panelx_k, offt_reg_conv_mixed_*.hip; picked only with
+// offt_filter_desc::mixed): contiguous lines, no cache-keeping twin ...
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variantx_conv() {
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  char nm[176];
+  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s convolution lds=%zuB", prec ? "f32" : "f64", N,
+           R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
+                               (const void *)fft_conv_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
+  registry().back().conv = true;
+}
+
+// ... and on half lines (fft_conv_half_panelx_k): the same shapes
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variantx_conv_half() {
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  char nm[176];
+  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s convolution on half lines lds=%zuB",
+           prec ? "f32" : "f64", N, R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
+                               (const void *)fft_conv_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
+  registry().back().conv = true;
+  registry().back().half = 3;
+}
+
 // instantiation groups (offt_reg_*.hip)
 void reg_pow2_f64();
 void reg_pow2_f64_1024();
@@ -1559,6 +1841,8 @@ void reg_mixed_f32_a();
 void reg_mixed_f32_b();
 void reg_conv_f64();
 void reg_conv_f32();
+void reg_conv_mixed_f64();
+void reg_conv_mixed_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();

@@ -7,7 +7,12 @@ process.  After a warm-up the three ALTERNATE, so that all see the same box stat
 against the byte model for complex data with a real filter, per point: (a) 6 x 2 esz x 2 (every pass reads and writes the
 volume), (b) (a) + 2 x 2 esz + esz (multiply sweep: read, filter, write), (c) 4 x 2 esz x 2 + 2 x 2 esz + esz (r2c: the
 same counts on the half spectrum for the y / x / fused passes, the z passes on the real rows).
-usage: conv_probe.py [f64|f32|r2c:]N ... [--zgroup-mib M]   (default: 1024 f32:1024 r2c:512)"""
+A spec with the prefix mixed: measures OFFT_HIP_OPT_CONV_MIXED instead (x lengths that are no powers of two): the plan's
+convolve with the option at 1 and at 0 ALTERNATES after a warm-up, MIXED_REPS times each (default 20), and the line
+reports min and median of both, their ratios, the option-off route's own spread (median / min - 1) and the byte model
+(c) / (b).  mixed:half:N does so on a pruned half-box plan (OFFT_HIP_OPT_HALF_MIXED, an N/2 box).
+usage: conv_probe.py [mixed:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+       (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768)"""
 import ctypes as C
 import os
 import sys
@@ -20,6 +25,7 @@ from offt_amd import api  # noqa: E402
 
 L = api.lib()
 REPS = int(os.environ.get("CONV_PROBE_REPS", "5"))
+MIXED_REPS = int(os.environ.get("CONV_PROBE_MIXED_REPS", "20"))
 OPT_ZGROUP_MIB = 0  # include/offt_hip.h
 
 
@@ -45,10 +51,12 @@ def main():
         i = args.index("--zgroup-mib")
         zg = int(args[i + 1])
         del args[i:i + 2]
-    specs = args or ["1024", "f32:1024", "r2c:512"]
+    specs = args or ["1024", "f32:1024", "r2c:512", "mixed:768", "mixed:f32:768", "mixed:1000", "mixed:f32:1000", "mixed:half:768"]
     torch.cuda.set_device(0)
     for spec in specs:
-        kind, _, n_s = spec.rpartition(":")
+        mixed = spec.startswith("mixed:")
+        half = mixed and spec[6:].startswith("half:")
+        kind, _, n_s = spec[(6 if mixed else 0) + (5 if half else 0):].rpartition(":")
         n = int(n_s)
         prec = api.F32 if kind == "f32" else api.F64
         r2c = kind == "r2c"
@@ -89,6 +97,33 @@ def main():
         def cv():
             api.offt_hip_execute_convolve(po, dev.data_ptr(), H.data_ptr(), api.FILTER_REAL)
 
+        if mixed:
+            # the same plan and buffers, the option alternating between 1 and 0 (set outside the timed region)
+            if half:
+                L.offt_hip_set_option(po, api.OPT_HALF_MIXED, 1)
+                api.offt_hip_set_half_box(po, True)
+            t = {1: [], 0: []}
+            fused = {}
+            for rep_i in range(2 + MIXED_REPS):
+                for on in (1, 0):
+                    L.offt_hip_set_option(po, api.OPT_CONV_MIXED, on)
+                    fused[on] = api.offt_hip_convolve_fused(po)
+                    dt = run(cv)
+                    if rep_i >= 2:
+                        t[on].append(dt)
+            _, mb, mc = model(n, esz, r2c)
+            mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+            tag = f"{'r2c f64' if r2c else ('f32' if prec == api.F32 else 'f64')} {n}^3"
+            if half:
+                tag += f" half box {n // 2}^3 [{'pruned' if api.offt_hip_half_box_pruned(po) else 'fallback'}]"
+            print(f"mixed: {tag}: option 1 [{'fused' if fused[1] else 'unfused'}] min {mn[1] * 1e3:.3f} ms median {md[1] * 1e3:.3f} ms  "
+                  f"option 0 [{'fused' if fused[0] else 'unfused'}] min {mn[0] * 1e3:.3f} ms median {md[0] * 1e3:.3f} ms  "
+                  f"1/0 min {mn[1] / mn[0]:.3f} median {md[1] / md[0]:.3f}  option-0 spread {md[0] / mn[0] - 1:.3f}  "
+                  f"byte model (full lines) {mc / mb:.3f}  n {MIXED_REPS}", flush=True)
+            api.offt_3d_fin(po)
+            del dev, H, spec_v, hv
+            torch.cuda.empty_cache()
+            continue
         for _ in range(2):
             a(); b(); cv()
         best = [1e30, 1e30, 1e30]
