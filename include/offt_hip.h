@@ -88,7 +88,8 @@ int offt_hip_convolve_fused(const struct _offt_plan *po);
  *   undefined, as after any c2r inverse).  Such a plan clears the padding and runs the ordinary schedule unless
  *   OFFT_HIP_OPT_HALF_R2C is set: then its passes skip the padding like a complex plan's.
  * Extents that are no powers of two: such a plan clears the padding and runs the ordinary schedule unless
- *   OFFT_HIP_OPT_HALF_MIXED is set and every extent has a half-line kernel (complex plans only).
+ *   OFFT_HIP_OPT_HALF_MIXED is set and every extent has a half-line kernel.  A real-input plan with such an extent needs
+ *   OFFT_HIP_OPT_HALF_R2C, OFFT_HIP_OPT_HALF_MIXED and OFFT_HIP_OPT_HALF_R2C_MIXED, all three.
  * -1 (plan unchanged, text in offt_hip_last_error) if an extent is odd.  Collective on several ranks. */
 int offt_hip_set_half_box(struct _offt_plan *po, int on);
 /* 1: every pass of this plan skips the padding (half-line kernels); 0: the library clears the padding and runs the
@@ -123,7 +124,8 @@ int offt_hip_wait(struct _offt_plan *po);
                                           after offt_hip_set_half_box: a half box that is on changes route at once (OFFT_HALF_R2C) */
 #define OFFT_HIP_OPT_HALF_MIXED 11     /* half box on a plan with an extent that is no power of two: 1 = its passes skip the padding where
                                           every pass has a half-line kernel (96, 192, 320, 384, 640, 768, 1000 points in double, 384,
-                                          640, 768, 1000 in single precision, next to the powers of two from 64 to 1024; complex plans),
+                                          640, 768, 1000 in single precision, next to the powers of two from 64 to 1024; complex plans -- real-input
+                                          ones need OFFT_HIP_OPT_HALF_R2C_MIXED as well),
                                           0 (default) = always clear and run the ordinary schedule.  Set before or after
                                           offt_hip_set_half_box, like OFFT_HIP_OPT_HALF_R2C (OFFT_HALF_MIXED) */
 #define OFFT_HIP_OPT_CONV_MIXED 12     /* convolve on a plan whose x extent is no power of two: 1 = the fused route (one launch for the
@@ -132,6 +134,12 @@ int offt_hip_wait(struct _offt_plan *po);
                                           single precision; complex and r2c plans, one rank; with OFFT_HIP_OPT_HALF_MIXED also a pruned
                                           half box), 0 (default) = forward, multiply, inverse.  Read by every convolve; the results
                                           agree to rounding (OFFT_CONV_MIXED) */
+#define OFFT_HIP_OPT_HALF_R2C_MIXED 13 /* half box on a real-input (r2c) plan with an extent that is no power of two: 1 = together with
+                                          OFFT_HIP_OPT_HALF_R2C and OFFT_HIP_OPT_HALF_MIXED (all three set) its passes skip the padding
+                                          where every pass has a half-line kernel -- the lengths listed at OFFT_HIP_OPT_HALF_MIXED, real
+                                          rows included; 0 (default) = such a plan always clears and runs the ordinary schedule, whatever
+                                          the other two say.  Neither of those changes its meaning.  Set before or after
+                                          offt_hip_set_half_box, like them (OFFT_HALF_R2C_MIXED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -71,10 +71,13 @@ typedef struct offt_pass_desc {
    * output indices < n/2 are stored, the others are not written.  Kernels: power-of-two lines of 64 ... 1024 points
    * (fft_half_panel_k) and the mixed-radix lengths 96, 192, 320, 384, 640, 768, 1000 in double and 384, 640, 768, 1000 in
    * single precision (fft_half_panelx_k), complex, no split, in the four flavours of offt_hipk_has_half; a pass that asks
-   * for a bit no kernel implements fails, it never runs the full line.  Together with real_input, two forms, at the
-   * power-of-two lengths only: real_input = 1 with bit 1 (the reals n >= n/2 of a row are zero and not read; contiguous
-   * in, strided out) and real_input = 2 with bit 2 (the reals n >= n/2 of a row are not written; strided in, contiguous
-   * out).  (The field sits in what used to be alignment padding: no
+   * for a bit no kernel implements fails, it never runs the full line.  Together with real_input, two forms: real_input = 1
+   * with bit 1 (the reals n >= n/2 of a row are zero and not read; contiguous in, strided out) and real_input = 2 with bit
+   * 2 (the reals n >= n/2 of a row are not written; strided in, contiguous out).  Bit 4 (value 4) is a permission on these
+   * two forms and nothing else: "real rows may run on a mixed-radix half-line kernel" (fft_half_r2c_panelx_k,
+   * fft_half_c2r_panelx_k, the mixed-radix lengths above).  Without it a real row has a kernel at the power-of-two lengths
+   * only; with it a power-of-two length resolves to the same kernel as without it.  Bits 1 and 2 keep their meaning; bit 4 on
+   * a complex descriptor, or alone (half = 4), has no kernel.  (The field sits in what used to be alignment padding: no
    * other offset moves.) */
   int half;
   /* first sub-pass of a four-step line (set by the launcher itself, offt_kernels.hip): multiply output index k1 of column
@@ -119,9 +122,10 @@ const char *offt_hipk_kernel_name(const offt_pass_desc *d);
 /* 1 if a half-line kernel exists for the descriptor (d->half = 1 or 2): power-of-two lines of 64 ... 1024 points or one of
  * the mixed-radix lengths listed at offt_pass_desc::half (offt_hipk_kernel_name: "fft_half_panelx_k"), complex,
  * no split, no four-step twiddles, and one of the flavours contiguous-in / strided-out with bit 1, contiguous / contiguous
- * with bit 1 or bit 2, strided-in / contiguous-out with bit 2.  Real rows, power-of-two lengths only: real_input = 1 with
- * bit 1 on contiguous-in / strided-out and real_input = 2 with bit 2 on strided-in / contiguous-out, nothing else.  A registry lookup: needs no
- * device. */
+ * with bit 1 or bit 2, strided-in / contiguous-out with bit 2.  Real rows: real_input = 1 with bit 1 on contiguous-in /
+ * strided-out and real_input = 2 with bit 2 on strided-in / contiguous-out, nothing else -- at the power-of-two lengths,
+ * and with bit 4 of d->half set also at the mixed-radix ones ("fft_half_r2c_panelx_k", "fft_half_c2r_panelx_k"); bit 4
+ * anywhere else: 0.  A registry lookup: needs no device. */
 int offt_hipk_has_half(const offt_pass_desc *d);
 /* ---- spectral convolution (offt_hip_execute_convolve) ------------------------------------------------------------------
  * A filter H laid out like a forward pass's OUTPUT: kind 0 = one real scalar of the pass's precision per complex slot

@@ -442,6 +442,8 @@ typedef struct hip_state {
     int half_r2c;        /* half box on a real-input plan: 1 = its passes may skip the padding (half_can_prune), 0 = always the fallback */
     int half_mixed;      /* half box with a length that is no power of two: 1 = its passes may skip the padding where every pass has a
                             half-line kernel (half_can_prune), 0 = always the fallback */
+    int half_r2c_mixed;  /* half box on a real-input plan with a length that is no power of two: 1 = together with the two options above
+                            its passes may skip the padding (half_can_prune), and a mixed-radix Nz puts bit 4 on the real z passes */
     int conv_mixed;      /* convolve: 1 = the fused launch may run on the mixed-radix kernels (offt_filter_desc::mixed), 0 = a
                             length that is no power of two takes the unfused route */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
@@ -1130,6 +1132,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.f32_pairs = !(getenv("OFFT_F32_PAIRS") && atoi(getenv("OFFT_F32_PAIRS")) == 0);
   st->opt.half_r2c = getenv("OFFT_HALF_R2C") && atoi(getenv("OFFT_HALF_R2C")) != 0;
   st->opt.half_mixed = getenv("OFFT_HALF_MIXED") && atoi(getenv("OFFT_HALF_MIXED")) != 0;
+  st->opt.half_r2c_mixed = getenv("OFFT_HALF_R2C_MIXED") && atoi(getenv("OFFT_HALF_R2C_MIXED")) != 0;
   st->opt.conv_mixed = getenv("OFFT_CONV_MIXED") && atoi(getenv("OFFT_CONV_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
@@ -1605,6 +1608,10 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
       st->opt.half_mixed = value != 0;
       if (st->half_box) st->half_pruned = half_can_prune(po);
       break;
+    case OFFT_HIP_OPT_HALF_R2C_MIXED: /* likewise */
+      st->opt.half_r2c_mixed = value != 0;
+      if (st->half_box) st->half_pruned = half_can_prune(po);
+      break;
     case OFFT_HIP_OPT_CONV_MIXED: st->opt.conv_mixed = value != 0; break; /* read by every convolve (conv_fused_route) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
@@ -1642,6 +1649,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_F32_PAIRS: return st->opt.f32_pairs;
     case OFFT_HIP_OPT_HALF_R2C: return st->opt.half_r2c;
     case OFFT_HIP_OPT_HALF_MIXED: return st->opt.half_mixed;
+    case OFFT_HIP_OPT_HALF_R2C_MIXED: return st->opt.half_r2c_mixed;
     case OFFT_HIP_OPT_CONV_MIXED: return st->opt.conv_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
@@ -1697,8 +1705,9 @@ typedef struct single_sched {
 } single_sched;
 
 /* a pass descriptor turned into its mirror image: input and output sides exchanged, the sign of the exponent flipped, the
- * real-input pass become the real-output one, a half line that is not loaded become one that is not stored.  `scale` and
- * `out_keep` stay as they are: the callers set them, each by its own rule. */
+ * real-input pass become the real-output one, a half line that is not loaded become one that is not stored (bit 4 of `half`,
+ * the permission for the mixed-radix real-row kernels, goes along unchanged).  `scale` and `out_keep` stay as they are: the
+ * callers set them, each by its own rule. */
 static void desc_mirror(offt_pass_desc *d) {
   const offt_pass_desc f = *d;
   d->direction = +1;
@@ -1709,7 +1718,7 @@ static void desc_mirror(offt_pass_desc *d) {
   d->in_block_tab = f.out_block_tab; d->out_block_tab = f.in_block_tab;
   d->in_contig = f.out_contig; d->out_contig = f.in_contig;
   if (f.real_input == 1) d->real_input = 2; /* real input -> real output: the complex-to-real inverse's z pass */
-  d->half = ((f.half & 1) << 1) | ((f.half >> 1) & 1);
+  d->half = ((f.half & 1) << 1) | ((f.half >> 1) & 1) | (f.half & 4);
 }
 
 static void single_schedule(struct _offt_plan *po, void *data, int dir, single_sched *ss) {
@@ -1824,6 +1833,9 @@ static void single_schedule(struct _offt_plan *po, void *data, int dir, single_s
       d[0].ncols = Ny / 2; d[0].nb1 = Nx / 2;
       d[1].ncols = Nx / 2;
       d[0].half = d[1].half = d[2].half = 1;
+      /* a real-input plan whose z length is no power of two (OFFT_HIP_OPT_HALF_R2C_MIXED): P1 asks for the mixed-radix real-row
+       * kernel with bit 4, and so does its mirror image.  No other descriptor changes: a power-of-two Nz sends what it sent before */
+      if (po->is_r2c && st->opt.half_r2c_mixed && (Nzf & (Nzf - 1))) d[0].half |= 4;
     }
   } else if (st->work2) {
     /* y-z-x output (is_equalxy) as a variation of the z-y-x schedule: the same two rotations, the second one into a second
@@ -2799,14 +2811,16 @@ static int wait_compute(hip_state *st) {
  * as the HIP one, and has to interpret offt_pass_desc::half).  A real-input plan only with OFFT_HIP_OPT_HALF_R2C set:
  * its two z passes are then the real-input pass with half = 1 and the real-output pass with half = 2.  A plan with a
  * length that is no power of two only with OFFT_HIP_OPT_HALF_MIXED set: the six descriptors are asked about then as for
- * any other plan.  The mixed-radix lengths have complex half-line kernels only: a real-input plan with such a length
- * falls back whatever the two options say (also where only its x or y extent is one: that chain has not been run). */
+ * any other plan.  A real-input plan with such a length only with OFFT_HIP_OPT_HALF_R2C_MIXED set as well, all three
+ * together: each of the two older options keeps the meaning it had, and without the third such a plan falls back whatever
+ * they say (also where only its x or y extent is mixed).  With it, a mixed-radix Nz runs its real z passes on the
+ * mixed-radix real-row kernels (bit 4 of offt_pass_desc::half, set by single_schedule). */
 static int half_can_prune(struct _offt_plan *po) {
   hip_state *st = (hip_state *)po->hip_state;
   if (st->use_pipeline || (po->is_r2c && !st->opt.half_r2c)) return 0;
   const int N[3] = {po->Nx, po->Ny, po->Nz};
   for (int i = 0; i < 3; i++)
-    if ((!st->opt.half_mixed || po->is_r2c) && (N[i] & (N[i] - 1))) return 0;
+    if ((!st->opt.half_mixed || (po->is_r2c && !st->opt.half_r2c_mixed)) && (N[i] & (N[i] - 1))) return 0;
   single_sched fw, iv;
   const int was = st->half_pruned;
   st->half_pruned = 1;

@@ -469,6 +469,8 @@ void build_registry() {
   reg_half_real_f32();
   reg_half_mixed_f64();
   reg_half_mixed_f32();
+  reg_half_real_mixed_f64();
+  reg_half_real_mixed_f32();
   reg_bluestein_all();
 #endif
 }
@@ -950,8 +952,8 @@ Variant *pick_variant(const offt_pass_desc *d, bool allow_pair = true) {
 }
 
 // Zero-padded half lines (offt_pass_desc::half = 1 or 2): the fft_half_panel_k instance (a power of two from 64 to 1024
-// points) or the fft_half_panelx_k instance (the mixed-radix lengths of offt_reg_half_mixed_*.hip, one column per lane,
-// complex lines only) that takes the descriptor, or
+// points) or the fft_half_panelx_k instance (the mixed-radix lengths of offt_reg_half_mixed_*.hip, one column per lane)
+// that takes the descriptor, or
 // nullptr -- there is no other route for such a pass.  Complex lines without a split or four-step twiddles, in the forms
 // the z-y-x half-box schedule and its mirror launch: bit 1 on a contiguous load side, bit 2 on a contiguous store side,
 // never strided on both sides.  Single precision: the column-pair instance where the descriptor is eligible (pair_ok)
@@ -959,25 +961,31 @@ Variant *pick_variant(const offt_pass_desc *d, bool allow_pair = true) {
 // Real rows, the two ends of that schedule on a real-input plan, in exactly two forms: the real-input pass with bit 1,
 // contiguous in / strided out (fft_half_r2c_panel_k), and the real-output pass with bit 2, strided in / contiguous out
 // (fft_half_c2r_panel_k), with the restrictions the full-line real passes have (pick_variant0).  Every other real form: none.
+// Bit 4 of offt_pass_desc::half is a permission, not a form: the two real forms at a mixed-radix length
+// (fft_half_r2c_panelx_k, fft_half_c2r_panelx_k) are handed out only to a descriptor that carries it.  A power-of-two real
+// row resolves with it as without it; on a complex descriptor, or without bit 1 or 2, it has no kernel.
 Variant *pick_half(const offt_pass_desc *d, bool allow_pair = true) {
-  if (!d || (d->half != 1 && d->half != 2) || d->n < 2 || (d->n & 1)) return nullptr;
+  if (!d || (d->half & ~7) || d->n < 2 || (d->n & 1)) return nullptr;
+  const int half = d->half & 3;
+  const bool real_mixed = (d->half & 4) != 0;
+  if ((half != 1 && half != 2) || (real_mixed && !d->real_input)) return nullptr;
   if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
   if (d->tw4 || d->in_split || d->in_split_nfloor || d->out_split || d->out_split_nfloor) return nullptr;
   const bool inc = d->in_contig != 0, outc = d->out_contig != 0;
   if (d->real_input) {
-    const bool r2c = d->real_input == 1 && d->half == 1 && inc && !outc && d->in_axis_stride == 1 && d->direction <= 0;
-    const bool c2r = d->real_input == 2 && d->half == 2 && !inc && outc && d->out_axis_stride == 1;
+    const bool r2c = d->real_input == 1 && half == 1 && inc && !outc && d->in_axis_stride == 1 && d->direction <= 0;
+    const bool c2r = d->real_input == 2 && half == 2 && !inc && outc && d->out_axis_stride == 1;
     if (!r2c && !c2r) return nullptr;
-    Variant *v = find_variant(d->n, d->precision, inc, outc, -1, r2c, false, false, c2r, false, d->half);
-    return v && v->half == d->half && v->r2c == r2c && v->c2r == c2r ? v : nullptr;
+    Variant *v = find_variant(d->n, d->precision, inc, outc, -1, r2c, false, false, c2r, false, half);
+    return v && v->half == half && v->r2c == r2c && v->c2r == c2r && (!v->mixed || real_mixed) ? v : nullptr;
   }
-  if (d->half == 1 ? !inc : !outc) return nullptr;
+  if (half == 1 ? !inc : !outc) return nullptr;
   if (allow_pair && env().f32_pairs && !d->no_pairs && pair_ok(d)) {
-    Variant *p = find_variant(d->n, OFFT_PREC_F32_PAIR, inc, outc, -1, false, false, false, false, false, d->half);
-    if (p && p->half == d->half) return p;
+    Variant *p = find_variant(d->n, OFFT_PREC_F32_PAIR, inc, outc, -1, false, false, false, false, false, half);
+    if (p && p->half == half) return p;
   }
-  Variant *v = find_variant(d->n, d->precision, inc, outc, -1, false, false, false, false, false, d->half);
-  return v && v->half == d->half && !v->conv ? v : nullptr;
+  Variant *v = find_variant(d->n, d->precision, inc, outc, -1, false, false, false, false, false, half);
+  return v && v->half == half && !v->conv ? v : nullptr;
 }
 
 // 1 if the descriptor, with out_keep set, runs on a kernel whose stores stay cached (a KEEP twin exists for its shape)
@@ -1616,6 +1624,7 @@ int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thr
 const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
   if (d->half) {
     const Variant *h = pick_half(d);
+    if (h && (h->r2c || h->c2r) && h->mixed) return h->r2c ? "fft_half_r2c_panelx_k" : "fft_half_c2r_panelx_k";
     if (h && (h->r2c || h->c2r)) return h->r2c ? "fft_half_r2c_panel_k" : "fft_half_c2r_panel_k";
     if (h && h->mixed) return "fft_half_panelx_k";
     return !h ? "no half-line kernel" : (h->prec == OFFT_PREC_F32_PAIR ? "fft_half_panel_k<pairs>" : "fft_half_panel_k");

@@ -1069,6 +1069,9 @@ struct PanelXCfg {
 //        TPL is and whether or not the butterfly is a predicated one.  The same holds for a store index n = q + t N/R of the
 //        last stage's radix R.  So the skipped half costs no load, no predicate and no address on either side; the first
 //        and the last radix of a half instance are even.
+//        With the two real forms, as in panel_body (fft_half_r2c_panelx_k, fft_half_c2r_panelx_k): R2C with bit 1 -- the reals
+//        n >= N/2 of a row are literal zeros; of the N/2+1 outputs, the stores with 2t > R are not compiled and the one
+//        with 2t == R is live for q == 0 only.  C2R with bit 2 -- the reals n >= N/2 of a row are not stored.
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool C2R, int HALF = 0>
 __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
                                             const typename vec2<T>::type *twt) {
@@ -1081,7 +1084,9 @@ __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::
   static_assert(R0 <= 32 && R1 <= 32 && R2 <= 32, "register radix <= 32");
   static_assert(!(R2C && C2R) && (!C2R || OUTC), "real output: contiguous rows");
   constexpr int RLAST = NSTAGE == 3 ? R2 : (NSTAGE == 2 ? R1 : R0);
-  static_assert(HALF == 0 || (R0 % 2 == 0 && RLAST % 2 == 0 && !R2C && !C2R), "half lines: complex, first and last radix even");
+  static_assert(HALF == 0 || (R0 % 2 == 0 && RLAST % 2 == 0), "half lines: first and last radix even");
+  static_assert(HALF == 0 || ((!R2C || (HALF == 1 && INC && !OUTC)) && (!C2R || (HALF == 2 && !INC))),
+                "half lines, real ends: bit 1 on the real-input pass, bit 2 on the real-output pass");
 
   extern __shared__ __align__(16) unsigned char smem[];
   T *exs = reinterpret_cast<T *>(smem);
@@ -1253,6 +1258,8 @@ __device__ __forceinline__ void panelx_body(PassArgs a, const typename vec2<T>::
         static_for<0, NB * R>([&](auto ii) {
           constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
           if constexpr ((HALF & 2) != 0 && 2 * t >= R) return;  // the upper half of the output is not wanted
+          // (real input on half lines: n = q + t N/R is <= N/2 only with 2t < R, or 2t == R and q == 0 -- the rest is not compiled)
+          if constexpr (HALF != 0 && R2C && 2 * t > R) return;
           const int q = j + u * TPL;
           const int n = q + t * NBF;
           constexpr int src = u * R + perm_mixed(R, t);
@@ -1291,6 +1298,21 @@ template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool INC
 __global__ void __launch_bounds__(TPL * COLS, (PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
 fft_half_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twt) {
   panelx_body<T, N, TPL, R0, R1, R2, COLS, INC, OUTC, SPLIT, false, false, HALF>(a, in, out, twt);
+}
+
+// the real ends of a half-box chain at a mixed-radix length (offt_pass_desc::real_input with ::half and its bit 4), names of
+// their own like fft_half_r2c_panel_k and fft_half_c2r_panel_k: the real-input z pass that does not load the reals
+// n >= N/2 (contiguous rows in, strided out) ...
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_half_r2c_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twt) {
+  panelx_body<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT, true, false, 1>(a, in, out, twt);
+}
+// ... and the real-output z pass that does not store them (strided in, contiguous rows out)
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_half_c2r_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out, const typename vec2<T>::type *twt) {
+  panelx_body<T, N, TPL, R0, R1, R2, COLS, false, true, SPLIT, false, true, 2>(a, in, out, twt);
 }
 
 // Spectral convolution of whole lines of a mixed-radix length (offt_hipk_conv_pass with offt_filter_desc::mixed): to
@@ -1569,7 +1591,7 @@ struct Variant {
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
   bool conv = false;  // fft_conv_panel_k / fft_conv_panelx_k (mixed) instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
   int half = 0;       // fft_half_panel_k / fft_half_panelx_k / fft_conv_half_panel_k / fft_conv_half_panelx_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
-                      // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2)
+                      // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2), and with mixed their panelx twins
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
 // (uneven, or not a power of two: grids split over 3, 6, ... ranks)
@@ -1795,6 +1817,26 @@ void reg_variantx_half() {
   if constexpr ((FLAV & H_SC2) != 0) add(false, true, 2, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, true, SPLIT, 2>);
 }
 
+// the real ends of a half-box chain at a mixed-radix length (fft_half_r2c_panelx_k, fft_half_c2r_panelx_k;
+// offt_reg_half_real_mixed_*.hip): keyed by r2c / c2r together with half and mixed, so that no complex or full-line lookup
+// finds them and pick_half hands them out only to a descriptor that carries bit 4 of offt_pass_desc::half
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variantx_half_real() {
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  static_assert(Cfg::QUARTER, "half lines: N is a multiple of 4");
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  char nm[176];
+  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s half lines, real rows lds=%zuB",
+           prec ? "f32" : "f64", N, R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  registry().push_back(Variant{N, prec, true, false, 0, true, true, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
+                               (const void *)fft_half_r2c_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
+  registry().back().half = 1;
+  registry().push_back(Variant{N, prec, false, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
+                               (const void *)fft_half_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
+  registry().back().c2r = true;
+  registry().back().half = 2;
+}
+
 // fused convolution instances of the mixed-radix kernel (fft_conv_panelx_k, offt_reg_conv_mixed_*.hip; picked only with
 // offt_filter_desc::mixed): contiguous lines, no cache-keeping twin ...
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
@@ -1849,6 +1891,8 @@ void reg_half_real_f64();
 void reg_half_real_f32();
 void reg_half_mixed_f64();
 void reg_half_mixed_f32();
+void reg_half_real_mixed_f64();
+void reg_half_real_mixed_f32();
 void reg_dev();
 
 }  // namespace offtk

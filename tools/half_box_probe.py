@@ -14,8 +14,13 @@ the real field has as many bytes, its box is 1/8 of a sweep; the baseline makes 
 Mixed-radix lengths (mixed:): likewise the half box stays on and OFFT_HIP_OPT_HALF_MIXED is switched between 1 and 0.
 Their x pass has no fused convolve kernel: the convolve is the pruned forward, a multiply (the spectrum read and written,
 the filter read) and the pruned inverse, 2.625 + 2 + 2.625 = 7.25 sweeps plus the filter.
-usage: half_box_probe.py [r2c:|mixed:][f64|f32:]N ... [--runs R] [--out FILE]
-       (default: 512 f32:512 1024 f32:1024 r2c:512 r2c:f32:512 r2c:1024 r2c:f32:1024)"""
+Real-input plans at mixed-radix lengths (r2c:mixed:): the half box, OFFT_HIP_OPT_HALF_R2C and OFFT_HIP_OPT_HALF_MIXED stay on
+and OFFT_HIP_OPT_HALF_R2C_MIXED is switched between 1 and 0 on the same plan and buffers; the models are those of the two
+kinds together (sweeps over the half-spectrum volume, the unfused convolve).
+usage: half_box_probe.py [r2c:][mixed:][f64|f32:]N ... [--runs R] [--out FILE]
+       (default: 512 f32:512 1024 f32:1024 r2c:512 r2c:f32:512 r2c:1024 r2c:f32:1024;
+        the mixed-radix lines: mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000
+                               r2c:mixed:768 r2c:mixed:f32:768 r2c:mixed:1000 r2c:mixed:f32:1000)"""
 import os
 import statistics
 import sys
@@ -91,7 +96,9 @@ def main():
             api.offt_hip_execute_convolve(po, p, H.data_ptr(), api.FILTER_REAL)
 
         def route(on):
-            if r2c:
+            if r2c and mixed:
+                assert L.offt_hip_set_option(po, api.OPT_HALF_R2C_MIXED, 1 if on else 0) == 0
+            elif r2c:
                 assert L.offt_hip_set_option(po, api.OPT_HALF_R2C, 1 if on else 0) == 0
             elif mixed:
                 assert L.offt_hip_set_option(po, api.OPT_HALF_MIXED, 1 if on else 0) == 0
@@ -108,11 +115,13 @@ def main():
 
         V = 2.0 * esz * float(n) ** 2 * (n // 2 + 1 if r2c else n)
         api.offt_hip_set_half_box(po, True)
+        if r2c and mixed:   # the two older options stay on: alone they leave such a plan on the fallback
+            assert L.offt_hip_set_option(po, api.OPT_HALF_R2C, 1) == 0 and L.offt_hip_set_option(po, api.OPT_HALF_MIXED, 1) == 0
         route(True)
         pruned = api.offt_hip_half_box_pruned(po)
         fused = api.offt_hip_convolve_fused(po)
         models = {"forward": 2.625 * V, "inverse": 2.625 * V, "convolve": (3.25 if fused else 7.25) * V + 0.5 * V}
-        tag = f"{'r2c ' if r2c else 'mixed ' if mixed else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3"
+        tag = f"{'r2c ' if r2c else ''}{'mixed ' if mixed else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3"
         base = "option off: library clear + ordinary" if opt else "clear + ordinary"
         for name, fn in (("forward", fwd), ("inverse", inv), ("convolve", conv)):
             t = {True: [], False: []}
