@@ -78,6 +78,27 @@ int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *fil
  * rank, an x extent that is a power of two from 64 to 1024 or, with OFFT_HIP_OPT_CONV_MIXED, one of the mixed-radix lengths
  * listed there */
 int offt_hip_convolve_fused(const struct _offt_plan *po);
+/* spectral convolution with several outputs: ONE forward transform of `data`, then for k = 0 ... nout-1
+ *   outs[k] = scale * N * ifftn(filters[k] * fftn(x))   (irfftn / rfftn for an r2c plan)
+ * in the INPUT layout, exactly as offt_hip_execute_convolve leaves `data` -- the force components of a particle-mesh code
+ * from one density, the potential and the field of a Hockney solver.  filters[k] is laid out like the forward's OUTPUT block;
+ * all filters share one filter_kind.  `data` is consumed: its contents are undefined afterwards, unless one outs[k] is `data`
+ * itself (at most one may be) -- that output is computed last and `data` holds it.  Every other outs[k] is a device buffer of
+ * its own of offt_hip_local_bytes(po) bytes that overlaps neither `data` nor another output.  The output scale applies once
+ * per output; stream, async, half box, OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_ZGROUP_MIB are honoured as in the
+ * single-output call (a mixed-radix x extent takes the generic route here: forward, then a multiply and an inverse per
+ * output).  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and offt_hip_last_error() for nout < 1 or
+ * nout > OFFT_HIP_CONV_MAX_OUT, a NULL or host-memory outs[k] or filters[k], two equal outs entries, an unknown
+ * filter_kind, host-memory data, a failed communicator.  With nout == 1 and outs[0] == data the call IS
+ * offt_hip_execute_convolve: the same bits.  offt_hip_last_device_seconds covers the whole call;
+ * offt_hip_last_pass_seconds reports zeros. */
+#define OFFT_HIP_CONV_MAX_OUT 8
+int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout, void *const *outs, const void *const *filters,
+                                    int filter_kind);
+/* 1 if outputs other than `data` run the fused multi-output route: the forward's z and y passes once, then per output one
+ * out-of-place launch (forward x pass . filter . inverse x pass, data -> outs[k]) and the inverse's y and z passes -- one
+ * rank, the default z-y-x layout, an x extent that is a power of two from 64 to 1024; 0: the generic route */
+int offt_hip_convolve_multi_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
  *   full spectrum of the zero-padded field, in the usual output layout.

@@ -100,6 +100,10 @@ def bind(L):
     L.offt_hip_execute_convolve.argtypes = [PP, C.c_void_p, C.c_void_p, i]
     L.offt_hip_convolve_fused.restype = i
     L.offt_hip_convolve_fused.argtypes = [PP]
+    L.offt_hip_execute_convolve_multi.restype = i
+    L.offt_hip_execute_convolve_multi.argtypes = [PP, C.c_void_p, i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i]
+    L.offt_hip_convolve_multi_fused.restype = i
+    L.offt_hip_convolve_multi_fused.argtypes = [PP]
     L.offt_hip_set_half_box.restype = i
     L.offt_hip_set_half_box.argtypes = [PP, i]
     L.offt_hip_half_box_pruned.restype = i
@@ -202,6 +206,27 @@ def offt_hip_execute_convolve(po, data, filt, filter_kind=FILTER_REAL):
 def offt_hip_convolve_fused(po):
     """True if the plan's convolve runs the fused route (one launch for forward pass . filter . inverse pass)"""
     return lib().offt_hip_convolve_fused(po) == 1
+
+
+def offt_hip_execute_convolve_multi(po, data, outs, filts, filter_kind=FILTER_REAL):
+    """one forward transform of `data`, then outs[k] = scale * N * ifftn(filts[k] * fftn(x)) for every k (lists of device
+    pointers of equal length; at most one outs[k] may be `data` itself, every other one is a buffer of its own of
+    offt_hip_local_bytes bytes).  `data` is consumed unless it is one of the outputs (include/offt_hip.h)"""
+    L = lib()
+    if len(outs) != len(filts):
+        raise ValueError("offt_hip_execute_convolve_multi: %d outputs, %d filters" % (len(outs), len(filts)))
+    n = len(outs)
+    po_, pf_ = (C.c_void_p * max(n, 1))(*outs), (C.c_void_p * max(n, 1))(*filts)
+    if L.offt_hip_execute_convolve_multi(po, data, n, po_, pf_, filter_kind) != 0:
+        raise RuntimeError("offt_hip_execute_convolve_multi failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_convolve_multi_fused(po):
+    """True if outputs other than `data` run the fused multi-output route (one out-of-place fused launch per output)"""
+    return lib().offt_hip_convolve_multi_fused(po) == 1
+
+
+CONV_MAX_OUT = 8  # offt_hip.h OFFT_HIP_CONV_MAX_OUT
 
 
 def offt_hip_set_half_box(po, on=True):

@@ -62,6 +62,14 @@ typedef struct offt_backend {
    * whose passes cannot skip the padding themselves); NULL: half-box is refused on this backend. */
   int (*zero_outside)(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1, long long s2,
                       void *stream);
+  /* ---- multi-output convolution (offt_hip_execute_convolve_multi); appended, so that a table written before them leaves
+   * both NULL ----
+   * conv_pass_oop: offt_hipk_conv_pass_oop -- the fused launch from `src` into `dst`; NULL: no fused multi-output route.
+   * pointwise_oop: offt_hipk_pointwise_oop -- out = in * H; NULL: memcpy_dd followed by the in-place pointwise. */
+  int (*conv_pass_oop)(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, const void *src, void *dst,
+                       void *stream);
+  int (*pointwise_oop)(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
+                       long long s1, long long s2, void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);

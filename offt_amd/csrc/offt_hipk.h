@@ -164,6 +164,22 @@ const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_fil
  * kind as offt_filter_desc::kind.  Non-temporal, 16 B per lane along the smallest stride. */
 int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2,
                         long long s0, long long s1, long long s2, void *stream);
+/* ---- multi-output convolution (offt_hip_execute_convolve_multi): the two operations that store somewhere other than where
+ * they loaded, so that a spectrum can stay where it is while several filters are applied to it ----
+ * offt_hipk_conv_pass with a separate destination: the lines of `src` (fwd's in_* addressing) convolved into `dst` at the
+ * same offsets; `src` is not written.  fwd->half: 0 or 3, as there; fwd->out_keep: the cache-keeping twin (every instance
+ * has one, the half-line ones too).  Power-of-two lines of 64 ... 1024 points only: f->mixed finds no kernel here.
+ * -1 if no such kernel exists, and for src == dst (that is offt_hipk_conv_pass). */
+int offt_hipk_conv_pass_oop(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, const void *src, void *dst,
+                            void *stream);
+/* 1 if offt_hipk_conv_pass_oop has a kernel for (fwd, f); the registry lookup needs no device */
+int offt_hipk_conv_has_fused_oop(const offt_pass_desc *fwd, const offt_filter_desc *f);
+/* "fft_conv_oop_panel_k", "fft_conv_oop_half_panel_k" (fwd->half = 3) or "no fused kernel" */
+const char *offt_hipk_conv_oop_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f);
+/* out[i0 s0 + i1 s1 + i2 s2] = in[same] * H[same] over the box n0 x n1 x n2: offt_hipk_pointwise with a separate destination
+ * (in != out; `in` is not written).  Non-temporal, 16 B per lane along the smallest stride. */
+int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2,
+                            long long s0, long long s1, long long s2, void *stream);
 /* zero a strided 3-D block n0 x n1 x n2 OUTSIDE the kept sub-box [0,k0) x [0,k1) x [0,k2) (0 <= k <= n); the kept part is
  * not touched.  Elements are complex values of `precision`, or, with OFFT_HIPK_ZERO_REAL or-ed into it, real scalars (the
  * rows of an r2c plan; strides and extents then count scalars).  Vector stores, 16 B per lane along a unit stride s2. */

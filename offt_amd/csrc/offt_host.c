@@ -667,6 +667,18 @@ static int hb_pointwise(void *data, const void *filter, int precision, int kind,
   if (rc) SET_ERR("pointwise multiply failed: %s", offt_hipk_last_error());
   return rc;
 }
+static int hb_conv_pass_oop(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, const void *src, void *dst,
+                            void *stream) {
+  const int rc = offt_hipk_conv_pass_oop(fwd, f, filter, src, dst, stream);
+  if (rc) SET_ERR("out-of-place fused convolution pass n=%d failed: %s", fwd->n, offt_hipk_last_error());
+  return rc;
+}
+static int hb_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
+                            long long s1, long long s2, void *stream) {
+  const int rc = offt_hipk_pointwise_oop(in, out, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
+  if (rc) SET_ERR("out-of-place pointwise multiply failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static int hb_zero_outside(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1, long long s2,
                            void *stream) {
   const int rc = offt_hipk_zero_outside(buf, precision, n0, n1, n2, k0, k1, k2, s0, s1, s2, stream);
@@ -676,7 +688,8 @@ static int hb_zero_outside(void *buf, int precision, int n0, int n1, int n2, int
 static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
-    hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside};
+    hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside,
+    hb_conv_pass_oop, hb_pointwise_oop};
 
 /* ------------------------------------------------------------------------- */
 /* helpers                                                                    */
@@ -3082,6 +3095,167 @@ int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *fil
     st->out_scale = scale;
     if (!rc) rc = conv_pointwise(po, data, filter, filter_kind);
     if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, data) : execute_single(po, data, +1);
+  }
+  st->out_scale = scale;
+  st->yx_fused = 0;
+  if (timed) be->event_record(st->ev1, st->s_compute);
+  if (rc) {
+    if (st->uses_rccl) comm_fail(st);
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if (st->async) { t[ALL] = wall_seconds() - t0; return 0; }
+  if (wait_compute(st)) { t[ALL] = 99999999.0; return -1; }
+  st->last_dev_s = 1e-3 * be->event_ms(st->ev0, st->ev1);
+  for (int i = 0; i < 3; i++) st->pass_s[i] = 0.0;
+  t[ALL] = wall_seconds() - t0;
+  return 0;
+}
+
+/* ------------------------------------------------------------------------- */
+/* multi-output spectral convolution: one forward, several filters             */
+/* ------------------------------------------------------------------------- */
+/* The fused multi-output route: one rank, the z-y-x layout, the conditions of conv_fused_route, and a backend and a kernel
+ * for the out-of-place fused launch (powers of two from 64 to 1024: a mixed-radix x extent has none, whatever
+ * OFFT_HIP_OPT_CONV_MIXED says).  Fills what conv_fused_route fills. */
+static int conv_multi_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, offt_pass_desc *fd,
+                                  offt_filter_desc *fl) {
+  hip_state *st = (hip_state *)po->hip_state;
+  if (!fw->zyx || !st->be->conv_pass_oop) return 0;
+  if (!conv_fused_route(po, fw, iv, kind, fd, fl)) return 0;
+  return offt_hipk_conv_has_fused_oop(fd, fl);
+}
+
+/* z-y-x: the forward is data -> W -> data with the x pass in place, the inverse x in place, y: buf -> W, z: W -> buf.  The
+ * spectrum ahead of the x pass stays in `data` while every output but the last is made from it:
+ *   P1 (z) once;
+ *   first output:  per plane group  forward y (W -> data, kept), out-of-place fused launch (data -> out, kept), inverse y
+ *                  (out -> W);  then inverse z (W -> out);
+ *   later outputs: the same without the forward y;
+ *   an output that IS `data` comes last (order[]) and runs the in-place fused launch.
+ * W is one volume, so the outputs are the outer loop: the inverse y of a group writes the part of W that the forward y of
+ * that group has read, and the next output's inverse y overwrites W only behind this output's inverse z.
+ * 1: no such route (the caller takes the generic one). */
+static int execute_convolve_multi_single(struct _offt_plan *po, void *data, int nout, const int *order, void *const *outs,
+                                         const void *const *filters, int kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  void *s = st->s_compute;
+  single_sched fw, iv;
+  single_schedule(po, data, -1, &fw);
+  single_schedule(po, data, +1, &iv);
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  if (!conv_multi_fused_route(po, &fw, &iv, kind, &fd, &fl)) return 1;
+  const size_t fesz = kind == OFFT_FILTER_COMPLEX ? st->esz : st->esz / 2; /* filter bytes per element */
+  const offt_pass_desc *py = &fw.d[1];
+  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
+  int ng = 0; /* planes per group, as in execute_convolve_single; 0: plain launches */
+  if (py->nb1 == cnt && fd.nb1 == cnt && iv.d[1].nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, py);
+  const int step = ng >= 1 ? ng : (cnt > 0 ? cnt : 1);
+  if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
+  for (int i = 0; i < nout; i++) {
+    void *out = outs[order[i]];
+    const void *filter = filters[order[i]];
+    single_schedule(po, out, +1, &iv); /* x in place on out, y: out -> W, z: W -> out, the output scale on the z pass */
+    for (int z0 = 0; z0 < cnt; z0 += step) {
+      const int g = cnt - z0 < step ? cnt - z0 : step;
+      offt_pass_desc a = *py, b = fd, q = iv.d[1];
+      a.nb1 = b.nb1 = q.nb1 = g;
+      a.out_keep = b.out_keep = ng >= 1;
+      const size_t off = (size_t)z0 * (size_t)b.in_b1_stride * st->esz; /* the group's planes, in data and in out alike */
+      const char *fg = (const char *)filter + (size_t)z0 * (size_t)fl.b1_stride * fesz;
+      if (i == 0 && be->pass(&a, (const char *)fw.src[1] + (size_t)z0 * (size_t)a.in_b1_stride * st->esz,
+                             (char *)fw.dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * st->esz, s))
+        return -1;
+      if (out == data ? be->conv_pass(&b, &fl, fg, (char *)data + off, s)
+                      : be->conv_pass_oop(&b, &fl, fg, (const char *)data + off, (char *)out + off, s))
+        return -1;
+      if (be->pass(&q, (const char *)iv.src[1] + (size_t)z0 * (size_t)q.in_b1_stride * st->esz,
+                   (char *)iv.dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * st->esz, s))
+        return -1;
+    }
+    if (be->pass(&iv.d[2], iv.src[2], iv.dst[2], s)) return -1;
+  }
+  return 0;
+}
+
+int offt_hip_convolve_multi_fused(const struct _offt_plan *po) {
+  if (!po || !po->hip_state) return 0;
+  single_sched fw, iv;
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  struct _offt_plan *p = (struct _offt_plan *)po;
+  if (((hip_state *)po->hip_state)->use_pipeline) return 0;
+  single_schedule(p, NULL, -1, &fw);
+  single_schedule(p, NULL, +1, &iv);
+  return conv_multi_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, &fd, &fl);
+}
+
+int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout, void *const *outs, const void *const *filters,
+                                    int filter_kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const struct _offt_comm *c = po->comm;
+  double *t = po->t;
+  memset(t, 0, GES * sizeof(double));
+  TEST_NOTE_MESH(po);
+#define MULTI_REFUSE(...) do { SET_ERR(__VA_ARGS__); t[ALL] = 99999999.0; return -1; } while (0)
+  if (nout < 1 || nout > OFFT_HIP_CONV_MAX_OUT)
+    MULTI_REFUSE("offt_hip_execute_convolve_multi: nout = %d (1 ... OFFT_HIP_CONV_MAX_OUT = %d outputs)", nout, OFFT_HIP_CONV_MAX_OUT);
+  if (filter_kind != OFFT_HIP_FILTER_REAL && filter_kind != OFFT_HIP_FILTER_COMPLEX)
+    MULTI_REFUSE("offt_hip_execute_convolve_multi: unknown filter_kind %d (OFFT_HIP_FILTER_REAL or OFFT_HIP_FILTER_COMPLEX)", filter_kind);
+  if (!outs || !filters) MULTI_REFUSE("offt_hip_execute_convolve_multi: outs and filters must be arrays of nout pointers (got NULL)");
+  if (!data || (!g_backend && !is_device_ptr(data)))
+    MULTI_REFUSE("offt_hip_execute_convolve_multi: the data must be device memory (no host staging for a convolve)");
+  for (int k = 0; k < nout; k++) {
+    if (!filters[k] || (!g_backend && !is_device_ptr(filters[k])))
+      MULTI_REFUSE("offt_hip_execute_convolve_multi: filter %d must be device memory%s", k, filters[k] ? "" : " (got NULL)");
+    if (!outs[k] || (!g_backend && !is_device_ptr(outs[k])))
+      MULTI_REFUSE("offt_hip_execute_convolve_multi: output %d must be device memory%s", k, outs[k] ? "" : " (got NULL)");
+    for (int j = 0; j < k; j++)
+      if (outs[j] == outs[k]) MULTI_REFUSE("offt_hip_execute_convolve_multi: outputs %d and %d are the same array", j, k);
+  }
+  if (!be->pointwise) MULTI_REFUSE("offt_hip_execute_convolve_multi: this backend has no pointwise multiply");
+  if ((st->uses_rccl || st->p2p) && G.comm_failed)
+    MULTI_REFUSE("offt_hip_execute_convolve_multi: the communicator failed earlier; make a new world (offt_hip_set_world) and plan");
+#undef MULTI_REFUSE
+  /* one output, in place: the single-output call itself, bit for bit */
+  if (nout == 1 && outs[0] == data) return offt_hip_execute_convolve(po, data, filters[0], filter_kind);
+  /* the output that is `data` (at most one: the entries differ) is computed last: until then `data` holds the spectrum */
+  int order[OFFT_HIP_CONV_MAX_OUT], n = 0;
+  for (int k = 0; k < nout; k++) if (outs[k] != data) order[n++] = k;
+  for (int k = 0; k < nout; k++) if (outs[k] == data) order[n++] = k;
+  const double t0 = wall_seconds();
+  const int timed = st->async ? 0 : 1;
+  st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros, as after a convolve */
+  if (timed) be->event_record(st->ev0, st->s_compute);
+  const double scale = st->out_scale;
+  int rc = half_box_clear(po, data);
+  if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_multi_single(po, data, nout, order, outs, filters, filter_kind);
+  if (rc > 0) {
+    /* generic: forward in place on data (unscaled), then per output the multiply data -> out and the inverse in place on out,
+     * the output scale on its last store.  Neither inverse ties its buffer to the forward's: execute_single builds its launches
+     * from the array it is given, and execute_inverse_multi records the forward schedule against that array (inv_data) --
+     * what else a step touches, under the staged and the direct-store exchange alike, is the plan's own send, receive and
+     * work volumes (peers map those, never the caller's array). */
+    st->out_scale = 1.0;
+    if (!st->use_pipeline) rc = execute_single(po, data, -1);
+    else rc = st->slab_zyx ? execute_slab(po, data) : execute_pipeline(po, data, -1);
+    st->out_scale = scale;
+    for (int i = 0; i < nout && !rc; i++) {
+      void *out = outs[order[i]];
+      const void *filter = filters[order[i]];
+      if (out == data) rc = conv_pointwise(po, data, filter, filter_kind);
+      else if (be->pointwise_oop)
+        rc = be->pointwise_oop(data, out, filter, st->prec, filter_kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0],
+                               c->ostride[1], c->ostride[2], st->s_compute) ? -1 : 0;
+      else { /* a backend from before the out-of-place multiply: copy, then multiply in place */
+        rc = be->memcpy_dd(out, data, local_elems(c) * st->esz, st->s_compute) ? -1 : 0;
+        if (!rc) rc = conv_pointwise(po, out, filter, filter_kind);
+      }
+      if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, out) : execute_single(po, out, +1);
+    }
   }
   st->out_scale = scale;
   st->yx_fused = 0;

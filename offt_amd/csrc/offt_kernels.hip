@@ -296,6 +296,46 @@ copy3d_k(const V2 *in, V2 *out, int n0, int n1, int n2, long long is0, long long
   }
 }
 
+// out = in * filter over a strided box (offt_hipk_pointwise_oop): pointwise_k with a separate destination at the same
+// offsets -- the source stays as it was, so that several filters can be applied to one spectrum.  16 B per lane,
+// non-temporal both ways.
+template <typename T, bool CPLX, int EPL>
+__global__ void __launch_bounds__(256)
+pointwise_oop_k(const typename vec2<T>::type *in, typename vec2<T>::type *out, const void *filter, int n1, int n2, long long s0, long long s1,
+                long long s2, long long rows) {
+  using V2 = typename vec2<T>::type;
+  const int i2 = (blockIdx.x * 256 + threadIdx.x) * EPL;
+  if (i2 >= n2) return;
+  for (long long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const long long i1 = r % n1, i0 = r / n1;
+    const long long o = i0 * s0 + i1 * s1 + (long long)i2 * s2;
+    if constexpr (EPL == 2) {  // (s2 == 1, n2 even, 16-B aligned rows: two float2 as one float4)
+      typedef float f4 __attribute__((ext_vector_type(4)));
+      typedef float f2v __attribute__((ext_vector_type(2)));
+      f4 x = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(in + o));
+      if constexpr (CPLX) {
+        const f4 h = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(reinterpret_cast<const V2 *>(filter) + o));
+        x = f4{x.x * h.x - x.y * h.y, x.x * h.y + x.y * h.x, x.z * h.z - x.w * h.w, x.z * h.w + x.w * h.z};
+      } else {
+        const f2v h = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(reinterpret_cast<const T *>(filter) + o));
+        x = f4{x.x * h.x, x.y * h.x, x.z * h.y, x.w * h.y};
+      }
+      __builtin_nontemporal_store(x, reinterpret_cast<f4 *>(out + o));
+    } else {
+      V2 x = gload(in + o);
+      if constexpr (CPLX) {
+        const V2 h = gload(reinterpret_cast<const V2 *>(filter) + o);
+        const T re = x.x * h.x - x.y * h.y, im = x.x * h.y + x.y * h.x;
+        x.x = re; x.y = im;
+      } else {
+        const T h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + o);
+        x.x *= h; x.y *= h;
+      }
+      gstore(out + o, x);
+    }
+  }
+}
+
 // pointwise multiply of a spectrum block by a filter at the same element index (offt_hipk_pointwise): rows along the
 // smallest stride, 16 B per lane (two single-precision elements when that stride is 1), non-temporal both ways --
 // every byte is touched once
@@ -461,6 +501,8 @@ void build_registry() {
   reg_mixed_f32_b();
   reg_conv_f64();
   reg_conv_f32();
+  reg_conv_oop_f64();
+  reg_conv_oop_f32();
   reg_conv_mixed_f64();
   reg_conv_mixed_f32();
   reg_half_f64();
@@ -481,22 +523,22 @@ std::mutex g_idx_mu;
 std::unordered_map<unsigned long long, std::vector<int>> g_idx;
 size_t g_idx_size = 0;
 unsigned long long variant_key(int n, int prec, bool inc, bool outc, bool r2c, bool keep = false, bool tw4 = false, bool c2r = false,
-                               bool conv = false, int half = 0) {
-  return ((unsigned long long)n << 11) | ((unsigned long long)(half & 3) << 9) | (conv ? 256u : 0u) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
+                               bool conv = false, int half = 0, bool oop = false) {
+  return ((unsigned long long)n << 12) | (oop ? 2048u : 0u) | ((unsigned long long)(half & 3) << 9) | (conv ? 256u : 0u) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
 }
 
 Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = false, bool keep = false, bool tw4 = false, bool c2r = false,
-                      bool conv = false, int half = 0) {
+                      bool conv = false, int half = 0, bool oop = false) {
   std::call_once(g_reg_once, build_registry);
   std::lock_guard<std::mutex> lk(g_idx_mu);
   auto &reg = registry();
   if (g_idx_size != reg.size()) {
     g_idx.clear();
     for (size_t i = 0; i < reg.size(); ++i)
-      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r, reg[i].conv, reg[i].half)].push_back((int)i);
+      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r, reg[i].conv, reg[i].half, reg[i].oop)].push_back((int)i);
     g_idx_size = reg.size();
   }
-  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r, conv, half));
+  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r, conv, half, oop));
   if (it == g_idx.end()) return nullptr;
   Variant *def = nullptr;
   for (int i : it->second) {
@@ -1795,16 +1837,17 @@ int offt_hipk_flag_wait(int n, unsigned long long *const *addr, unsigned long lo
 namespace {
 // the fused instance for (fwd, f), or nullptr: contiguous complex lines without a split, a unit-stride filter axis.  The
 // mixed-radix instances (fft_conv_panelx_k; lengths that have no power-of-two instance) only with f->mixed.
-Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep) {
+// oop: the out-of-place instances (fft_conv_oop_panel_k): the power-of-two lengths only, each with a cache-keeping twin, half lines included.
+Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep, bool oop = false) {
   if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
   if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
   if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || f->axis_stride != 1)
     return nullptr;
   if (d->half && d->half != 3) return nullptr;  // half lines: loads and stores together, or not at all
-  if (d->half && keep) return nullptr;          // (no cache-keeping twin)
-  Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true, d->half);
-  if (v && v->mixed && !f->mixed) return nullptr;
-  return v && v->conv && v->keep == keep && v->half == d->half ? v : nullptr;
+  if (d->half && keep && !oop) return nullptr;  // (no cache-keeping twin of the in-place half-line kernels)
+  Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true, d->half, oop);
+  if (v && v->mixed && (!f->mixed || oop)) return nullptr;
+  return v && v->conv && v->oop == oop && v->keep == keep && v->half == d->half ? v : nullptr;
 }
 }  // namespace
 
@@ -1830,6 +1873,34 @@ int offt_hipk_conv_pass(const offt_pass_desc *d, const offt_filter_desc *f, cons
   fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
   void *args[] = {(void *)&a, (void *)&fa, (void *)&data, (void *)&filter, (void *)&tb.full};
   return launch("offt_hipk_conv_pass", v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2,
+                &a.xcd_lim, &a.xcd_gshift, args, (hipStream_t)stream);
+}
+
+int offt_hipk_conv_has_fused_oop(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false, true) != nullptr; }
+
+const char *offt_hipk_conv_oop_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
+  const Variant *v = pick_conv(fwd, f, false, true);
+  if (!v) return "no fused kernel";
+  return fwd->half ? "fft_conv_oop_half_panel_k" : "fft_conv_oop_panel_k";
+}
+
+int offt_hipk_conv_pass_oop(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream) {
+  if (!src || !dst || src == dst) {
+    snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass_oop: needs two different arrays (src == dst is offt_hipk_conv_pass)");
+    return -1;
+  }
+  Variant *v = pick_conv(d, f, d && d->out_keep, true);
+  if (!v && d && d->out_keep) v = pick_conv(d, f, false, true);
+  if (!v) { snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass_oop: no out-of-place fused convolution kernel for this descriptor (n=%d)", d ? d->n : 0); return -1; }
+  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  PassArgs a = pass_args(d, v->cols, true);
+  ConvArgs fa;
+  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
+  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
+  void *args[] = {(void *)&a, (void *)&fa, (void *)&src, (void *)&dst, (void *)&filter, (void *)&tb.full};
+  return launch("offt_hipk_conv_pass_oop", v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2,
                 &a.xcd_lim, &a.xcd_gshift, args, (hipStream_t)stream);
 }
 
@@ -1860,6 +1931,38 @@ int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind,
   else if (cx) FOR_PREC(precision, POINTWISE(T, true, 1));
   else FOR_PREC(precision, POINTWISE(T, false, 1));
 #undef POINTWISE
+  HIPK_CHECK(hipGetLastError());
+  return 0;
+}
+
+int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
+                            long long s1, long long s2, void *stream) {
+  if (kind != OFFT_FILTER_REAL && kind != OFFT_FILTER_COMPLEX) { snprintf(g_err, sizeof g_err, "offt_hipk_pointwise_oop: bad filter kind %d", kind); return -1; }
+  if (!in || !out || in == out) { snprintf(g_err, sizeof g_err, "offt_hipk_pointwise_oop: needs two different arrays (in place: offt_hipk_pointwise)"); return -1; }
+  if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
+  // rows along the smallest stride
+  int n[3] = {n0, n1, n2};
+  long long st[3] = {s0, s1, s2};
+  for (int a = 0; a < 2; a++)
+    for (int b = 0; b < 2 - a; b++)
+      if (st[b] < st[b + 1]) { int tn = n[b]; n[b] = n[b + 1]; n[b + 1] = tn; long long ts = st[b]; st[b] = st[b + 1]; st[b + 1] = ts; }
+  const long long rows = (long long)n[0] * n[1];
+  const bool f32 = precision == OFFT_PREC_F32;
+  // two single-precision elements per lane: unit stride, whole pairs, 16-B aligned rows and bases
+  const bool pair = f32 && st[2] == 1 && !(n[2] & 1) && !(st[1] & 1) && !(st[0] & 1) && !((uintptr_t)in & 15) && !((uintptr_t)out & 15) &&
+                    !((uintptr_t)filter & (kind == OFFT_FILTER_COMPLEX ? 15 : 7));
+  const int epl = pair ? 2 : 1;
+  const unsigned gx = (unsigned)((n[2] / epl + 255) / 256);
+  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
+  hipStream_t sm = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const bool cx = kind == OFFT_FILTER_COMPLEX;
+#define POINTWISE_OOP(T, CPLX, EPL) \
+  hipLaunchKernelGGL((pointwise_oop_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, (const typename vec2<T>::type *)in, (typename vec2<T>::type *)out, filter, n[1], n[2], st[0], st[1], st[2], rows)
+  if (pair) { if (cx) POINTWISE_OOP(float, true, 2); else POINTWISE_OOP(float, false, 2); }
+  else if (cx) FOR_PREC(precision, POINTWISE_OOP(T, true, 1));
+  else FOR_PREC(precision, POINTWISE_OOP(T, false, 1));
+#undef POINTWISE_OOP
   HIPK_CHECK(hipGetLastError());
   return 0;
 }

@@ -657,9 +657,11 @@ struct ConvArgs {
 // HALF (fft_conv_half_panel_k, offt_pass_desc::half = 3): the lines are zero above N/2 going in and only their lower half
 // is wanted coming out -- the upper half is neither loaded nor stored (compile-time, as in panel_body); the filter and
 // everything between the two is the full line
+// The lines are loaded from `data` and stored at the same offsets from `dst`: the in-place kernels pass one pointer twice,
+// the out-of-place ones (fft_conv_oop_panel_k, offt_hipk_conv_pass_oop) a second volume, and never write the first.
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP, bool HALF = false>
-__device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter,
-                                          const typename vec2<T>::type *twq) {
+__device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, const typename vec2<T>::type *data, typename vec2<T>::type *dst,
+                                          const void *filter, const typename vec2<T>::type *twq) {
   using V2 = typename vec2<T>::type;
   using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
   constexpr int TPL = Cfg::TPL, NT = Cfg::NT, NSTAGE = Cfg::NSTAGE;
@@ -696,7 +698,9 @@ __device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<
   const int c0 = cp * COLS;
   const int j = tid % TPL, c = tid / TPL;
   const bool valid = (c0 + c) < a.ncols;
-  V2 *line = data + (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col + (long long)j * a.in_axis;
+  const long long lo = (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col + (long long)j * a.in_axis;
+  const V2 *line = data + lo;
+  V2 *sline = dst + lo;
   const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col + (long long)j * f.axis;
 
   // a wave owns whole columns when TPL divides 64: its exchanges need no workgroup barrier (see panel_body)
@@ -887,7 +891,7 @@ __device__ __forceinline__ void conv_body(PassArgs a, ConvArgs f, typename vec2<
     V2 w;
     w.x = x.x * sc;
     w.y = -x.y * sc;
-    if (valid) gstore_p<KEEP>(line + (long long)cn * a.in_axis, w);
+    if (valid) gstore_p<KEEP>(sline + (long long)cn * a.in_axis, w);
   });
 }
 
@@ -899,13 +903,30 @@ constexpr int conv_wps() { return PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WP
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
 __global__ void __launch_bounds__((N / E) * COLS, (conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
 fft_conv_panel_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twq) {
-  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP>(a, f, data, filter, twq);
+  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP>(a, f, data, data, filter, twq);
 }
 
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
 __global__ void __launch_bounds__((N / E) * COLS, (conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
 fft_conv_half_panel_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twq) {
-  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP, true>(a, f, data, filter, twq);
+  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP, true>(a, f, data, data, filter, twq);
+}
+
+// out of place (offt_hipk_conv_pass_oop): the lines of `src` convolved into `dst` at the same offsets, `src` left as it
+// was -- the multi-output convolution applies several filters to one spectrum.  Kernels of their own names: the in-place
+// symbols above stay what they were.
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_oop_panel_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst, const void *filter,
+                     const typename vec2<T>::type *twq) {
+  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP>(a, f, src, dst, filter, twq);
+}
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_oop_half_panel_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst, const void *filter,
+                          const typename vec2<T>::type *twq) {
+  conv_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP, true>(a, f, src, dst, filter, twq);
 }
 
 // ---------------------------------------------------------------------------
@@ -1590,6 +1611,7 @@ struct Variant {
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
   bool conv = false;  // fft_conv_panel_k / fft_conv_panelx_k (mixed) instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
+  bool oop = false;   // fft_conv_oop_panel_k / fft_conv_oop_half_panel_k instance (offt_hipk_conv_pass_oop): conv with a separate store base
   int half = 0;       // fft_half_panel_k / fft_half_panelx_k / fft_conv_half_panel_k / fft_conv_half_panelx_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
                       // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2), and with mixed their panelx twins
 };
@@ -1757,6 +1779,28 @@ void reg_variant_conv_half() {
   registry().back().half = 3;
 }
 
+// out-of-place fused convolution (fft_conv_oop_panel_k, fft_conv_oop_half_panel_k; offt_reg_conv_oop_*.hip): the shapes of
+// reg_variant_conv, full lines and half lines, each plain and with cache-keeping stores
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variant_conv_oop() {
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  auto add = [&](bool keep, int half, const void *fn) {
+    char nm[176];
+    snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s out-of-place convolution%s lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1,
+             R2, COLS, SPLIT ? "split-re/im" : "packed", half ? " on half lines" : "", (size_t)Cfg::LDS_BYTES);
+    registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
+    registry().back().keep = keep;
+    registry().back().conv = true;
+    registry().back().oop = true;
+    registry().back().half = half;
+  };
+  add(false, 0, (const void *)fft_conv_oop_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
+  add(true, 0, (const void *)fft_conv_oop_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
+  add(false, 3, (const void *)fft_conv_oop_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
+  add(true, 3, (const void *)fft_conv_oop_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
+}
+
 // mixed-radix (2^a 3^b 5^c) panel kernel: TPL threads per line instead of elements per thread.
 // FLAV limits which (in_contig, out_contig) flavours are instantiated at all (compile time), defmask says for
 // which of them this variant is the default.
@@ -1883,6 +1927,8 @@ void reg_mixed_f32_a();
 void reg_mixed_f32_b();
 void reg_conv_f64();
 void reg_conv_f32();
+void reg_conv_oop_f64();
+void reg_conv_oop_f32();
 void reg_conv_mixed_f64();
 void reg_conv_mixed_f32();
 void reg_half_f64();

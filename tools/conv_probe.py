@@ -11,8 +11,14 @@ A spec with the prefix mixed: measures OFFT_HIP_OPT_CONV_MIXED instead (x length
 convolve with the option at 1 and at 0 ALTERNATES after a warm-up, MIXED_REPS times each (default 20), and the line
 reports min and median of both, their ratios, the option-off route's own spread (median / min - 1) and the byte model
 (c) / (b).  mixed:half:N does so on a pruned half-box plan (OFFT_HIP_OPT_HALF_MIXED, an N/2 box).
-usage: conv_probe.py [mixed:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
-       (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768)"""
+A spec with the prefix multi: measures offt_hip_execute_convolve_multi with K = 3 real filters (two outputs of their own,
+the third in `data`) against three offt_hip_execute_convolve calls on the same plan and buffers -- the single-output code
+is the baseline.  The two ALTERNATE after a warm-up, MIXED_REPS times each, and the line reports min and median of both,
+their ratios, the baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5.  multi:half:N does so on a
+pruned half-box plan (an N/2 box).
+usage: conv_probe.py [mixed:|multi:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+       (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768;
+        the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512)"""
 import ctypes as C
 import os
 import sys
@@ -54,7 +60,8 @@ def main():
     specs = args or ["1024", "f32:1024", "r2c:512", "mixed:768", "mixed:f32:768", "mixed:1000", "mixed:f32:1000", "mixed:half:768"]
     torch.cuda.set_device(0)
     for spec in specs:
-        mixed = spec.startswith("mixed:")
+        multi = spec.startswith("multi:")
+        mixed = spec.startswith("mixed:") or multi  # (the same grammar behind the prefix)
         half = mixed and spec[6:].startswith("half:")
         kind, _, n_s = spec[(6 if mixed else 0) + (5 if half else 0):].rpartition(":")
         n = int(n_s)
@@ -97,6 +104,44 @@ def main():
         def cv():
             api.offt_hip_execute_convolve(po, dev.data_ptr(), H.data_ptr(), api.FILTER_REAL)
 
+        if multi:
+            K = 3
+            if half:
+                api.offt_hip_set_half_box(po, True)
+            Hs = [H] + [torch.rand(api.local_elems(po), dtype=td, device="cuda") * (1.0 / float(n) ** 3) for _ in range(K - 1)]
+            outs = [torch.zeros_like(dev) for _ in range(K - 1)] + [dev]
+            op, fp = [o_.data_ptr() for o_ in outs], [h_.data_ptr() for h_ in Hs]
+
+            def mv():
+                api.offt_hip_execute_convolve_multi(po, dev.data_ptr(), op, fp, api.FILTER_REAL)
+
+            def three():
+                for h_ in Hs:
+                    api.offt_hip_execute_convolve(po, dev.data_ptr(), h_.data_ptr(), api.FILTER_REAL)
+
+            t = {"multi": [], "three": []}
+            for rep_i in range(2 + MIXED_REPS):
+                for name, fn in (("multi", mv), ("three", three)):
+                    dt = run(fn)
+                    if rep_i >= 2:
+                        t[name].append(dt)
+            mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+            fused1, fusedk = api.offt_hip_convolve_fused(po), api.offt_hip_convolve_multi_fused(po)
+            # bytes per point in units of esz (f64: x 8), complex plan, full lines: K fused calls 168 K / 8, the fused multi
+            # route (64 + 104 K) / 8; unfused 232 K / 8 against (96 + 136 K) / 8
+            byte_model = (8 + 13 * K) / (21.0 * K) if fusedk else (12 + 17 * K) / (29.0 * K)
+            tag = f"{'r2c f64' if r2c else ('f32' if prec == api.F32 else 'f64')} {n}^3 K={K}"
+            if half:
+                tag += f" half box {n // 2}^3 [{'pruned' if api.offt_hip_half_box_pruned(po) else 'fallback'}]"
+            print(f"multi: {tag}: multi [{'fused' if fusedk else 'generic'}] min {mn['multi'] * 1e3:.3f} ms median {md['multi'] * 1e3:.3f} ms  "
+                  f"three calls [{'fused' if fused1 else 'unfused'}] min {mn['three'] * 1e3:.3f} ms median {md['three'] * 1e3:.3f} ms  "
+                  f"multi/three min {mn['multi'] / mn['three']:.3f} median {md['multi'] / md['three']:.3f}  "
+                  f"three-calls spread {md['three'] / mn['three'] - 1:.3f}  byte model (complex, full lines) {byte_model:.3f}  "
+                  f"n {MIXED_REPS}  zgroup_mib {L.offt_hip_get_option(po, OPT_ZGROUP_MIB)}", flush=True)
+            api.offt_3d_fin(po)
+            del dev, H, Hs, outs, spec_v, hv
+            torch.cuda.empty_cache()
+            continue
         if mixed:
             # the same plan and buffers, the option alternating between 1 and 0 (set outside the timed region)
             if half:
