@@ -86,8 +86,8 @@ int offt_hip_convolve_fused(const struct _offt_plan *po);
  * itself (at most one may be) -- that output is computed last and `data` holds it.  Every other outs[k] is a device buffer of
  * its own of offt_hip_local_bytes(po) bytes that overlaps neither `data` nor another output.  The output scale applies once
  * per output; stream, async, half box, OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_ZGROUP_MIB are honoured as in the
- * single-output call (a mixed-radix x extent takes the generic route here: forward, then a multiply and an inverse per
- * output).  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and offt_hip_last_error() for nout < 1 or
+ * single-output call (a mixed-radix x extent takes the generic route here -- forward, then a multiply and an inverse per
+ * output -- unless OFFT_HIP_OPT_CONV_MULTI_MIXED is set as well).  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and offt_hip_last_error() for nout < 1 or
  * nout > OFFT_HIP_CONV_MAX_OUT, a NULL or host-memory outs[k] or filters[k], two equal outs entries, an unknown
  * filter_kind, host-memory data, a failed communicator.  With nout == 1 and outs[0] == data the call IS
  * offt_hip_execute_convolve: the same bits.  offt_hip_last_device_seconds covers the whole call;
@@ -97,7 +97,8 @@ int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout,
                                     int filter_kind);
 /* 1 if outputs other than `data` run the fused multi-output route: the forward's z and y passes once, then per output one
  * out-of-place launch (forward x pass . filter . inverse x pass, data -> outs[k]) and the inverse's y and z passes -- one
- * rank, the default z-y-x layout, an x extent that is a power of two from 64 to 1024; 0: the generic route */
+ * rank, the default z-y-x layout, an x extent that is a power of two from 64 to 1024 or, with OFFT_HIP_OPT_CONV_MIXED and
+ * OFFT_HIP_OPT_CONV_MULTI_MIXED both set, one of the mixed-radix lengths listed there; 0: the generic route */
 int offt_hip_convolve_multi_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
@@ -161,6 +162,13 @@ int offt_hip_wait(struct _offt_plan *po);
                                           rows included; 0 (default) = such a plan always clears and runs the ordinary schedule, whatever
                                           the other two say.  Neither of those changes its meaning.  Set before or after
                                           offt_hip_set_half_box, like them (OFFT_HALF_R2C_MIXED) */
+#define OFFT_HIP_OPT_CONV_MULTI_MIXED 14 /* multi-output convolve on a plan whose x extent is no power of two: 1 = together with
+                                          OFFT_HIP_OPT_CONV_MIXED (both set) the fused multi-output route where that extent has an
+                                          out-of-place fused mixed-radix kernel (the lengths listed at OFFT_HIP_OPT_CONV_MIXED; complex
+                                          and r2c plans, one rank, the z-y-x layout; with OFFT_HIP_OPT_HALF_MIXED also a pruned half
+                                          box), 0 (default) = one forward, then a multiply and an inverse per output.  Alone it changes
+                                          nothing.  Read by every multi-output convolve; the results agree to rounding
+                                          (OFFT_CONV_MULTI_MIXED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -134,9 +134,12 @@ int offt_hipk_has_half(const offt_pass_desc *d);
 #define OFFT_FILTER_COMPLEX 1
 typedef struct offt_filter_desc {
   int kind;
-  /* 1 = a line length without a power-of-two fused kernel may run on the mixed-radix fused kernels (fft_conv_panelx_k,
-   * fft_conv_half_panelx_k: 96, 192, 320, 384, 640, 768, 1000 points in double and 384, 640, 768, 1000 in single precision),
-   * 0 = such a length has no fused kernel (plan option OFFT_HIP_OPT_CONV_MIXED) */
+  /* a bit set.  Bit 1 (value 1) = a line length without a power-of-two fused kernel may run on the mixed-radix fused kernels
+   * (fft_conv_panelx_k, fft_conv_half_panelx_k: 96, 192, 320, 384, 640, 768, 1000 points in double and 384, 640, 768, 1000 in
+   * single precision), 0 = such a length has no fused kernel (plan option OFFT_HIP_OPT_CONV_MIXED).  Bit 2 (value 2) = such a
+   * length may run the out-of-place kernel too (fft_conv_oop_panelx_k, fft_conv_oop_half_panelx_k, the same lengths;
+   * offt_hipk_conv_pass_oop; plan option OFFT_HIP_OPT_CONV_MULTI_MIXED): it counts only together with bit 1 (mixed = 3), and
+   * the in-place launch does not look at it.  A power-of-two length resolves to the same kernel whatever the field says. */
   int mixed;
   long long axis_stride, col_stride, b1_stride, b2_stride;
 } offt_filter_desc;
@@ -168,13 +171,16 @@ int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind,
  * they loaded, so that a spectrum can stay where it is while several filters are applied to it ----
  * offt_hipk_conv_pass with a separate destination: the lines of `src` (fwd's in_* addressing) convolved into `dst` at the
  * same offsets; `src` is not written.  fwd->half: 0 or 3, as there; fwd->out_keep: the cache-keeping twin (every instance
- * has one, the half-line ones too).  Power-of-two lines of 64 ... 1024 points only: f->mixed finds no kernel here.
+ * has one, the half-line ones too).  Power-of-two lines of 64 ... 1024 points; with bits 1 and 2 of f->mixed both set
+ * (f->mixed = 3) also the mixed-radix lengths listed at offt_filter_desc::mixed, whose instances have no cache-keeping twin
+ * (fwd->out_keep is ignored there, as by offt_hipk_conv_pass); with f->mixed 0, 1 or 2 such a length finds no kernel.
  * -1 if no such kernel exists, and for src == dst (that is offt_hipk_conv_pass). */
 int offt_hipk_conv_pass_oop(const offt_pass_desc *fwd, const offt_filter_desc *f, const void *filter, const void *src, void *dst,
                             void *stream);
 /* 1 if offt_hipk_conv_pass_oop has a kernel for (fwd, f); the registry lookup needs no device */
 int offt_hipk_conv_has_fused_oop(const offt_pass_desc *fwd, const offt_filter_desc *f);
-/* "fft_conv_oop_panel_k", "fft_conv_oop_half_panel_k" (fwd->half = 3) or "no fused kernel" */
+/* "fft_conv_oop_panel_k", "fft_conv_oop_half_panel_k" (fwd->half = 3), with f->mixed = 3 at a mixed-radix length
+ * "fft_conv_oop_panelx_k", "fft_conv_oop_half_panelx_k" (fwd->half = 3), or "no fused kernel" */
 const char *offt_hipk_conv_oop_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f);
 /* out[i0 s0 + i1 s1 + i2 s2] = in[same] * H[same] over the box n0 x n1 x n2: offt_hipk_pointwise with a separate destination
  * (in != out; `in` is not written).  Non-temporal, 16 B per lane along the smallest stride. */

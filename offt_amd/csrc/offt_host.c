@@ -446,6 +446,8 @@ typedef struct hip_state {
                             its passes may skip the padding (half_can_prune), and a mixed-radix Nz puts bit 4 on the real z passes */
     int conv_mixed;      /* convolve: 1 = the fused launch may run on the mixed-radix kernels (offt_filter_desc::mixed), 0 = a
                             length that is no power of two takes the unfused route */
+    int conv_multi_mixed; /* multi-output convolve: 1 = together with conv_mixed the out-of-place fused launch may run on the
+                            mixed-radix kernels too (bit 2 of offt_filter_desc::mixed), 0 = such a length takes the generic route */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -1147,6 +1149,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.half_mixed = getenv("OFFT_HALF_MIXED") && atoi(getenv("OFFT_HALF_MIXED")) != 0;
   st->opt.half_r2c_mixed = getenv("OFFT_HALF_R2C_MIXED") && atoi(getenv("OFFT_HALF_R2C_MIXED")) != 0;
   st->opt.conv_mixed = getenv("OFFT_CONV_MIXED") && atoi(getenv("OFFT_CONV_MIXED")) != 0;
+  st->opt.conv_multi_mixed = getenv("OFFT_CONV_MULTI_MIXED") && atoi(getenv("OFFT_CONV_MULTI_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
   st->opt.block_pad = getenv("OFFT_BLOCK_PAD") && atoi(getenv("OFFT_BLOCK_PAD")) != 0;
@@ -1626,6 +1629,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
       if (st->half_box) st->half_pruned = half_can_prune(po);
       break;
     case OFFT_HIP_OPT_CONV_MIXED: st->opt.conv_mixed = value != 0; break; /* read by every convolve (conv_fused_route) */
+    case OFFT_HIP_OPT_CONV_MULTI_MIXED: st->opt.conv_multi_mixed = value != 0; break; /* read by every multi-output convolve (conv_multi_fused_route) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
@@ -1664,6 +1668,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_HALF_MIXED: return st->opt.half_mixed;
     case OFFT_HIP_OPT_HALF_R2C_MIXED: return st->opt.half_r2c_mixed;
     case OFFT_HIP_OPT_CONV_MIXED: return st->opt.conv_mixed;
+    case OFFT_HIP_OPT_CONV_MULTI_MIXED: return st->opt.conv_multi_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
     case OFFT_HIP_OPT_P2P_TIMEOUT_S: return (long long)st->opt.p2p_timeout_s;
@@ -3116,13 +3121,15 @@ int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *fil
 /* multi-output spectral convolution: one forward, several filters             */
 /* ------------------------------------------------------------------------- */
 /* The fused multi-output route: one rank, the z-y-x layout, the conditions of conv_fused_route, and a backend and a kernel
- * for the out-of-place fused launch (powers of two from 64 to 1024: a mixed-radix x extent has none, whatever
- * OFFT_HIP_OPT_CONV_MIXED says).  Fills what conv_fused_route fills. */
+ * for the out-of-place fused launch: powers of two from 64 to 1024, and a mixed-radix x extent that has a fused kernel where
+ * OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_MULTI_MIXED are BOTH set (bits 1 and 2 of offt_filter_desc::mixed; the
+ * in-place launch of an output that is `data` reads bit 1 alone).  Fills what conv_fused_route fills. */
 static int conv_multi_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, offt_pass_desc *fd,
                                   offt_filter_desc *fl) {
   hip_state *st = (hip_state *)po->hip_state;
   if (!fw->zyx || !st->be->conv_pass_oop) return 0;
   if (!conv_fused_route(po, fw, iv, kind, fd, fl)) return 0;
+  if (st->opt.conv_mixed && st->opt.conv_multi_mixed) fl->mixed |= 2;
   return offt_hipk_conv_has_fused_oop(fd, fl);
 }
 

@@ -505,6 +505,8 @@ void build_registry() {
   reg_conv_oop_f32();
   reg_conv_mixed_f64();
   reg_conv_mixed_f32();
+  reg_conv_oop_mixed_f64();
+  reg_conv_oop_mixed_f32();
   reg_half_f64();
   reg_half_f32();
   reg_half_real_f64();
@@ -1836,8 +1838,9 @@ int offt_hipk_flag_wait(int n, unsigned long long *const *addr, unsigned long lo
 // ---- spectral convolution (offt_hipk.h) ----
 namespace {
 // the fused instance for (fwd, f), or nullptr: contiguous complex lines without a split, a unit-stride filter axis.  The
-// mixed-radix instances (fft_conv_panelx_k; lengths that have no power-of-two instance) only with f->mixed.
-// oop: the out-of-place instances (fft_conv_oop_panel_k): the power-of-two lengths only, each with a cache-keeping twin, half lines included.
+// mixed-radix instances (fft_conv_panelx_k; lengths that have no power-of-two instance) only with bit 1 of f->mixed.
+// oop: the out-of-place instances (fft_conv_oop_panel_k): the power-of-two lengths, each with a cache-keeping twin, half
+// lines included, and the mixed-radix ones (fft_conv_oop_panelx_k, no keeping twin) only with bits 1 and 2 of f->mixed.
 Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep, bool oop = false) {
   if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
   if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
@@ -1846,7 +1849,7 @@ Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep
   if (d->half && d->half != 3) return nullptr;  // half lines: loads and stores together, or not at all
   if (d->half && keep && !oop) return nullptr;  // (no cache-keeping twin of the in-place half-line kernels)
   Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true, d->half, oop);
-  if (v && v->mixed && (!f->mixed || oop)) return nullptr;
+  if (v && v->mixed && (oop ? (f->mixed & 3) != 3 : !f->mixed)) return nullptr;
   return v && v->conv && v->oop == oop && v->keep == keep && v->half == d->half ? v : nullptr;
 }
 }  // namespace
@@ -1881,6 +1884,7 @@ int offt_hipk_conv_has_fused_oop(const offt_pass_desc *fwd, const offt_filter_de
 const char *offt_hipk_conv_oop_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
   const Variant *v = pick_conv(fwd, f, false, true);
   if (!v) return "no fused kernel";
+  if (v->mixed) return fwd->half ? "fft_conv_oop_half_panelx_k" : "fft_conv_oop_panelx_k";
   return fwd->half ? "fft_conv_oop_half_panel_k" : "fft_conv_oop_panel_k";
 }
 

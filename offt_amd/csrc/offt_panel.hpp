@@ -1345,9 +1345,12 @@ fft_half_c2r_panelx_k(PassArgs a, const typename vec2<T>::type *in, typename vec
 //        half is wanted coming out; a load index q + t N/R0 is in the upper half exactly when 2t >= R0 and a store index
 //        q + t N/RL exactly when 2t >= RL (see panelx_body), so neither is compiled.  The filter and everything between the
 //        two is the full line.
+// The lines are loaded from `data` and stored at the same offsets from `dst` (as in conv_body): the in-place kernels pass
+// one pointer twice, the out-of-place ones (fft_conv_oop_panelx_k, offt_hipk_conv_pass_oop) a second volume, and never
+// write the first.
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT, bool HALF = false>
-__device__ __forceinline__ void convx_body(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter,
-                                           const typename vec2<T>::type *twt) {
+__device__ __forceinline__ void convx_body(PassArgs a, ConvArgs f, const typename vec2<T>::type *data, typename vec2<T>::type *dst,
+                                           const void *filter, const typename vec2<T>::type *twt) {
   using V2 = typename vec2<T>::type;
   using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
   constexpr int NT = Cfg::NT, NSTAGE = Cfg::NSTAGE, LSTRIDE = Cfg::LSTRIDE, EMAX = Cfg::EMAX;
@@ -1383,7 +1386,9 @@ __device__ __forceinline__ void convx_body(PassArgs a, ConvArgs f, typename vec2
   const int c0 = cp * COLS;
   const int j = tid % TPL, c = tid / TPL;
   const bool valid = (c0 + c) < a.ncols;
-  V2 *line = data + (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col;
+  const long long lo = (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col;
+  const V2 *line = data + lo;
+  V2 *sline = dst + lo;
   const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col;
   // butterfly u of a stage with NBF butterflies per line is live for this thread (compile-time true but for the last one)
   auto live0 = [&](int u) { return (u + 1) * TPL <= NBF0 || j + u * TPL < NBF0; };
@@ -1570,7 +1575,7 @@ __device__ __forceinline__ void convx_body(PassArgs a, ConvArgs f, typename vec2
     V2 w;
     w.x = x.x * sc;
     w.y = -x.y * sc;
-    if (valid && liveL(u)) gstore(line + (long long)n * a.in_axis, w);
+    if (valid && liveL(u)) gstore(sline + (long long)n * a.in_axis, w);
   });
 }
 
@@ -1581,13 +1586,29 @@ constexpr int convx_wps() { return PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
 __global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
 fft_conv_panelx_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twt) {
-  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT>(a, f, data, filter, twt);
+  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT>(a, f, data, data, filter, twt);
 }
 
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
 __global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
 fft_conv_half_panelx_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twt) {
-  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, data, filter, twt);
+  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, data, data, filter, twt);
+}
+
+// out of place (offt_hipk_conv_pass_oop with both bits of offt_filter_desc::mixed): the lines of `src` convolved into `dst`
+// at the same offsets, `src` left as it was.  Kernels of their own names: the in-place symbols above stay what they were.
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_oop_panelx_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst, const void *filter,
+                      const typename vec2<T>::type *twt) {
+  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT>(a, f, src, dst, filter, twt);
+}
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_oop_half_panelx_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst, const void *filter,
+                           const typename vec2<T>::type *twt) {
+  convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, src, dst, filter, twt);
 }
 
 // ---------------------------------------------------------------------------
@@ -1611,7 +1632,7 @@ struct Variant {
   bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
   bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
   bool conv = false;  // fft_conv_panel_k / fft_conv_panelx_k (mixed) instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
-  bool oop = false;   // fft_conv_oop_panel_k / fft_conv_oop_half_panel_k instance (offt_hipk_conv_pass_oop): conv with a separate store base
+  bool oop = false;   // fft_conv_oop_panel_k / fft_conv_oop_half_panel_k / fft_conv_oop_panelx_k / fft_conv_oop_half_panelx_k (mixed) instance (offt_hipk_conv_pass_oop): conv with a separate store base
   int half = 0;       // fft_half_panel_k / fft_half_panelx_k / fft_conv_half_panel_k / fft_conv_half_panelx_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
                       // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2), and with mixed their panelx twins
 };
@@ -1909,6 +1930,26 @@ void reg_variantx_conv_half() {
   registry().back().half = 3;
 }
 
+// ... and out of place (fft_conv_oop_panelx_k, fft_conv_oop_half_panelx_k; offt_reg_conv_oop_mixed_*.hip; picked only with
+// both bits of offt_filter_desc::mixed): the shapes of reg_variantx_conv, full lines and half lines, no cache-keeping twin
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variantx_conv_oop() {
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  auto add = [&](int half, const void *fn) {
+    char nm[192];
+    snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s out-of-place convolution%s lds=%zuB",
+             prec ? "f32" : "f64", N, R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", half ? " on half lines" : "",
+             (size_t)Cfg::LDS_BYTES);
+    registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES, fn, nm, false, true, false, nullptr});
+    registry().back().conv = true;
+    registry().back().oop = true;
+    registry().back().half = half;
+  };
+  add(0, (const void *)fft_conv_oop_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>);
+  add(3, (const void *)fft_conv_oop_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>);
+}
+
 // instantiation groups (offt_reg_*.hip)
 void reg_pow2_f64();
 void reg_pow2_f64_1024();
@@ -1931,6 +1972,8 @@ void reg_conv_oop_f64();
 void reg_conv_oop_f32();
 void reg_conv_mixed_f64();
 void reg_conv_mixed_f32();
+void reg_conv_oop_mixed_f64();
+void reg_conv_oop_mixed_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();

@@ -16,9 +16,17 @@ the third in `data`) against three offt_hip_execute_convolve calls on the same p
 is the baseline.  The two ALTERNATE after a warm-up, MIXED_REPS times each, and the line reports min and median of both,
 their ratios, the baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5.  multi:half:N does so on a
 pruned half-box plan (an N/2 box).
-usage: conv_probe.py [mixed:|multi:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+A spec with the prefix multi:mixed: measures OFFT_HIP_OPT_CONV_MULTI_MIXED (the fused multi-output route at x lengths that
+are no powers of two), with OFFT_HIP_OPT_CONV_MIXED on throughout: the multi call with the option at 1 ALTERNATES with three
+offt_hip_execute_convolve calls and with the multi call with the option at 0 (the generic route: the code of before the
+option existed), MIXED_REPS times each after a warm-up.  The line reports min and median of all three, the ratios against
+both baselines, each baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5 (376 / 504 for K = 3,
+against either baseline).  multi:mixed:half:N does so on a pruned half-box plan (OFFT_HIP_OPT_HALF_MIXED, an N/2 box).
+usage: conv_probe.py [mixed:|multi:|multi:mixed:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
        (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768;
-        the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512)"""
+        the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512;
+        the multi:mixed: set of profiles/conv_multi_mixed.txt: multi:mixed:768 multi:mixed:f32:768 multi:mixed:1000
+        multi:mixed:f32:1000 multi:mixed:half:768)"""
 import ctypes as C
 import os
 import sys
@@ -62,8 +70,10 @@ def main():
     for spec in specs:
         multi = spec.startswith("multi:")
         mixed = spec.startswith("mixed:") or multi  # (the same grammar behind the prefix)
-        half = mixed and spec[6:].startswith("half:")
-        kind, _, n_s = spec[(6 if mixed else 0) + (5 if half else 0):].rpartition(":")
+        multi_mixed = multi and spec[6:].startswith("mixed:")
+        rest = spec[(6 if mixed else 0) + (6 if multi_mixed else 0):]
+        half = mixed and rest.startswith("half:")
+        kind, _, n_s = rest[(5 if half else 0):].rpartition(":")
         n = int(n_s)
         prec = api.F32 if kind == "f32" else api.F64
         r2c = kind == "r2c"
@@ -106,6 +116,10 @@ def main():
 
         if multi:
             K = 3
+            if multi_mixed:
+                L.offt_hip_set_option(po, api.OPT_CONV_MIXED, 1)
+                if half:
+                    L.offt_hip_set_option(po, api.OPT_HALF_MIXED, 1)
             if half:
                 api.offt_hip_set_half_box(po, True)
             Hs = [H] + [torch.rand(api.local_elems(po), dtype=td, device="cuda") * (1.0 / float(n) ** 3) for _ in range(K - 1)]
@@ -119,6 +133,38 @@ def main():
                 for h_ in Hs:
                     api.offt_hip_execute_convolve(po, dev.data_ptr(), h_.data_ptr(), api.FILTER_REAL)
 
+            if multi_mixed:
+                # the same plan and buffers; the option is set outside the timed region
+                def opt(v):
+                    L.offt_hip_set_option(po, api.OPT_CONV_MULTI_MIXED, v)
+
+                t = {"on": [], "three": [], "off": []}
+                route = {}
+                for rep_i in range(2 + MIXED_REPS):
+                    for name, fn, v in (("on", mv, 1), ("three", three, 1), ("off", mv, 0)):
+                        opt(v)
+                        route[name] = api.offt_hip_convolve_multi_fused(po)
+                        dt = run(fn)
+                        if rep_i >= 2:
+                            t[name].append(dt)
+                opt(0)
+                mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+                fused1 = api.offt_hip_convolve_fused(po)
+                tag = f"{'r2c f64' if r2c else ('f32' if prec == api.F32 else 'f64')} {n}^3 K={K}"
+                if half:
+                    tag += f" half box {n // 2}^3 [{'pruned' if api.offt_hip_half_box_pruned(po) else 'fallback'}]"
+                print(f"multi:mixed: {tag}: option 1 [{'fused' if route['on'] else 'generic'}] min {mn['on'] * 1e3:.3f} ms median {md['on'] * 1e3:.3f} ms  "
+                      f"three calls [{'fused' if fused1 else 'unfused'}] min {mn['three'] * 1e3:.3f} ms median {md['three'] * 1e3:.3f} ms  "
+                      f"option 0 [{'fused' if route['off'] else 'generic'}] min {mn['off'] * 1e3:.3f} ms median {md['off'] * 1e3:.3f} ms  "
+                      f"1/three min {mn['on'] / mn['three']:.3f} median {md['on'] / md['three']:.3f}  "
+                      f"1/0 min {mn['on'] / mn['off']:.3f} median {md['on'] / md['off']:.3f}  "
+                      f"three-calls spread {md['three'] / mn['three'] - 1:.3f}  option-0 spread {md['off'] / mn['off'] - 1:.3f}  "
+                      f"byte model (complex, full lines) {(8 + 13 * K) / (21.0 * K):.3f}  n {MIXED_REPS}  "
+                      f"zgroup_mib {L.offt_hip_get_option(po, OPT_ZGROUP_MIB)}", flush=True)
+                api.offt_3d_fin(po)
+                del dev, H, Hs, outs, spec_v, hv
+                torch.cuda.empty_cache()
+                continue
             t = {"multi": [], "three": []}
             for rep_i in range(2 + MIXED_REPS):
                 for name, fn in (("multi", mv), ("three", three)):
