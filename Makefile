@@ -98,6 +98,21 @@ else
 	$(CC) -std=gnu11 -O2 -Wall -Iinclude -o $@ harness/run-fft.c -Lofft_amd -loffthip -L$(ROCM)/lib -lamdhip64 -lm -Wl,-rpath,'$$ORIGIN/../offt_amd' -Wl,-rpath,$(ROCM)/lib
 endif
 
+# the registry queries of offt_hipk.h under AddressSanitizer + UBSan in a stand-alone program (tools/registry_dump.cpp): the
+# HOST side of every kernel source is compiled again with the sanitizers around the device code of the product object; the
+# program launches nothing and needs no GPU.  Its output is kept for comparing two builds.
+ASANREG   := $(BUILD)/asan_registry
+$(ASANREG)/%.o: $(CSRC)/%.hip $(BUILD)/%.o
+	mkdir -p $(ASANREG)
+	$(ROCM)/lib/llvm/bin/llvm-objcopy --dump-section .hip_fatbin=$(ASANREG)/$*.fatbin $(BUILD)/$*.o
+	$(HIPCC) --offload-arch=$(ARCH) --cuda-host-only -Xclang -fcuda-include-gpubinary -Xclang $(ASANREG)/$*.fatbin -O1 -g -std=c++17 \
+	  -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -I$(CSRC) -Iinclude -I$(BUILD) -c $< -o $@
+asan-registry: $(HIPSRC:%=$(ASANREG)/%.o) tools/registry_dump.cpp
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -fsanitize=address,undefined -I$(CSRC) tools/registry_dump.cpp $(HIPSRC:%=$(ASANREG)/%.o) -o $(ASANREG)/registry_dump \
+	  -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib -ldl -lpthread
+	$(ASANREG)/registry_dump > $(ASANREG)/registry_dump.txt
+	@echo "asan-registry: clean, `wc -l < $(ASANREG)/registry_dump.txt` answers in $(ASANREG)/registry_dump.txt"
+
 # host logic under AddressSanitizer + UBSan on the CPU test backend (GPU ASan is not available on the pool)
 asan-test: $(HIPOBJ)
 	mkdir -p $(BUILD)/asan

@@ -519,28 +519,24 @@ void build_registry() {
 #endif
 }
 
-// (n, precision, flavour) -> registry entries, rebuilt when the registry has grown (plan-time instances): a launch must
-// not scan several hundred variants
+// VariantKey -> registry entries, rebuilt when the registry has grown (plan-time instances): a launch must not scan
+// several hundred variants
 std::mutex g_idx_mu;
-std::unordered_map<unsigned long long, std::vector<int>> g_idx;
+std::unordered_map<VariantKey, std::vector<int>, VariantKeyHash> g_idx;
 size_t g_idx_size = 0;
-unsigned long long variant_key(int n, int prec, bool inc, bool outc, bool r2c, bool keep = false, bool tw4 = false, bool c2r = false,
-                               bool conv = false, int half = 0, bool oop = false) {
-  return ((unsigned long long)n << 12) | (oop ? 2048u : 0u) | ((unsigned long long)(half & 3) << 9) | (conv ? 256u : 0u) | (c2r ? 128u : 0u) | (tw4 ? 64u : 0u) | (keep ? 32u : 0u) | ((unsigned long long)prec << 3) | (inc ? 4u : 0u) | (outc ? 2u : 0u) | (r2c ? 1u : 0u);
-}
 
-Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = false, bool keep = false, bool tw4 = false, bool c2r = false,
-                      bool conv = false, int half = 0, bool oop = false) {
+// the entry of `key` with this id, else the key's default, else nullptr.  The key is compared whole: what comes back IS
+// that kernel, and a caller checks only what is not part of the key (id, is_default, mixed)
+Variant *find_variant(const VariantKey &key, int id = -1) {
   std::call_once(g_reg_once, build_registry);
   std::lock_guard<std::mutex> lk(g_idx_mu);
   auto &reg = registry();
   if (g_idx_size != reg.size()) {
     g_idx.clear();
-    for (size_t i = 0; i < reg.size(); ++i)
-      g_idx[variant_key(reg[i].n, reg[i].prec, reg[i].inc, reg[i].outc, reg[i].r2c, reg[i].keep, reg[i].tw4, reg[i].c2r, reg[i].conv, reg[i].half, reg[i].oop)].push_back((int)i);
+    for (size_t i = 0; i < reg.size(); ++i) g_idx[reg[i].key].push_back((int)i);
     g_idx_size = reg.size();
   }
-  auto it = g_idx.find(variant_key(n, prec, inc, outc, r2c, keep, tw4, c2r, conv, half, oop));
+  auto it = g_idx.find(key);
   if (it == g_idx.end()) return nullptr;
   Variant *def = nullptr;
   for (int i : it->second) {
@@ -550,6 +546,9 @@ Variant *find_variant(int n, int prec, bool inc, bool outc, int id, bool r2c = f
   }
   return def;
 }
+// the keys most lookups ask for: the plain full-line kernel of a flavour, and the four-step twin of a short first factor
+VariantKey plain_key(int n, int prec, bool inc, bool outc) { return VariantKey{n, prec, inc, outc, Role::Plain, false, 0}; }
+Variant *find_tw4(int n, int prec) { return find_variant(VariantKey{n, prec, false, false, Role::TW4, false, 0}); }
 
 // ---------------------------------------------------------------------------
 // Plan-time specialisation.  A length without a precompiled panel kernel whose prime factors are <= 31 gets
@@ -691,7 +690,7 @@ bool choose_shapes(int N, int prec, int want, std::vector<Shape> *out) {
 // of the default shape instead (the complex instances exist already)
 int rtc_build(int n, int prec, bool c2r = false) {
   std::lock_guard<std::mutex> lk(g_rtc_mu);
-  if (find_variant(n, prec, true, true, -1, false, false, false, c2r)) return 0;  // somebody was faster
+  if (find_variant(VariantKey{n, prec, true, true, c2r ? Role::C2R : Role::Plain, false, 0})) return 0;  // somebody was faster
   static bool warned = false;
   auto fail = [&](const char *what, const std::string &detail) {
     if (!warned) fprintf(stderr, "offt(hip): no plan-time kernel for n=%d (%s%s%s); using the any-length kernel\n", n, what,
@@ -764,12 +763,10 @@ int rtc_build(int n, int prec, bool c2r = false) {
   for (size_t e = 0; e < inst.size(); ++e) {
     const Shape &sh = shapes[inst[e].shape];
     const bool *fl = flav[inst[e].f];
-    char nm[200];
-    snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d split-re/im lds=%zuB [plan-time hipRTC]",
-             prec ? "f32" : "f64", n, sh.r0, sh.r1, sh.r2, sh.tpl, sh.emax, sh.cols, sh.lds);
-    registry().push_back(Variant{n, prec, fl[0], fl[1], inst[e].shape, inst[e].shape == 0, fl[2], sh.cols, sh.tpl * sh.cols, sh.emax, sh.lds,
-                                 nullptr, nm, false, true, n % 4 != 0, (void *)fn[e]});
-    registry().back().c2r = fl[3];
+    const Role role = fl[3] ? Role::C2R : fl[2] ? Role::R2C : Role::Plain;
+    add_variant(VariantKey{n, prec, fl[0], fl[1], role, false, 0},
+                VariantShape{sh.cols, sh.tpl * sh.cols, sh.emax, sh.lds, true, n % 4 != 0, sh.r0, sh.r1, sh.r2, sh.tpl, layout_name(true)}, nullptr,
+                fl[3] ? "fft_c2r_panelx_k" : "fft_panelx_k", "", inst[e].shape, inst[e].shape == 0, (void *)fn[e]);
   }
   return 0;
 }
@@ -868,7 +865,7 @@ bool blue_lookup(int n, int prec, BlueTab *out) {
 size_t elem_size(int prec) { return prec == OFFT_PREC_F64 ? sizeof(double2) : sizeof(float2); }
 // two images of a line fit the LDS of the any-length kernel (5120 double / 10240 single points)
 bool fits_any_length(int n, int prec) { return 2 * (size_t)n * elem_size(prec) <= LDS_BYTES; }
-bool has_panel(int n, int prec) { return find_variant(n, prec, true, true, -1) != nullptr; }
+bool has_panel(int n, int prec) { return find_variant(plain_key(n, prec, true, true)) != nullptr; }
 int max_prime_factor(int n) {
   int maxp = 1;
   for (int p = 2; p * p <= n; ++p) while (n % p == 0) { maxp = p > maxp ? p : maxp; n /= p; }
@@ -888,11 +885,12 @@ bool blue_panel_candidate(int n, int prec, bool inc, bool outc) {
 int blue_m_long(int n, int prec) {
   const long long need = 2LL * n - 1;
   const int n1 = prec == OFFT_PREC_F64 ? 64 : 32;
-  if (!find_variant(n1, prec, false, false, -1, false, false, true)) return 0;
+  if (!find_tw4(n1, prec)) return 0;
   long long best = 0;
   for (auto &v : registry()) {
-    if (v.prec != prec || !v.inc || !v.outc || v.r2c || v.c2r || v.tw4 || v.conv || v.id != 0 || v.n < 64 || v.n > 4096) continue;
-    const long long m = (long long)n1 * v.n;
+    const VariantKey &k = v.key;
+    if (k.prec != prec || !k.inc || !k.outc || k.role != Role::Plain || v.id != 0 || k.n < 64 || k.n > 4096) continue;
+    const long long m = (long long)n1 * k.n;
     if (m >= need && m < (1LL << 24) && (!best || m < best)) best = m;
   }
   return best && best < blue_m(n) ? (int)best : 0;
@@ -967,16 +965,17 @@ Variant *pick_variant0(const offt_pass_desc *d, bool allow_pair) {
   int want = d->variant;
   if (want >= VARIANT_PAIR0 || (want < 0 && env().f32_pairs && !d->no_pairs)) {
     if (allow_pair && !uneven && !odd_split && pair_ok(d)) {
-      Variant *p = find_variant(d->n, OFFT_PREC_F32_PAIR, inc, outc, want < 0 ? -1 : want - VARIANT_PAIR0);
+      Variant *p = find_variant(plain_key(d->n, OFFT_PREC_F32_PAIR, inc, outc), want < 0 ? -1 : want - VARIANT_PAIR0);
       if (p && (want >= 0 ? p->id == want - VARIANT_PAIR0 : p->is_default)) return p;
     }
     if (want >= VARIANT_PAIR0) want = -1;
   }
-  Variant *v = find_variant(d->n, d->precision, inc, outc, r2c || c2r ? -1 : want, r2c, false, false, c2r);
+  const VariantKey key{d->n, d->precision, inc, outc, r2c ? Role::R2C : c2r ? Role::C2R : Role::Plain, false, 0};
+  Variant *v = find_variant(key, r2c || c2r ? -1 : want);
   if (!v) return nullptr;
   if (v->mixed || !(uneven || odd_split)) return v;
   // fft_panel_k addresses per-peer blocks with shifts: other block lengths go to the length's fft_panelx_k instance
-  Variant *w = find_variant(d->n, d->precision, inc, outc, VARIANT_ANYSPLIT, r2c, false, false, c2r);
+  Variant *w = find_variant(key, VARIANT_ANYSPLIT);
   return (w && w->id == VARIANT_ANYSPLIT) ? w : nullptr;
 }
 
@@ -985,12 +984,14 @@ Variant *pick_variant(const offt_pass_desc *d, bool allow_pair = true) {
   if (d->tw4) {  // first sub-pass of a four-step line: the strided / strided kernel with the twiddles on its stores, or nothing
     if (d->in_contig || d->out_contig || d->real_input || d->in_split_nfloor || d->out_split_nfloor) return nullptr;
     if ((d->in_split && !is_pow2(d->in_split)) || (d->out_split && !is_pow2(d->out_split))) return nullptr;
-    return find_variant(d->n, d->precision, false, false, -1, false, false, true);
+    return find_tw4(d->n, d->precision);
   }
   Variant *v = pick_variant0(d, allow_pair);
-  if (v && d->out_keep && env().keep_stores && !v->mixed && !v->r2c && !v->c2r) {
-    Variant *k = find_variant(v->n, v->prec, v->inc, v->outc, v->id, false, true);
-    if (k && k->keep && k->id == v->id) return k;
+  if (v && d->out_keep && env().keep_stores && !v->mixed && v->key.role == Role::Plain) {
+    VariantKey twin = v->key;
+    twin.keep = true;
+    Variant *k = find_variant(twin, v->id);
+    if (k && k->id == v->id) return k;
   }
   return v;
 }
@@ -1020,16 +1021,15 @@ Variant *pick_half(const offt_pass_desc *d, bool allow_pair = true) {
     const bool r2c = d->real_input == 1 && half == 1 && inc && !outc && d->in_axis_stride == 1 && d->direction <= 0;
     const bool c2r = d->real_input == 2 && half == 2 && !inc && outc && d->out_axis_stride == 1;
     if (!r2c && !c2r) return nullptr;
-    Variant *v = find_variant(d->n, d->precision, inc, outc, -1, r2c, false, false, c2r, false, half);
-    return v && v->half == half && v->r2c == r2c && v->c2r == c2r && (!v->mixed || real_mixed) ? v : nullptr;
+    Variant *v = find_variant(VariantKey{d->n, d->precision, inc, outc, r2c ? Role::R2C : Role::C2R, false, half});
+    return v && (!v->mixed || real_mixed) ? v : nullptr;
   }
   if (half == 1 ? !inc : !outc) return nullptr;
   if (allow_pair && env().f32_pairs && !d->no_pairs && pair_ok(d)) {
-    Variant *p = find_variant(d->n, OFFT_PREC_F32_PAIR, inc, outc, -1, false, false, false, false, false, half);
-    if (p && p->half == half) return p;
+    Variant *p = find_variant(VariantKey{d->n, OFFT_PREC_F32_PAIR, inc, outc, Role::Plain, false, half});
+    if (p) return p;
   }
-  Variant *v = find_variant(d->n, d->precision, inc, outc, -1, false, false, false, false, false, half);
-  return v && v->half == half && !v->conv ? v : nullptr;
+  return find_variant(VariantKey{d->n, d->precision, inc, outc, Role::Plain, false, half});
 }
 
 // 1 if the descriptor, with out_keep set, runs on a kernel whose stores stay cached (a KEEP twin exists for its shape)
@@ -1038,7 +1038,7 @@ extern "C" int offt_hipk_keeps_output(const offt_pass_desc *d) {
   offt_pass_desc k = *d;
   k.out_keep = 1;
   const Variant *v = pick_variant(&k);
-  return v && v->keep;
+  return v && v->key.keep;
 }
 
 // ---------------------------------------------------------------------------
@@ -1245,7 +1245,7 @@ struct Route {
 void resolve_direct(const offt_pass_desc *d, const void *in, const void *out, Route *r) {
   // 1. a panel kernel (column pairs, any-split instance, cache-keeping twin, plan-time instance: pick_variant)
   r->v = pick_variant(d);
-  if (r->v && r->v->prec == OFFT_PREC_F32_PAIR &&
+  if (r->v && r->v->key.prec == OFFT_PREC_F32_PAIR &&
       ((!d->in_contig && ((uintptr_t)in & 15)) || (!d->out_contig && ((uintptr_t)out & 15))))
     r->v = pick_variant(d, false);  // a strided side off the 16-B grid: the one-column kernels
   if (r->v) { r->via = Via::Panel; return; }
@@ -1365,7 +1365,7 @@ void by_precision(int prec, F &&f) { if (prec == OFFT_PREC_F64) f(double{}); els
   by_precision(prec, [&](auto t_) { using T = decltype(t_); using V2 = typename vec2<T>::type; (void)sizeof(V2); __VA_ARGS__; })
 
 int launch_panel(const offt_pass_desc *d, const void *in, void *out, const Tables &tb, hipStream_t st, Variant *v) {
-  if (d->tw4 && !v->tw4) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no kernel with four-step twiddles for n=%d", d->n); return -1; }
+  if (d->tw4 && v->key.role != Role::TW4) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no kernel with four-step twiddles for n=%d", d->n); return -1; }
   PassArgs a = pass_args(d, v->cols);
   // every panel kernel stages its twiddles from the exact full-wave table w^m, m < n (the quarter- and half-wave
   // tables they keep in LDS are prefixes of it)
@@ -1453,7 +1453,7 @@ int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, 
         // pass then leaves S'[k1][j2][c] as it is and C reads it with the caller's columns as its columns -- which needs a
         // strided-out pass as well; strided-in / contig-out keeps the transposing twiddle sweep.
         const bool fused = env().fourstep_fuse && (inL || !outL) && (!d->in_split || is_pow2(d->in_split / N2)) &&
-                           find_variant(N1, d->precision, false, false, -1, false, false, true) != nullptr;
+                           find_tw4(N1, d->precision) != nullptr;
         if (fused) { a.tw4 = fs.t4; a.tw4_b1 = inL ? 0 : 1; a.tw4_n2 = N2; }
         if (inL) {  // the axis is the unit-stride dimension: j2 becomes the column dimension
           a.ncols = N2; a.in_col_stride = d->in_axis_stride;
@@ -1597,7 +1597,7 @@ int choose_four_split(int n, int precision, bool fused_only) {
     // (third: a long factor with a prime factor > 13 that runs on the Bluestein panel kernel -- 4076 = 4 x 1019)
     const bool blue2 = !f2 && !rtc2 && blue_panel_candidate(n2, precision, true, false) && blue_panel_candidate(n2, precision, false, false);
     for (int r = 0; pref[r]; ++r)
-      if (n1 == pref[r] && (f2 || rtc2 || blue2) && find_variant(n1, precision, false, false, -1, false, false, true))
+      if (n1 == pref[r] && (f2 || rtc2 || blue2) && find_tw4(n1, precision))
         score = (f2 ? -10.0 : rtc2 ? -5.0 : -3.0) + 0.1 * r;
     // a factor that would itself go through scratch lines (or the any-length kernel with a radix of hundreds) is a last resort
     if (!f1 && max_prime_factor(n1) > 61 && !(n1 <= 2048 && env().bluestein)) score += 8.0;
@@ -1645,19 +1645,20 @@ int offt_hipk_has_fast_path(int n, int precision) { return has_panel(n, precisio
 
 int offt_hipk_variant_count(int n, int precision) {
   std::call_once(g_reg_once, build_registry);
+  const VariantKey key = plain_key(n, precision, true, true);
   int c = 0;
   for (auto &v : registry())
-    if (v.n == n && v.prec == precision && v.inc && v.outc && !v.r2c && !v.c2r && !v.conv && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
+    if (v.key == key && v.id < VARIANT_ANYSPLIT) c = v.id + 1 > c ? v.id + 1 : c;
   return c;
 }
 
 const char *offt_hipk_variant_name(int n, int precision, int variant) {
-  Variant *v = find_variant(n, precision, true, true, variant);
+  Variant *v = find_variant(plain_key(n, precision, true, true), variant);
   return v ? v->name.c_str() : "mixed-radix any-length";
 }
 
 int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thread, int *cols) {
-  Variant *v = find_variant(n, precision, true, true, variant);
+  Variant *v = find_variant(plain_key(n, precision, true, true), variant);
   if (!v || (variant >= 0 && v->id != variant)) return -1;
   if (elems_per_thread) *elems_per_thread = v->e;
   if (cols) *cols = v->cols;
@@ -1665,20 +1666,19 @@ int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thr
 }
 
 // the direct layer of resolve(): a pass that is decomposed (four-step, scratch lines) is named by what would launch it alone
+// A panel kernel's name is the registry's: every entry carries the __global__ template it was instantiated from
+// (Variant::kernel, "<pairs>" appended for the column-pair instances).  Only the two kernels outside that registry and
+// the refusal of a half-line descriptor are spelled here.
 const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
   if (d->half) {
     const Variant *h = pick_half(d);
-    if (h && (h->r2c || h->c2r) && h->mixed) return h->r2c ? "fft_half_r2c_panelx_k" : "fft_half_c2r_panelx_k";
-    if (h && (h->r2c || h->c2r)) return h->r2c ? "fft_half_r2c_panel_k" : "fft_half_c2r_panel_k";
-    if (h && h->mixed) return "fft_half_panelx_k";
-    return !h ? "no half-line kernel" : (h->prec == OFFT_PREC_F32_PAIR ? "fft_half_panel_k<pairs>" : "fft_half_panel_k");
+    return h ? h->kernel : "no half-line kernel";
   }
   Route r;
   resolve_direct(d, nullptr, nullptr, &r);
   if (r.via == Via::BluePanel) return "fft_bluestein_k";
   if (r.via == Via::AnyLength) return "fft_mixed_k";
-  if (r.v->c2r) return r.v->mixed ? "fft_c2r_panelx_k" : "fft_c2r_panel_k";
-  return r.v->mixed ? "fft_panelx_k" : (r.v->prec == OFFT_PREC_F32_PAIR ? "fft_panel_k<pairs>" : "fft_panel_k");
+  return r.v->kernel;
 }
 
 int offt_hipk_has_half(const offt_pass_desc *d) { return pick_half(d) != nullptr; }
@@ -1691,7 +1691,7 @@ int offt_hipk_prepare(int n, int precision) {
     if (offt_hipk_prepare(n, precision)) return -1;
     // real-output instances for a length whose panel kernel was compiled at plan time (the precompiled lengths have theirs);
     // best effort like the complex ones: without them the real-output pass runs on the any-length kernel
-    const Variant *v = find_variant(n, precision, true, true, -1);
+    const Variant *v = find_variant(plain_key(n, precision, true, true));
     if (v && v->modfn && env().rtc) (void)rtc_build(n, precision, true);
     return 0;
   }
@@ -1744,7 +1744,7 @@ int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void 
   if (d->half) {
     // half lines run on their own kernels or not at all: no other route knows the bits, and none may run the full line
     Variant *h = pick_half(d);
-    if (h && h->prec == OFFT_PREC_F32_PAIR && ((!d->in_contig && ((uintptr_t)in & 15)) || (!d->out_contig && ((uintptr_t)out & 15))))
+    if (h && h->key.prec == OFFT_PREC_F32_PAIR && ((!d->in_contig && ((uintptr_t)in & 15)) || (!d->out_contig && ((uintptr_t)out & 15))))
       h = pick_half(d, false);  // a strided side off the 16-B grid: the one-column kernel
     if (!h) {
       snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no half-line kernel for this descriptor (n=%d, half=%d, in_contig=%d, out_contig=%d)",
@@ -1848,54 +1848,22 @@ Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep
     return nullptr;
   if (d->half && d->half != 3) return nullptr;  // half lines: loads and stores together, or not at all
   if (d->half && keep && !oop) return nullptr;  // (no cache-keeping twin of the in-place half-line kernels)
-  Variant *v = find_variant(d->n, d->precision, true, true, -1, false, keep, false, false, true, d->half, oop);
+  Variant *v = find_variant(VariantKey{d->n, d->precision, true, true, oop ? Role::ConvOop : Role::Conv, keep, d->half});
   if (v && v->mixed && (oop ? (f->mixed & 3) != 3 : !f->mixed)) return nullptr;
-  return v && v->conv && v->oop == oop && v->keep == keep && v->half == d->half ? v : nullptr;
+  return v;
 }
-}  // namespace
+const char *conv_kernel_name(const Variant *v) { return v ? v->kernel : "no fused kernel"; }
 
-int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false) != nullptr; }
-
-const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
-  const Variant *v = pick_conv(fwd, f, false);
-  if (!v) return "no fused kernel";
-  if (v->mixed) return fwd->half ? "fft_conv_half_panelx_k" : "fft_conv_panelx_k";
-  return fwd->half ? "fft_conv_half_panel_k" : "fft_conv_panel_k";
-}
-
-int offt_hipk_conv_pass(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream) {
-  Variant *v = pick_conv(d, f, d && d->out_keep);
-  if (!v && d && d->out_keep) v = pick_conv(d, f, false);
-  if (!v) { snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass: no fused convolution kernel for this descriptor (n=%d)", d ? d->n : 0); return -1; }
-  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
-  Tables tb;
-  if (get_tables(d->n, d->precision, tb, false)) return -1;
-  PassArgs a = pass_args(d, v->cols, true);
-  ConvArgs fa;
-  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
-  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
-  void *args[] = {(void *)&a, (void *)&fa, (void *)&data, (void *)&filter, (void *)&tb.full};
-  return launch("offt_hipk_conv_pass", v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2,
-                &a.xcd_lim, &a.xcd_gshift, args, (hipStream_t)stream);
-}
-
-int offt_hipk_conv_has_fused_oop(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false, true) != nullptr; }
-
-const char *offt_hipk_conv_oop_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
-  const Variant *v = pick_conv(fwd, f, false, true);
-  if (!v) return "no fused kernel";
-  if (v->mixed) return fwd->half ? "fft_conv_oop_half_panelx_k" : "fft_conv_oop_panelx_k";
-  return fwd->half ? "fft_conv_oop_half_panel_k" : "fft_conv_oop_panel_k";
-}
-
-int offt_hipk_conv_pass_oop(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream) {
-  if (!src || !dst || src == dst) {
-    snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass_oop: needs two different arrays (src == dst is offt_hipk_conv_pass)");
+// offt_hipk_conv_pass (src == dst, oop = false) and offt_hipk_conv_pass_oop: the out-of-place kernels take (a, f, src, dst,
+// filter, twt), the in-place ones (a, f, data, filter, twt)
+int conv_launch(const char *who, const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, bool oop,
+                void *stream) {
+  Variant *v = pick_conv(d, f, d && d->out_keep, oop);
+  if (!v && d && d->out_keep) v = pick_conv(d, f, false, oop);
+  if (!v) {
+    snprintf(g_err, sizeof g_err, "%s: no %sfused convolution kernel for this descriptor (n=%d)", who, oop ? "out-of-place " : "", d ? d->n : 0);
     return -1;
   }
-  Variant *v = pick_conv(d, f, d && d->out_keep, true);
-  if (!v && d && d->out_keep) v = pick_conv(d, f, false, true);
-  if (!v) { snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass_oop: no out-of-place fused convolution kernel for this descriptor (n=%d)", d ? d->n : 0); return -1; }
   if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
   Tables tb;
   if (get_tables(d->n, d->precision, tb, false)) return -1;
@@ -1903,46 +1871,20 @@ int offt_hipk_conv_pass_oop(const offt_pass_desc *d, const offt_filter_desc *f, 
   ConvArgs fa;
   fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
   fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
-  void *args[] = {(void *)&a, (void *)&fa, (void *)&src, (void *)&dst, (void *)&filter, (void *)&tb.full};
-  return launch("offt_hipk_conv_pass_oop", v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2,
-                &a.xcd_lim, &a.xcd_gshift, args, (hipStream_t)stream);
+  void *args[6];
+  int na = 0;
+  args[na++] = (void *)&a; args[na++] = (void *)&fa;
+  if (oop) args[na++] = (void *)&src;
+  args[na++] = (void *)&dst; args[na++] = (void *)&filter; args[na++] = (void *)&tb.full;
+  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
+                args, (hipStream_t)stream);
 }
 
-int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0, long long s1,
-                        long long s2, void *stream) {
-  if (kind != OFFT_FILTER_REAL && kind != OFFT_FILTER_COMPLEX) { snprintf(g_err, sizeof g_err, "offt_hipk_pointwise: bad filter kind %d", kind); return -1; }
-  if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
-  // rows along the smallest stride
-  int n[3] = {n0, n1, n2};
-  long long st[3] = {s0, s1, s2};
-  for (int a = 0; a < 2; a++)
-    for (int b = 0; b < 2 - a; b++)
-      if (st[b] < st[b + 1]) { int tn = n[b]; n[b] = n[b + 1]; n[b + 1] = tn; long long ts = st[b]; st[b] = st[b + 1]; st[b + 1] = ts; }
-  const long long rows = (long long)n[0] * n[1];
-  const bool f32 = precision == OFFT_PREC_F32;
-  // two single-precision elements per lane: unit stride, whole pairs, 16-B aligned rows and bases
-  const bool pair = f32 && st[2] == 1 && !(n[2] & 1) && !(st[1] & 1) && !(st[0] & 1) && !((uintptr_t)data & 15) &&
-                    !((uintptr_t)filter & (kind == OFFT_FILTER_COMPLEX ? 15 : 7));
-  const int epl = pair ? 2 : 1;
-  const unsigned gx = (unsigned)((n[2] / epl + 255) / 256);
-  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
-  hipStream_t sm = (hipStream_t)stream;
-  (void)hipGetLastError();
-  const bool cx = kind == OFFT_FILTER_COMPLEX;
-#define POINTWISE(T, CPLX, EPL) \
-  hipLaunchKernelGGL((pointwise_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, (typename vec2<T>::type *)data, filter, n[1], n[2], st[0], st[1], st[2], rows)
-  if (pair) { if (cx) POINTWISE(float, true, 2); else POINTWISE(float, false, 2); }
-  else if (cx) FOR_PREC(precision, POINTWISE(T, true, 1));
-  else FOR_PREC(precision, POINTWISE(T, false, 1));
-#undef POINTWISE
-  HIPK_CHECK(hipGetLastError());
-  return 0;
-}
-
-int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
-                            long long s1, long long s2, void *stream) {
-  if (kind != OFFT_FILTER_REAL && kind != OFFT_FILTER_COMPLEX) { snprintf(g_err, sizeof g_err, "offt_hipk_pointwise_oop: bad filter kind %d", kind); return -1; }
-  if (!in || !out || in == out) { snprintf(g_err, sizeof g_err, "offt_hipk_pointwise_oop: needs two different arrays (in place: offt_hipk_pointwise)"); return -1; }
+// offt_hipk_pointwise (in == out, oop = false) and offt_hipk_pointwise_oop: rows along the smallest stride, the pair test, the grid
+int pointwise_launch(const char *who, const void *in, void *out, bool oop, const void *filter, int precision, int kind, int n0, int n1, int n2,
+                     long long s0, long long s1, long long s2, void *stream) {
+  if (kind != OFFT_FILTER_REAL && kind != OFFT_FILTER_COMPLEX) { snprintf(g_err, sizeof g_err, "%s: bad filter kind %d", who, kind); return -1; }
+  if (oop && (!in || !out || in == out)) { snprintf(g_err, sizeof g_err, "%s: needs two different arrays (in place: offt_hipk_pointwise)", who); return -1; }
   if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
   // rows along the smallest stride
   int n[3] = {n0, n1, n2};
@@ -1961,14 +1903,52 @@ int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int p
   hipStream_t sm = (hipStream_t)stream;
   (void)hipGetLastError();
   const bool cx = kind == OFFT_FILTER_COMPLEX;
-#define POINTWISE_OOP(T, CPLX, EPL) \
+#define DISPATCH(LAUNCH)                                                             \
+  do {                                                                               \
+    if (pair) { if (cx) LAUNCH(float, true, 2); else LAUNCH(float, false, 2); }      \
+    else if (cx) FOR_PREC(precision, LAUNCH(T, true, 1));                            \
+    else FOR_PREC(precision, LAUNCH(T, false, 1));                                   \
+  } while (0)
+#define IN_PLACE(T, CPLX, EPL) \
+  hipLaunchKernelGGL((pointwise_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, (typename vec2<T>::type *)out, filter, n[1], n[2], st[0], st[1], st[2], rows)
+#define OUT_OF_PLACE(T, CPLX, EPL) \
   hipLaunchKernelGGL((pointwise_oop_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, (const typename vec2<T>::type *)in, (typename vec2<T>::type *)out, filter, n[1], n[2], st[0], st[1], st[2], rows)
-  if (pair) { if (cx) POINTWISE_OOP(float, true, 2); else POINTWISE_OOP(float, false, 2); }
-  else if (cx) FOR_PREC(precision, POINTWISE_OOP(T, true, 1));
-  else FOR_PREC(precision, POINTWISE_OOP(T, false, 1));
-#undef POINTWISE_OOP
+  if (!oop) DISPATCH(IN_PLACE);
+  else DISPATCH(OUT_OF_PLACE);
+#undef OUT_OF_PLACE
+#undef IN_PLACE
+#undef DISPATCH
   HIPK_CHECK(hipGetLastError());
   return 0;
+}
+}  // namespace
+
+int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false) != nullptr; }
+const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) { return conv_kernel_name(pick_conv(fwd, f, false)); }
+int offt_hipk_conv_pass(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream) {
+  return conv_launch("offt_hipk_conv_pass", d, f, filter, data, data, false, stream);
+}
+
+int offt_hipk_conv_has_fused_oop(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false, true) != nullptr; }
+const char *offt_hipk_conv_oop_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
+  return conv_kernel_name(pick_conv(fwd, f, false, true));
+}
+int offt_hipk_conv_pass_oop(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream) {
+  if (!src || !dst || src == dst) {
+    snprintf(g_err, sizeof g_err, "offt_hipk_conv_pass_oop: needs two different arrays (src == dst is offt_hipk_conv_pass)");
+    return -1;
+  }
+  return conv_launch("offt_hipk_conv_pass_oop", d, f, filter, src, dst, true, stream);
+}
+
+int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0, long long s1,
+                        long long s2, void *stream) {
+  return pointwise_launch("offt_hipk_pointwise", data, data, false, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
+}
+
+int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
+                            long long s1, long long s2, void *stream) {
+  return pointwise_launch("offt_hipk_pointwise_oop", in, out, true, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
 }
 
 int offt_hipk_zero_outside(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1,

@@ -1612,29 +1612,57 @@ fft_conv_oop_half_panelx_k(PassArgs a, ConvArgs f, const typename vec2<T>::type 
 }
 
 // ---------------------------------------------------------------------------
-// variant registry: every instantiation registers itself under (n, precision, flavour, id)
+// variant registry: every instantiation registers itself under a VariantKey (which kernel it is) and an id
 // ---------------------------------------------------------------------------
+// what an instance does to a line
+enum class Role {
+  Plain,    // complex lines: fft_panel_k / fft_panelx_k, on half lines fft_half_panel_k / fft_half_panelx_k
+  R2C,      // real-input z pass (offt_pass_desc::real_input = 1); on half lines fft_half_r2c_panel_k / fft_half_r2c_panelx_k
+  C2R,      // real-output z pass (real_input = 2): fft_c2r_panel_k / fft_c2r_panelx_k; on half lines fft_half_c2r_panel(x)_k
+  TW4,      // four-step twiddles on the stores (offt_pass_desc::tw4): the first sub-pass of a long line
+  Conv,     // fused convolution in place (offt_hipk_conv_pass): fft_conv_panel_k, fft_conv_half_panel_k and their panelx twins
+  ConvOop,  // ... with a separate store base (offt_hipk_conv_pass_oop): fft_conv_oop_panel_k, fft_conv_oop_half_panel_k, ...
+};
+// column-pair instances (T = f32x2) are kept under their own precision so that the one-column variants and their ids stay
+// what they were
+enum { OFFT_PREC_F32_PAIR = 3, VARIANT_PAIR0 = 200 };  // descriptor variant 200 + id forces pair variant `id`
+template <typename T>
+constexpr int prec_of() { return std::is_same<T, double>::value ? OFFT_PREC_F64 : (lanes<T>::n == 2 ? OFFT_PREC_F32_PAIR : OFFT_PREC_F32); }
+
+// The identity of an instance: a lookup compares all of it, so whoever asks for a key gets that kernel or none.  `mixed`
+// (fft_panel_k or fft_panelx_k) is NOT part of it: the any-split fft_panelx_k instance of a power-of-two length shares the
+// bucket of the fft_panel_k ones and is told apart by its id, VARIANT_ANYSPLIT.
+struct VariantKey {
+  int n, prec;     // prec: OFFT_PREC_F64, OFFT_PREC_F32 or OFFT_PREC_F32_PAIR
+  bool inc, outc;  // the (in_contig, out_contig) flavour
+  Role role;
+  bool keep;       // KEEP instantiation (offt_pass_desc::out_keep): default-policy stores.  (The TW4 instance is compiled with
+                   // TW4_KEEP but registered without: nobody asks for a TW4 twin.)
+  int half;        // the offt_pass_desc::half it implements: 0 full lines; 1, 2; Conv / ConvOop: 3
+  bool operator==(const VariantKey &o) const {
+    return n == o.n && prec == o.prec && inc == o.inc && outc == o.outc && role == o.role && keep == o.keep && half == o.half;
+  }
+};
+struct VariantKeyHash {
+  size_t operator()(const VariantKey &k) const {
+    return ((size_t)(unsigned)k.n << 16) ^ ((size_t)(unsigned)k.half << 8) ^ ((size_t)k.role << 5) ^ ((size_t)(unsigned)k.prec << 3) ^
+           (k.inc ? 4u : 0u) ^ (k.outc ? 2u : 0u) ^ (k.keep ? 1u : 0u);
+  }
+};
+
 struct Variant {
-  int n, prec;
-  bool inc, outc;
+  VariantKey key;
   int id;
-  bool is_default;  // default for this (n, prec, inc, outc) flavour
-  bool r2c;         // real-input z-pass instantiation
+  bool is_default;  // the default of its key: what a lookup without a matching id gets
   int cols, threads, e;
   size_t lds;
   const void *fn;
-  std::string name;
-  bool attr_set;
-  bool mixed;       // fft_panelx_k (any split length incl. uneven, quarter or full twiddle table)
-  bool full_table;
   void *modfn;      // hipFunction_t of an instance compiled at plan time (hipRTC), launched instead of fn
-  bool keep = false;  // KEEP instantiation (offt_pass_desc::out_keep): default-policy stores
-  bool tw4 = false;   // TW4 instantiation (offt_pass_desc::tw4): four-step twiddles on the stores
-  bool c2r = false;   // real-output z-pass instantiation (offt_pass_desc::real_input = 2)
-  bool conv = false;  // fft_conv_panel_k / fft_conv_panelx_k (mixed) instance (offt_hipk_conv_pass), launched with ConvArgs and a filter
-  bool oop = false;   // fft_conv_oop_panel_k / fft_conv_oop_half_panel_k / fft_conv_oop_panelx_k / fft_conv_oop_half_panelx_k (mixed) instance (offt_hipk_conv_pass_oop): conv with a separate store base
-  int half = 0;       // fft_half_panel_k / fft_half_panelx_k / fft_conv_half_panel_k / fft_conv_half_panelx_k instance: the offt_pass_desc::half it implements (1, 2; conv: 3);
-                      // with r2c / c2r: fft_half_r2c_panel_k (1) / fft_half_c2r_panel_k (2), and with mixed their panelx twins
+  bool attr_set;
+  bool mixed;       // fft_panelx_k family (any split length incl. uneven, quarter or full twiddle table)
+  bool full_table;
+  const char *kernel;  // the __global__ template it is an instance of ("<pairs>" appended for T = f32x2)
+  std::string name;
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
 // (uneven, or not a power of two: grids split over 3, 6, ... ranks)
@@ -1642,46 +1670,71 @@ enum { VARIANT_ANYSPLIT = 100 };
 
 std::vector<Variant> &registry();  // defined in offt_kernels.hip
 
+// the launch shape of an instance and what its name says about it: from a PanelCfg, a PanelXCfg (mixed) or a shape chosen
+// at plan time
+struct VariantShape {
+  int cols, threads, e;
+  size_t lds;
+  bool mixed, full_table;
+  int r0, r1, r2, tpl;  // tpl: threads per line (mixed)
+  const char *layout;   // of the exchange through LDS
+};
+inline const char *layout_name(bool split) { return split ? "split-re/im" : "packed"; }
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+VariantShape panel_shape() {
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  return VariantShape{lanes<T>::n * COLS, Cfg::NT, E, Cfg::LDS_BYTES, false, false, R0, R1, R2, 0, layout_name(SPLIT)};
+}
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+VariantShape panelx_shape() {
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  return VariantShape{COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES, true, !Cfg::QUARTER, R0, R1, R2, TPL, layout_name(SPLIT)};
+}
+
+// THE way into the registry.  `kernel`: the __global__ template `fn` (or `modfn`) is an instance of; `suffix`: what the
+// name says after the layout (" half lines", " convolution", ...)
+inline void add_variant(const VariantKey &key, const VariantShape &s, const void *fn, const char *kernel, const char *suffix, int id = 0,
+                        bool is_default = true, void *modfn = nullptr) {
+  const char *p = key.prec ? "f32" : "f64";
+  char nm[224];
+  if (s.mixed)
+    snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s%s lds=%zuB%s", p, key.n, s.r0, s.r1,
+             s.r2, s.tpl, s.e, s.cols, s.layout, suffix, s.lds, modfn ? " [plan-time hipRTC]" : "");
+  else
+    snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d%s %s%s lds=%zuB", p, key.n, s.e, s.r0, s.r1, s.r2, s.cols,
+             key.prec == OFFT_PREC_F32_PAIR ? " (column pairs)" : "", s.layout, suffix, s.lds);
+  registry().push_back(Variant{key, id, is_default, s.cols, s.threads, s.e, s.lds, fn, modfn, false, s.mixed, s.full_table, kernel, nm});
+}
+
 // flavour bits for `defmask`: which (in_contig, out_contig) kernels use this variant by default
 enum { F_CC = 1, F_SS = 2, F_CS = 4, F_SC = 8, F_ALL = 15 };
 
+// T = f32x2: the column-pair instances (reg_variant_pair), which have no real-input or real-output form
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant(int id, int defmask = -1) {
   if (defmask < 0) defmask = id == 0 ? F_ALL : 0;
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[160];
-  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s lds=%zuB", prec ? "f32" : "f64", N, E, R0,
-           R1, R2, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  auto add = [&](bool inc, bool outc, int bit, const void *fn, bool r2c = false) {
-    registry().push_back(Variant{N, prec, inc, outc, id, (defmask & bit) != 0, r2c, COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
+  constexpr bool PAIRS = lanes<T>::n == 2;
+  const VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
+  auto add = [&](bool inc, bool outc, int bit, const void *fn, Role role = Role::Plain, bool keep = false, const char *kernel = nullptr) {
+    add_variant(VariantKey{N, prec_of<T>(), inc, outc, role, keep, 0}, s, fn, kernel ? kernel : PAIRS ? "fft_panel_k<pairs>" : "fft_panel_k", "",
+                id, (defmask & bit) != 0);
   };
   add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT>);
   add(false, false, F_SS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, false, false, SPLIT>);
   add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT>);
   add(false, true, F_SC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, false, true, SPLIT>);
-  // real-input z pass: only the contiguous-read flavours of the default variant need it
-  if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, true>, true);
-  if (defmask & F_CS) add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, true>, true);
-  // real-output z pass (the mirror image): only the contiguous-write flavours of the default variant
-  if (defmask & F_CC) {
-    add(true, true, F_CC, (const void *)fft_c2r_panel_k<T, N, E, R0, R1, R2, COLS, true, SPLIT>);
-    registry().back().c2r = true;
-  }
-  if (defmask & F_SC) {
-    add(false, true, F_SC, (const void *)fft_c2r_panel_k<T, N, E, R0, R1, R2, COLS, false, SPLIT>);
-    registry().back().c2r = true;
+  if constexpr (!PAIRS) {
+    // real-input z pass: only the contiguous-read flavours of the default variant need it
+    if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, true>, Role::R2C);
+    if (defmask & F_CS) add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, true>, Role::R2C);
+    // real-output z pass (the mirror image): only the contiguous-write flavours of the default variant
+    if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_c2r_panel_k<T, N, E, R0, R1, R2, COLS, true, SPLIT>, Role::C2R, false, "fft_c2r_panel_k");
+    if (defmask & F_SC) add(false, true, F_SC, (const void *)fft_c2r_panel_k<T, N, E, R0, R1, R2, COLS, false, SPLIT>, Role::C2R, false, "fft_c2r_panel_k");
   }
   // cache-keeping stores (out_keep): the contig-in / strided-out default, i.e. the y pass of the z-y-x schedules ...
-  if (defmask & F_CS) {
-    add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, false, true>);
-    registry().back().keep = true;
-  }
+  if (defmask & F_CS) add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, false, true>, Role::Plain, true);
   // ... and the contig / contig default: the x pass of the INVERSE z-y-x transform, whose planes the y pass re-reads
-  if (defmask & F_CC) {
-    add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, false, true>);
-    registry().back().keep = true;
-  }
+  if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, false, true>, Role::Plain, true);
 }
 
 // strided / strided instance with the four-step twiddles on its stores (the first sub-pass of a long line, offt_kernels.hip)
@@ -1691,56 +1744,26 @@ void reg_variant(int id, int defmask = -1) {
 constexpr bool TW4_KEEP = OFFT_TW4_KEEP != 0;  // its stores go to the scratch the second sub-pass reads right away: default cache policy
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant_tw4(int id) {
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[160];
-  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d four-step twiddles on the stores lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2,
-           COLS, (size_t)Cfg::LDS_BYTES);
-  registry().push_back(Variant{N, prec, false, false, id, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES,
-                               (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, false, false, SPLIT, false, TW4_KEEP, true>, nm, false, false, false, nullptr});
-  registry().back().tw4 = true;
+  VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
+  s.layout = "four-step twiddles on the stores";  // (its name says this where the others say the layout)
+  add_variant(VariantKey{N, prec_of<T>(), false, false, Role::TW4, false, 0}, s,
+              (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, false, false, SPLIT, false, TW4_KEEP, true>, "fft_panel_k", "", id);
 }
 
-// column-pair instances of fft_panel_k (T = f32x2): kept under their own precision key so that the one-column variants and
-// their ids stay what they were; `defmask` says for which flavours an eligible descriptor prefers the pair kernel.
-enum { OFFT_PREC_F32_PAIR = 3, VARIANT_PAIR0 = 200 };  // descriptor variant 200 + id forces pair variant `id`
+// column-pair instances of fft_panel_k (T = f32x2, under OFFT_PREC_F32_PAIR); `defmask` says for which flavours an eligible
+// descriptor prefers the pair kernel.
 template <int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant_pair(int id, int defmask) {
-  using T = f32x2;
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
-  char nm[160];
-  snprintf(nm, sizeof nm, "f32 N=%d E=%d radix=%dx%dx%d cols=%d (column pairs) %s lds=%zuB", N, E, R0, R1, R2, 2 * COLS,
-           SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  auto add = [&](bool inc, bool outc, int bit, const void *fn) {
-    registry().push_back(Variant{N, OFFT_PREC_F32_PAIR, inc, outc, id, (defmask & bit) != 0, false, 2 * COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
-  };
-  add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT>);
-  add(false, false, F_SS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, false, false, SPLIT>);
-  add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT>);
-  add(false, true, F_SC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, false, true, SPLIT>);
-  if (defmask & F_CS) {
-    add(true, false, F_CS, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, false, true>);
-    registry().back().keep = true;
-  }
-  if (defmask & F_CC) {
-    add(true, true, F_CC, (const void *)fft_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, false, true>);
-    registry().back().keep = true;
-  }
+  reg_variant<f32x2, N, E, R0, R1, R2, COLS, SPLIT>(id, defmask);
 }
 
 // fused convolution instances (fft_conv_panel_k, offt_reg_conv_*.hip): contiguous lines, plus a twin with cache-keeping
 // stores for the alternating launches over groups of z-planes (offt_host.c)
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant_conv() {
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[160];
-  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s convolution lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2,
-           COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  const VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
   auto add = [&](bool keep, const void *fn) {
-    registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
-    registry().back().keep = keep;
-    registry().back().conv = true;
+    add_variant(VariantKey{N, prec_of<T>(), true, true, Role::Conv, keep, 0}, s, fn, "fft_conv_panel_k", " convolution");
   };
   add(false, (const void *)fft_conv_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
   add(true, (const void *)fft_conv_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
@@ -1751,15 +1774,10 @@ void reg_variant_conv() {
 enum { H_CS1 = 1, H_CC1 = 2, H_CC2 = 4, H_SC2 = 8, H_ALL = 15 };
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, int FLAV = H_ALL>
 void reg_variant_half() {
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
-  constexpr int NL = lanes<T>::n;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : (NL == 2 ? OFFT_PREC_F32_PAIR : OFFT_PREC_F32);
-  char nm[160];
-  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d%s %s half lines lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2, NL * COLS,
-           NL == 2 ? " (column pairs)" : "", SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  const VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
   auto add = [&](bool inc, bool outc, int half, const void *fn) {
-    registry().push_back(Variant{N, prec, inc, outc, 0, true, false, NL * COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
-    registry().back().half = half;
+    add_variant(VariantKey{N, prec_of<T>(), inc, outc, Role::Plain, false, half}, s, fn,
+                lanes<T>::n == 2 ? "fft_half_panel_k<pairs>" : "fft_half_panel_k", " half lines");
   };
   if constexpr ((FLAV & H_CS1) != 0) add(true, false, 1, (const void *)fft_half_panel_k<T, N, E, R0, R1, R2, COLS, true, false, SPLIT, 1>);
   if constexpr ((FLAV & H_CC1) != 0) add(true, true, 1, (const void *)fft_half_panel_k<T, N, E, R0, R1, R2, COLS, true, true, SPLIT, 1>);
@@ -1768,53 +1786,32 @@ void reg_variant_half() {
 }
 
 // the real ends of a half-box chain (fft_half_r2c_panel_k, fft_half_c2r_panel_k; offt_reg_half_real_*.hip): one column per
-// lane, keyed by r2c / c2r together with half, so that no complex or full-line lookup finds them
+// lane, keyed by R2C / C2R together with half, so that no complex or full-line lookup finds them
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant_half_real() {
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
   static_assert(lanes<T>::n == 1, "real rows: one column per lane");
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[160];
-  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s half lines, real rows lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2, COLS,
-           SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  registry().push_back(Variant{N, prec, true, false, 0, true, true, COLS, Cfg::NT, E, Cfg::LDS_BYTES,
-                               (const void *)fft_half_r2c_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>, nm, false, false, false, nullptr});
-  registry().back().half = 1;
-  registry().push_back(Variant{N, prec, false, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES,
-                               (const void *)fft_half_c2r_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>, nm, false, false, false, nullptr});
-  registry().back().c2r = true;
-  registry().back().half = 2;
+  const VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
+  add_variant(VariantKey{N, prec_of<T>(), true, false, Role::R2C, false, 1}, s, (const void *)fft_half_r2c_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>,
+              "fft_half_r2c_panel_k", " half lines, real rows");
+  add_variant(VariantKey{N, prec_of<T>(), false, true, Role::C2R, false, 2}, s, (const void *)fft_half_c2r_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>,
+              "fft_half_c2r_panel_k", " half lines, real rows");
 }
 
 // fused convolution on half lines (fft_conv_half_panel_k): the shapes of reg_variant_conv
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant_conv_half() {
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[160];
-  snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s convolution on half lines lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1, R2,
-           COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES,
-                               (const void *)fft_conv_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>, nm, false, false, false, nullptr});
-  registry().back().conv = true;
-  registry().back().half = 3;
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::Conv, false, 3}, panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>(),
+              (const void *)fft_conv_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>, "fft_conv_half_panel_k", " convolution on half lines");
 }
 
 // out-of-place fused convolution (fft_conv_oop_panel_k, fft_conv_oop_half_panel_k; offt_reg_conv_oop_*.hip): the shapes of
 // reg_variant_conv, full lines and half lines, each plain and with cache-keeping stores
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variant_conv_oop() {
-  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
+  const VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
   auto add = [&](bool keep, int half, const void *fn) {
-    char nm[176];
-    snprintf(nm, sizeof nm, "%s N=%d E=%d radix=%dx%dx%d cols=%d %s out-of-place convolution%s lds=%zuB", prec ? "f32" : "f64", N, E, R0, R1,
-             R2, COLS, SPLIT ? "split-re/im" : "packed", half ? " on half lines" : "", (size_t)Cfg::LDS_BYTES);
-    registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, E, Cfg::LDS_BYTES, fn, nm, false, false, false, nullptr});
-    registry().back().keep = keep;
-    registry().back().conv = true;
-    registry().back().oop = true;
-    registry().back().half = half;
+    add_variant(VariantKey{N, prec_of<T>(), true, true, Role::ConvOop, keep, half}, s, fn, half ? "fft_conv_oop_half_panel_k" : "fft_conv_oop_panel_k",
+                half ? " out-of-place convolution on half lines" : " out-of-place convolution");
   };
   add(false, 0, (const void *)fft_conv_oop_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
   add(true, 0, (const void *)fft_conv_oop_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
@@ -1829,35 +1826,26 @@ template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPL
 void reg_variantx(int id, int defmask = -1) {
   if (defmask < 0) defmask = id == 0 ? F_ALL : 0;
   defmask &= FLAV;
-  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[160];
-  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s lds=%zuB", prec ? "f32" : "f64", N,
-           R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  auto add = [&](bool inc, bool outc, int bit, const void *fn, bool r2c = false) {
-    registry().push_back(Variant{N, prec, inc, outc, id, (defmask & bit) != 0, r2c, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES, fn, nm, false, true, !Cfg::QUARTER, nullptr});
+  const VariantShape s = panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>();
+  auto add = [&](bool inc, bool outc, int bit, const void *fn, Role role = Role::Plain) {
+    add_variant(VariantKey{N, prec_of<T>(), inc, outc, role, false, 0}, s, fn, role == Role::C2R ? "fft_c2r_panelx_k" : "fft_panelx_k", "", id,
+                (defmask & bit) != 0);
   };
   if constexpr ((FLAV & F_CC) != 0) {
     add(true, true, F_CC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT>);
-    if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT, true>, true);
+    if (defmask & F_CC) add(true, true, F_CC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT, true>, Role::R2C);
     // (real output: also the any-split instances of the power-of-two lengths, so that the inverse's z pass of a grid split
     //  over 3, 5, 6 ... ranks runs here rather than on the any-length kernel)
-    if ((defmask & F_CC) || id == VARIANT_ANYSPLIT) {
-      add(true, true, F_CC, (const void *)fft_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, SPLIT>);
-      registry().back().c2r = true;
-    }
+    if ((defmask & F_CC) || id == VARIANT_ANYSPLIT) add(true, true, F_CC, (const void *)fft_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, SPLIT>, Role::C2R);
   }
   if constexpr ((FLAV & F_SS) != 0) add(false, false, F_SS, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, false, SPLIT>);
   if constexpr ((FLAV & F_CS) != 0) {
     add(true, false, F_CS, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT>);
-    if (defmask & F_CS) add(true, false, F_CS, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT, true>, true);
+    if (defmask & F_CS) add(true, false, F_CS, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT, true>, Role::R2C);
   }
   if constexpr ((FLAV & F_SC) != 0) {
     add(false, true, F_SC, (const void *)fft_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, true, SPLIT>);
-    if ((defmask & F_SC) || id == VARIANT_ANYSPLIT) {
-      add(false, true, F_SC, (const void *)fft_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, SPLIT>);
-      registry().back().c2r = true;
-    }
+    if ((defmask & F_SC) || id == VARIANT_ANYSPLIT) add(false, true, F_SC, (const void *)fft_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, false, SPLIT>, Role::C2R);
   }
 }
 
@@ -1866,15 +1854,10 @@ void reg_variantx(int id, int defmask = -1) {
 // contiguous shape registers that shape for H_CC1 | H_CC2 and the wide one for H_CS1 | H_SC2.
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT, int FLAV = H_ALL>
 void reg_variantx_half() {
-  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
-  static_assert(Cfg::QUARTER, "half lines: N is a multiple of 4");
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[176];
-  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s half lines lds=%zuB", prec ? "f32" : "f64", N,
-           R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
+  static_assert(PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::QUARTER, "half lines: N is a multiple of 4");
+  const VariantShape s = panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>();
   auto add = [&](bool inc, bool outc, int half, const void *fn) {
-    registry().push_back(Variant{N, prec, inc, outc, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES, fn, nm, false, true, false, nullptr});
-    registry().back().half = half;
+    add_variant(VariantKey{N, prec_of<T>(), inc, outc, Role::Plain, false, half}, s, fn, "fft_half_panelx_k", " half lines");
   };
   if constexpr ((FLAV & H_CS1) != 0) add(true, false, 1, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, false, SPLIT, 1>);
   if constexpr ((FLAV & H_CC1) != 0) add(true, true, 1, (const void *)fft_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, true, true, SPLIT, 1>);
@@ -1883,71 +1866,42 @@ void reg_variantx_half() {
 }
 
 // the real ends of a half-box chain at a mixed-radix length (fft_half_r2c_panelx_k, fft_half_c2r_panelx_k;
-// offt_reg_half_real_mixed_*.hip): keyed by r2c / c2r together with half and mixed, so that no complex or full-line lookup
-// finds them and pick_half hands them out only to a descriptor that carries bit 4 of offt_pass_desc::half
+// offt_reg_half_real_mixed_*.hip): keyed by R2C / C2R together with half, so that no complex or full-line lookup finds
+// them; they are `mixed`, and pick_half hands them out only to a descriptor that carries bit 4 of offt_pass_desc::half
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variantx_half_real() {
-  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
-  static_assert(Cfg::QUARTER, "half lines: N is a multiple of 4");
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[176];
-  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s half lines, real rows lds=%zuB",
-           prec ? "f32" : "f64", N, R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  registry().push_back(Variant{N, prec, true, false, 0, true, true, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
-                               (const void *)fft_half_r2c_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
-  registry().back().half = 1;
-  registry().push_back(Variant{N, prec, false, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
-                               (const void *)fft_half_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
-  registry().back().c2r = true;
-  registry().back().half = 2;
+  static_assert(PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::QUARTER, "half lines: N is a multiple of 4");
+  const VariantShape s = panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>();
+  add_variant(VariantKey{N, prec_of<T>(), true, false, Role::R2C, false, 1}, s, (const void *)fft_half_r2c_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_half_r2c_panelx_k", " half lines, real rows");
+  add_variant(VariantKey{N, prec_of<T>(), false, true, Role::C2R, false, 2}, s, (const void *)fft_half_c2r_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_half_c2r_panelx_k", " half lines, real rows");
 }
 
 // fused convolution instances of the mixed-radix kernel (fft_conv_panelx_k, offt_reg_conv_mixed_*.hip; picked only with
 // offt_filter_desc::mixed): contiguous lines, no cache-keeping twin ...
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variantx_conv() {
-  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[176];
-  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s convolution lds=%zuB", prec ? "f32" : "f64", N,
-           R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
-                               (const void *)fft_conv_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
-  registry().back().conv = true;
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::Conv, false, 0}, panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>(),
+              (const void *)fft_conv_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, "fft_conv_panelx_k", " convolution");
 }
 
 // ... and on half lines (fft_conv_half_panelx_k): the same shapes
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variantx_conv_half() {
-  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  char nm[176];
-  snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s convolution on half lines lds=%zuB",
-           prec ? "f32" : "f64", N, R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", (size_t)Cfg::LDS_BYTES);
-  registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES,
-                               (const void *)fft_conv_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, nm, false, true, false, nullptr});
-  registry().back().conv = true;
-  registry().back().half = 3;
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::Conv, false, 3}, panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>(),
+              (const void *)fft_conv_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>, "fft_conv_half_panelx_k", " convolution on half lines");
 }
 
 // ... and out of place (fft_conv_oop_panelx_k, fft_conv_oop_half_panelx_k; offt_reg_conv_oop_mixed_*.hip; picked only with
 // both bits of offt_filter_desc::mixed): the shapes of reg_variantx_conv, full lines and half lines, no cache-keeping twin
 template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
 void reg_variantx_conv_oop() {
-  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
-  const int prec = std::is_same<T, double>::value ? OFFT_PREC_F64 : OFFT_PREC_F32;
-  auto add = [&](int half, const void *fn) {
-    char nm[192];
-    snprintf(nm, sizeof nm, "%s N=%d mixed radix=%dx%dx%d threads/line=%d (<=%d elems/thread) cols=%d %s out-of-place convolution%s lds=%zuB",
-             prec ? "f32" : "f64", N, R0, R1, R2, TPL, Cfg::EMAX, COLS, SPLIT ? "split-re/im" : "packed", half ? " on half lines" : "",
-             (size_t)Cfg::LDS_BYTES);
-    registry().push_back(Variant{N, prec, true, true, 0, true, false, COLS, Cfg::NT, Cfg::EMAX, Cfg::LDS_BYTES, fn, nm, false, true, false, nullptr});
-    registry().back().conv = true;
-    registry().back().oop = true;
-    registry().back().half = half;
-  };
-  add(0, (const void *)fft_conv_oop_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>);
-  add(3, (const void *)fft_conv_oop_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>);
+  const VariantShape s = panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>();
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::ConvOop, false, 0}, s, (const void *)fft_conv_oop_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_conv_oop_panelx_k", " out-of-place convolution");
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::ConvOop, false, 3}, s, (const void *)fft_conv_oop_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_conv_oop_half_panelx_k", " out-of-place convolution on half lines");
 }
 
 // instantiation groups (offt_reg_*.hip)
