@@ -119,6 +119,26 @@ int offt_hipk_variant_info(int n, int precision, int variant, int *elems_per_thr
  * launcher's resolve().  A pass that is decomposed (four-step, lines through scratch) launches several kernels and is
  * named by the kernel that would take its descriptor alone.                      */
 const char *offt_hipk_kernel_name(const offt_pass_desc *d);
+/* How offt_hipk_fft_pass would run the descriptor: the launcher's own resolve(), asked without launching.  Unlike
+ * offt_hipk_kernel_name it names the decomposing routes, and it says WHICH registry entry a panel pass gets -- a forced
+ * d->variant that no entry of the flavour carries resolves to the flavour's default, and only this query shows it.
+ * *variant_id (may be NULL): the registry id of the panel entry; 200 + id for a column-pair entry (VARIANT_PAIR0, the
+ * range d->variant forces them with), 100 for the any-split instance of a power-of-two length (VARIANT_ANYSPLIT); -1 for
+ * every route that is not a panel kernel.
+ * *n1, *n2 (may be NULL): the factors of a four-step line, else 0.
+ * OFFT_ROUTE_NONE: the pass launches nothing -- an empty batch, a half-line or four-step-twiddle descriptor no kernel
+ * takes, a line too long for the any-length kernel.  Base pointers count as aligned (as for offt_hipk_kernel_name).  The
+ * decomposing routes exist for a length only after offt_hipk_prepare; everything else is a registry lookup and needs
+ * no device. */
+enum {
+  OFFT_ROUTE_NONE = 0,
+  OFFT_ROUTE_PANEL = 1,            /* fft_panel_k / fft_panelx_k and their real, half-line and four-step-twiddle forms */
+  OFFT_ROUTE_BLUESTEIN_PANEL = 2,  /* fft_bluestein_k */
+  OFFT_ROUTE_ANY_LENGTH = 3,       /* fft_mixed_k */
+  OFFT_ROUTE_FOUR_STEP = 4,        /* n = n1 n2: two sub-passes through scratch */
+  OFFT_ROUTE_SCRATCH_LINES = 5     /* gathered into contiguous scratch lines (uneven blocks, real lines, long Bluestein) */
+};
+int offt_hipk_pass_route(const offt_pass_desc *d, int *variant_id, int *n1, int *n2);
 /* 1 if a half-line kernel exists for the descriptor (d->half = 1 or 2): power-of-two lines of 64 ... 1024 points or one of
  * the mixed-radix lengths listed at offt_pass_desc::half (offt_hipk_kernel_name: "fft_half_panelx_k"), complex,
  * no split, no four-step twiddles, and one of the flavours contiguous-in / strided-out with bit 1, contiguous / contiguous

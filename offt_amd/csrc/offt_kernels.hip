@@ -1280,7 +1280,14 @@ Route resolve(const offt_pass_desc *d, const void *in, const void *out) {
   if (long_lookup(d->n, d->precision, &r.lt)) { r.via = Via::ScratchLines; return r; }
   // 4. one launch: panel kernel, Bluestein panel kernel, any-length kernel
   resolve_direct(d, in, out, &r);
-  if (r.via != Via::AnyLength || !d->real_input) return r;
+  if (r.via != Via::AnyLength) return r;
+  if (!d->real_input) {
+    // 4b. a complex line with a register kernel of its own but blocks that kernel cannot address, beyond the any-length
+    //     kernel (8192 double-precision points, contiguous / contiguous, uneven blocks -- the strided flavours took the
+    //     four-step branch above): gathered with the split, transformed as plain contiguous lines
+    if (has_panel(d->n, d->precision) && !fits_any_length(d->n, d->precision)) r.via = Via::ScratchLines;
+    return r;
+  }
   // 5. a REAL-input (or real-output) line of a Bluestein length: gathered as complex lines into scratch, transformed there by
   //    the Bluestein panel kernel, the first n/2 + 1 outputs (the n real parts) scattered -- three sweeps, against a radix of the
   //    size of its largest prime factor on the any-length kernel (OFFT_R2C_BLUESTEIN=0: that kernel, as in rounds 1-2)
@@ -1290,6 +1297,9 @@ Route resolve(const offt_pass_desc *d, const void *in, const void *out) {
   else if (d->real_input == 2 && !fits_any_length(d->n, d->precision)) r.via = Via::ScratchLines;
   return r;
 }
+
+// four-step twiddles ride on the stores of a TW4 panel instance and of nothing else: every other route would drop them
+bool drops_tw4(const offt_pass_desc *d, const Route &r) { return d->tw4 && !(r.via == Via::Panel && r.v->key.role == Role::TW4); }
 
 // ---- packing and launching ----
 int log2i(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
@@ -1683,6 +1693,35 @@ const char *offt_hipk_kernel_name(const offt_pass_desc *d) {
 
 int offt_hipk_has_half(const offt_pass_desc *d) { return pick_half(d) != nullptr; }
 
+// what offt_hipk_fft_pass does with a descriptor, step for step, with resolve()'s answer reported instead of launched
+int offt_hipk_pass_route(const offt_pass_desc *d, int *variant_id, int *n1, int *n2) {
+  if (variant_id) *variant_id = -1;
+  if (n1) *n1 = 0;
+  if (n2) *n2 = 0;
+  if (!d || d->n < 1 || d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return OFFT_ROUTE_NONE;
+  auto panel = [&](const Variant *v) {
+    if (variant_id) *variant_id = v->key.prec == OFFT_PREC_F32_PAIR ? VARIANT_PAIR0 + v->id : v->id;
+    return (int)OFFT_ROUTE_PANEL;
+  };
+  if (d->half) {
+    const Variant *h = pick_half(d);
+    return h ? panel(h) : (int)OFFT_ROUTE_NONE;
+  }
+  const Route r = resolve(d, nullptr, nullptr);
+  if (drops_tw4(d, r)) return OFFT_ROUTE_NONE;
+  switch (r.via) {
+    case Via::FourStep:
+      if (n1) *n1 = r.fs.n1;
+      if (n2) *n2 = r.fs.n2;
+      return OFFT_ROUTE_FOUR_STEP;
+    case Via::ScratchLines: return OFFT_ROUTE_SCRATCH_LINES;
+    case Via::Panel: return panel(r.v);
+    case Via::BluePanel: return OFFT_ROUTE_BLUESTEIN_PANEL;
+    case Via::AnyLength: return fits_any_length(d->n, d->precision) ? (int)OFFT_ROUTE_ANY_LENGTH : (int)OFFT_ROUTE_NONE;
+  }
+  return OFFT_ROUTE_NONE;
+}
+
 int offt_hipk_prepare(int n, int precision) {
   const bool c2r = (precision & OFFT_HIPK_PREP_C2R) != 0;
   precision &= ~OFFT_HIPK_PREP_C2R;
@@ -1754,6 +1793,7 @@ int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void 
     return launch_panel(d, in, out, tb, (hipStream_t)stream, h);
   }
   const Route r = resolve(d, in, out);
+  if (drops_tw4(d, r)) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: no kernel with four-step twiddles for n=%d", d->n); return -1; }
   switch (r.via) {
     case Via::FourStep: return four_pass(d, in, out, stream, r.fs, tb);
     case Via::ScratchLines: return long_pass(d, in, out, stream, r.lt);

@@ -540,21 +540,38 @@ def test_host_pointer_boundary(built):
 
 
 def test_sweep_variants_agree(built):
+    """every sweep variant id of the 512-, 1024- and 2048-point kernels in both precisions, forced on all three axes of a
+    plan (offt_hip_set_variant, what run-fft -l does with a variant that wins), with the long axis in each position and
+    in both layouts -- so that each id runs in every pass flavour the schedules have.  Forward against numpy's transform of
+    the field (single precision: of the complex64-rounded field), then the inverse on the result against the field: the
+    variants agree because each of them is right, not with one another."""
     L = api.lib()
-    n = 1024
-    shape = (n, 8, 8)
-    base, _ = gpu_fft(shape)
-    nv = L.offt_hipk_variant_count(n, 0)
-    assert nv >= 2
-    for v in range(nv):
-        po = api.offt_3d_init(*shape)
-        for ax in range(3):
-            L.offt_hip_set_variant(po, ax, v)
-        dev, _ = make_input(po, O.hash_field(*shape))
-        api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
-        got = read_output(po, dev, shape)
-        api.offt_3d_fin(po)
-        assert rel(got, base) < 1e-15 * 10
+    for prec, n in [(p, n) for p in (api.F64, api.F32) for n in (512, 1024, 2048)]:
+        nv = L.offt_hipk_variant_count(n, prec)
+        assert nv >= 2
+        ct = np.complex128 if prec == api.F64 else np.complex64
+        for shape in ((n, 8, 8), (8, n, 8), (8, 8, n)):
+            field = O.hash_field(*shape)
+            want = np.fft.fftn(field.astype(ct).astype(np.complex128))
+            for layout in (dict(S=1), dict()):
+                for v in range(nv):
+                    po = api.offt_3d_init(*shape, custom_params=api.make_params(**layout), precision=prec)
+                    try:
+                        for ax in range(3):
+                            L.offt_hip_set_variant(po, ax, v)
+                        dev, idx = make_input(po, field, prec)
+                        api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+                        got = read_output(po, dev, shape, prec)
+                        api.offt_3d_execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
+                        back = dev.cpu().numpy().view(ct)[idx].reshape(shape) / np.prod(shape)
+                    finally:
+                        api.offt_3d_fin(po)
+                    if prec == api.F64:
+                        check64(got, want)
+                        assert rel(back, field) <= TOL64, (n, shape, layout, v)
+                    else:
+                        assert rel(got.astype(np.complex128), want) <= TOL32, (n, shape, layout, v)
+                        assert rel(back, field) <= TOL32, (n, shape, layout, v)
 
 
 def test_rccl_self_exchange_one_rank(built, monkeypatch):
