@@ -100,6 +100,28 @@ int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout,
  * rank, the default z-y-x layout, an x extent that is a power of two from 64 to 1024 or, with OFFT_HIP_OPT_CONV_MIXED and
  * OFFT_HIP_OPT_CONV_MULTI_MIXED both set, one of the mixed-radix lengths listed there; 0: the generic route */
 int offt_hip_convolve_multi_fused(const struct _offt_plan *po);
+/* spectral convolution with several inputs: nin forward transforms, ONE inverse:
+ *   out = scale * N * ifftn( sum_k filters[k] * fftn(x_k) )   (irfftn / rfftn for an r2c plan)
+ * -- the transpose of offt_hip_execute_convolve_multi: the inverse Laplacian of the divergence of a vector field (pressure
+ * projection), the potential of several charge species with a shape function each, multi-channel correlation.  ins[k] is this
+ * rank's block of input k in the INPUT layout and follows the rules of `data` in the single-output call (real rows on an r2c
+ * plan, the half box); filters[k] is laid out like the forward's OUTPUT block, all filters share one filter_kind; `out`
+ * receives the result in the INPUT layout and may be any one of the ins[k] or a device buffer of its own of
+ * offt_hip_local_bytes(po) bytes.  EVERY ins[k] is consumed: its contents are undefined afterwards, unless it is `out`.  The
+ * terms are added in the order k = 0 ... nin-1 on every route (a call is reproducible bit for bit); the output scale applies
+ * once, on the final store.  Stream, async, half box and OFFT_HIP_OPT_ZGROUP_MIB are honoured as in
+ * offt_hip_execute_convolve_multi.  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and
+ * offt_hip_last_error(), and nothing launched, for nin < 1 or nin > OFFT_HIP_CONV_MAX_IN, NULL ins or filters arrays, a NULL
+ * or host-memory ins[k], filters[k] or out, two equal ins entries, an unknown filter_kind, a backend without the
+ * multiply-and-sum, a failed communicator.  With nin == 1 and out == ins[0] the call IS offt_hip_execute_convolve: the same
+ * bits.  offt_hip_last_device_seconds covers the whole call; offt_hip_last_pass_seconds reports zeros. */
+#define OFFT_HIP_CONV_MAX_IN 8
+int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *ins, const void *const *filters, int filter_kind, void *out);
+/* 1 if the call runs the fused multi-input route: the forward's z and y passes per input, then ONE launch that runs the
+ * forward x pass of every input, multiplies, sums in registers and runs the inverse x pass (all ins -> out), and the
+ * inverse's y and z passes once -- one rank, the default z-y-x layout, an x extent that is a power of two from 64 to 1024;
+ * 0: the generic route (a forward per input, one multiply-and-sum sweep, one inverse) */
+int offt_hip_convolve_sum_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
  *   full spectrum of the zero-padded field, in the usual output layout.

@@ -105,6 +105,10 @@ def bind(L):
     L.offt_hip_execute_convolve_multi.argtypes = [PP, C.c_void_p, i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i]
     L.offt_hip_convolve_multi_fused.restype = i
     L.offt_hip_convolve_multi_fused.argtypes = [PP]
+    L.offt_hip_execute_convolve_sum.restype = i
+    L.offt_hip_execute_convolve_sum.argtypes = [PP, i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i, C.c_void_p]
+    L.offt_hip_convolve_sum_fused.restype = i
+    L.offt_hip_convolve_sum_fused.argtypes = [PP]
     L.offt_hip_set_half_box.restype = i
     L.offt_hip_set_half_box.argtypes = [PP, i]
     L.offt_hip_half_box_pruned.restype = i
@@ -228,6 +232,27 @@ def offt_hip_convolve_multi_fused(po):
 
 
 CONV_MAX_OUT = 8  # offt_hip.h OFFT_HIP_CONV_MAX_OUT
+
+
+def offt_hip_execute_convolve_sum(po, ins, filts, out, filter_kind=FILTER_REAL):
+    """out = scale * N * ifftn(sum_k filts[k] * fftn(ins[k])): one forward per input, ONE inverse (lists of device pointers of
+    equal length; `out` may be any one of the inputs or a buffer of its own of offt_hip_local_bytes bytes).  Every input is
+    consumed unless it is `out` (include/offt_hip.h)"""
+    L = lib()
+    if len(ins) != len(filts):
+        raise ValueError("offt_hip_execute_convolve_sum: %d inputs, %d filters" % (len(ins), len(filts)))
+    n = len(ins)
+    pi_, pf_ = (C.c_void_p * max(n, 1))(*ins), (C.c_void_p * max(n, 1))(*filts)
+    if L.offt_hip_execute_convolve_sum(po, n, pi_, pf_, filter_kind, out) != 0:
+        raise RuntimeError("offt_hip_execute_convolve_sum failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_convolve_sum_fused(po):
+    """True if the call runs the fused multi-input route (one gather launch for the x passes of all inputs)"""
+    return lib().offt_hip_convolve_sum_fused(po) == 1
+
+
+CONV_MAX_IN = 8  # offt_hip.h OFFT_HIP_CONV_MAX_IN
 
 
 def offt_hip_set_half_box(po, on=True):

@@ -70,9 +70,19 @@ typedef struct offt_backend {
                        void *stream);
   int (*pointwise_oop)(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
                        long long s1, long long s2, void *stream);
+  /* ---- multi-input convolution (offt_hip_execute_convolve_sum); appended again, so that an older table leaves both NULL ----
+   * conv_pass_sum: offt_hipk_conv_pass_sum -- the fused launch from nin sources into `dst`; NULL: no fused multi-input route.
+   * pointwise_sum: offt_hipk_pointwise_sum -- out = sum_k in_k * H_k; NULL: the call is refused. */
+  int (*conv_pass_sum)(const offt_pass_desc *fwd, const offt_filter_desc *f, int nin, const void *const *filters, const void *const *srcs,
+                       void *dst, void *stream);
+  int (*pointwise_sum)(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,
+                       int n2, long long s0, long long s1, long long s2, void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);
+/* the HIP backend itself with conv_pass_sum withheld (a table for offt_hip_test_set_backend): the generic multi-input route
+ * on the device, for timing it against the fused one */
+const offt_backend *offt_hip_test_hip_backend_no_conv_sum(void);
 
 /* keep the HIP backend but route the exchange through `fn` (called with the comm stream
  * drained; device pointers): several test ranks can then share one GPU */

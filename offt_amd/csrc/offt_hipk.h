@@ -206,6 +206,25 @@ const char *offt_hipk_conv_oop_kernel_name(const offt_pass_desc *fwd, const offt
  * (in != out; `in` is not written).  Non-temporal, 16 B per lane along the smallest stride. */
 int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2,
                             long long s0, long long s1, long long s2, void *stream);
+/* ---- multi-input convolution (offt_hip_execute_convolve_sum): several sources filtered and summed into one destination ----
+ * offt_hipk_conv_pass with nin sources: the lines of every srcs[k] (fwd's in_* addressing) are transformed, multiplied by
+ * filters[k] (all addressed by f) and added in the order k = 0 ... nin-1 in registers; ONE inverse transform of the sum,
+ * times fwd->scale, is stored to `dst` at the same offsets.  `dst` may be one of the sources (a workgroup has loaded its lines
+ * from every source before its only stores); no other source is written.  fwd->half: 0 or 3; fwd->out_keep: the cache-keeping
+ * twin (every instance has one).  Power-of-two lines of 64 ... 1024 points; a mixed-radix length has no kernel whatever
+ * f->mixed says.  -1, and nothing launched, for nin < 1, nin > OFFT_HIPK_CONV_MAX_IN, a NULL pointer or no kernel. */
+#define OFFT_HIPK_CONV_MAX_IN 8
+int offt_hipk_conv_pass_sum(const offt_pass_desc *fwd, const offt_filter_desc *f, int nin, const void *const *filters,
+                            const void *const *srcs, void *dst, void *stream);
+/* 1 if offt_hipk_conv_pass_sum has a kernel for (fwd, f): pick_conv's conditions (contiguous lines, unit-stride filter axis,
+ * no split, half 0 or 3) at a power of two; the registry lookup needs no device */
+int offt_hipk_conv_has_fused_sum(const offt_pass_desc *fwd, const offt_filter_desc *f);
+/* "fft_conv_sum_panel_k", "fft_conv_sum_half_panel_k" (fwd->half = 3) or "no fused kernel" */
+const char *offt_hipk_conv_sum_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f);
+/* out[i0 s0 + i1 s1 + i2 s2] = sum_k ins[k][same] * filters[k][same] over the box n0 x n1 x n2, the terms added in the order
+ * k = 0 ... nin-1: ONE sweep, non-temporal, 16 B per lane along the smallest stride.  `out` may be one of the inputs. */
+int offt_hipk_pointwise_sum(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,
+                            int n2, long long s0, long long s1, long long s2, void *stream);
 /* zero a strided 3-D block n0 x n1 x n2 OUTSIDE the kept sub-box [0,k0) x [0,k1) x [0,k2) (0 <= k <= n); the kept part is
  * not touched.  Elements are complex values of `precision`, or, with OFFT_HIPK_ZERO_REAL or-ed into it, real scalars (the
  * rows of an r2c plan; strides and extents then count scalars).  Vector stores, 16 B per lane along a unit stride s2. */

@@ -675,6 +675,18 @@ static int hb_conv_pass_oop(const offt_pass_desc *fwd, const offt_filter_desc *f
   if (rc) SET_ERR("out-of-place fused convolution pass n=%d failed: %s", fwd->n, offt_hipk_last_error());
   return rc;
 }
+static int hb_conv_pass_sum(const offt_pass_desc *fwd, const offt_filter_desc *f, int nin, const void *const *filters,
+                            const void *const *srcs, void *dst, void *stream) {
+  const int rc = offt_hipk_conv_pass_sum(fwd, f, nin, filters, srcs, dst, stream);
+  if (rc) SET_ERR("multi-input fused convolution pass failed: %s", offt_hipk_last_error());
+  return rc;
+}
+static int hb_pointwise_sum(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,
+                            int n2, long long s0, long long s1, long long s2, void *stream) {
+  const int rc = offt_hipk_pointwise_sum(nin, ins, filters, out, precision, kind, n0, n1, n2, s0, s1, s2, stream);
+  if (rc) SET_ERR("pointwise multiply-and-sum failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static int hb_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
                             long long s1, long long s2, void *stream) {
   const int rc = offt_hipk_pointwise_oop(in, out, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
@@ -691,7 +703,17 @@ static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
     hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside,
-    hb_conv_pass_oop, hb_pointwise_oop};
+    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum};
+#ifdef OFFT_TEST_SEAMS
+/* the HIP backend without its fused multi-input launch, for offt_hip_test_set_backend: a plan made under it takes the generic
+ * route of offt_hip_execute_convolve_sum on the device (tools/conv_probe.py times that route with it) */
+const offt_backend *offt_hip_test_hip_backend_no_conv_sum(void) {
+  static offt_backend b;
+  b = k_hip_backend;
+  b.conv_pass_sum = NULL;
+  return &b;
+}
+#endif
 
 /* ------------------------------------------------------------------------- */
 /* helpers                                                                    */
@@ -3263,6 +3285,154 @@ int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout,
       }
       if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, out) : execute_single(po, out, +1);
     }
+  }
+  st->out_scale = scale;
+  st->yx_fused = 0;
+  if (timed) be->event_record(st->ev1, st->s_compute);
+  if (rc) {
+    if (st->uses_rccl) comm_fail(st);
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if (st->async) { t[ALL] = wall_seconds() - t0; return 0; }
+  if (wait_compute(st)) { t[ALL] = 99999999.0; return -1; }
+  st->last_dev_s = 1e-3 * be->event_ms(st->ev0, st->ev1);
+  for (int i = 0; i < 3; i++) st->pass_s[i] = 0.0;
+  t[ALL] = wall_seconds() - t0;
+  return 0;
+}
+
+/* ------------------------------------------------------------------------- */
+/* multi-input spectral convolution: several forwards, one inverse             */
+/* ------------------------------------------------------------------------- */
+/* The fused multi-input route: one rank, the z-y-x layout, the conditions of conv_fused_route, and a backend and a kernel for
+ * the launch that gathers several sources: powers of two from 64 to 1024 (a mixed-radix x extent has no such kernel, whatever
+ * the plan's options say).  conv_fused_route asks for the single-input kernel as well, which every such length has.  Fills
+ * what conv_fused_route fills. */
+static int conv_sum_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, offt_pass_desc *fd,
+                                offt_filter_desc *fl) {
+  hip_state *st = (hip_state *)po->hip_state;
+  if (!fw->zyx || !st->be->conv_pass_sum) return 0;
+  if (!conv_fused_route(po, fw, iv, kind, fd, fl)) return 0;
+  return offt_hipk_conv_has_fused_sum(fd, fl);
+}
+
+/* z-y-x: the forward of an input is in -> W -> in with the x pass in place.  W is one volume, so the inputs are the outer
+ * loop of the forward:
+ *   inputs 0 ... nin-2:  forward z (ins[k] -> W), forward y (W -> ins[k]), plain launches;
+ *   the last input:      forward z, then per plane group  forward y (W -> ins[nin-1], kept), the gather launch (forward x pass
+ *                        of every input . filter . sum . inverse x pass, all ins -> out, kept), inverse y (out -> W);
+ *   inverse z (W -> out), with the output scale.
+ * The inverse y of a group writes the part of W that the last input's forward y of that group has read.  `out` may be one
+ * of the inputs: the gather launch loads a line from every input before it stores it.
+ * 1: no such route (the caller takes the generic one). */
+static int execute_convolve_sum_single(struct _offt_plan *po, int nin, void *const *ins, const void *const *filters, int kind, void *out) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  void *s = st->s_compute;
+  single_sched fw, iv;
+  single_schedule(po, out, -1, &fw);
+  single_schedule(po, out, +1, &iv); /* x in place on out, y: out -> W, z: W -> out, the output scale on the z pass */
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  if (!conv_sum_fused_route(po, &fw, &iv, kind, &fd, &fl)) return 1;
+  const size_t fesz = kind == OFFT_FILTER_COMPLEX ? st->esz : st->esz / 2; /* filter bytes per element */
+  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
+  int ng = 0; /* planes per group, as in execute_convolve_multi_single; 0: plain launches */
+  if (fw.d[1].nb1 == cnt && fd.nb1 == cnt && iv.d[1].nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, &fw.d[1]);
+  const int step = ng >= 1 ? ng : (cnt > 0 ? cnt : 1);
+  for (int k = 0; k < nin; k++) {
+    single_schedule(po, ins[k], -1, &fw);
+    if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
+    if (k < nin - 1 && be->pass(&fw.d[1], fw.src[1], fw.dst[1], s)) return -1;
+  }
+  const offt_pass_desc *py = &fw.d[1]; /* of the last input */
+  for (int z0 = 0; z0 < cnt; z0 += step) {
+    const int g = cnt - z0 < step ? cnt - z0 : step;
+    offt_pass_desc a = *py, b = fd, q = iv.d[1];
+    a.nb1 = b.nb1 = q.nb1 = g;
+    a.out_keep = b.out_keep = ng >= 1;
+    const size_t off = (size_t)z0 * (size_t)b.in_b1_stride * st->esz; /* the group's planes, in every input and in out alike */
+    const void *srcs[OFFT_HIP_CONV_MAX_IN], *fg[OFFT_HIP_CONV_MAX_IN];
+    for (int k = 0; k < nin; k++) {
+      srcs[k] = (const char *)ins[k] + off;
+      fg[k] = (const char *)filters[k] + (size_t)z0 * (size_t)fl.b1_stride * fesz;
+    }
+    if (be->pass(&a, (const char *)fw.src[1] + (size_t)z0 * (size_t)a.in_b1_stride * st->esz,
+                 (char *)fw.dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * st->esz, s))
+      return -1;
+    if (be->conv_pass_sum(&b, &fl, nin, fg, srcs, (char *)out + off, s)) return -1;
+    if (be->pass(&q, (const char *)iv.src[1] + (size_t)z0 * (size_t)q.in_b1_stride * st->esz,
+                 (char *)iv.dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * st->esz, s))
+      return -1;
+  }
+  return be->pass(&iv.d[2], iv.src[2], iv.dst[2], s) ? -1 : 0;
+}
+
+int offt_hip_convolve_sum_fused(const struct _offt_plan *po) {
+  if (!po || !po->hip_state) return 0;
+  single_sched fw, iv;
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  struct _offt_plan *p = (struct _offt_plan *)po;
+  if (((hip_state *)po->hip_state)->use_pipeline) return 0;
+  single_schedule(p, NULL, -1, &fw);
+  single_schedule(p, NULL, +1, &iv);
+  return conv_sum_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, &fd, &fl);
+}
+
+int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *ins, const void *const *filters, int filter_kind, void *out) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const struct _offt_comm *c = po->comm;
+  double *t = po->t;
+  memset(t, 0, GES * sizeof(double));
+  TEST_NOTE_MESH(po);
+#define SUM_REFUSE(...) do { SET_ERR(__VA_ARGS__); t[ALL] = 99999999.0; return -1; } while (0)
+  if (nin < 1 || nin > OFFT_HIP_CONV_MAX_IN)
+    SUM_REFUSE("offt_hip_execute_convolve_sum: nin = %d (1 ... OFFT_HIP_CONV_MAX_IN = %d inputs)", nin, OFFT_HIP_CONV_MAX_IN);
+  if (filter_kind != OFFT_HIP_FILTER_REAL && filter_kind != OFFT_HIP_FILTER_COMPLEX)
+    SUM_REFUSE("offt_hip_execute_convolve_sum: unknown filter_kind %d (OFFT_HIP_FILTER_REAL or OFFT_HIP_FILTER_COMPLEX)", filter_kind);
+  if (!ins || !filters) SUM_REFUSE("offt_hip_execute_convolve_sum: ins and filters must be arrays of nin pointers (got NULL)");
+  if (!out || (!g_backend && !is_device_ptr(out)))
+    SUM_REFUSE("offt_hip_execute_convolve_sum: the output must be device memory (no host staging for a convolve)%s", out ? "" : " (got NULL)");
+  for (int k = 0; k < nin; k++) {
+    if (!filters[k] || (!g_backend && !is_device_ptr(filters[k])))
+      SUM_REFUSE("offt_hip_execute_convolve_sum: filter %d must be device memory%s", k, filters[k] ? "" : " (got NULL)");
+    if (!ins[k] || (!g_backend && !is_device_ptr(ins[k])))
+      SUM_REFUSE("offt_hip_execute_convolve_sum: input %d must be device memory%s", k, ins[k] ? "" : " (got NULL)");
+    for (int j = 0; j < k; j++)
+      if (ins[j] == ins[k]) SUM_REFUSE("offt_hip_execute_convolve_sum: inputs %d and %d are the same array", j, k);
+  }
+  if (!be->pointwise_sum) SUM_REFUSE("offt_hip_execute_convolve_sum: this backend has no pointwise multiply-and-sum");
+  if ((st->uses_rccl || st->p2p) && G.comm_failed)
+    SUM_REFUSE("offt_hip_execute_convolve_sum: the communicator failed earlier; make a new world (offt_hip_set_world) and plan");
+#undef SUM_REFUSE
+  /* one input, in place: the single-output call itself, bit for bit */
+  if (nin == 1 && out == ins[0]) return offt_hip_execute_convolve(po, out, filters[0], filter_kind);
+  const double t0 = wall_seconds();
+  const int timed = st->async ? 0 : 1;
+  st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros, as after a convolve */
+  if (timed) be->event_record(st->ev0, st->s_compute);
+  const double scale = st->out_scale;
+  int rc = 0;
+  for (int k = 0; k < nin && !rc; k++) rc = half_box_clear(po, ins[k]);
+  if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_sum_single(po, nin, ins, filters, filter_kind, out);
+  if (rc > 0) {
+    /* generic: the forward in place on every input (unscaled), ONE multiply-and-sum sweep into out, the inverse in place on
+     * out with the output scale on its last store.  As in the multi-output call, neither transform ties its buffer to
+     * another's: what a step touches besides the array it is given is the plan's own send, receive and work volumes. */
+    st->out_scale = 1.0;
+    rc = 0;
+    for (int k = 0; k < nin && !rc; k++) {
+      if (!st->use_pipeline) rc = execute_single(po, ins[k], -1);
+      else rc = st->slab_zyx ? execute_slab(po, ins[k]) : execute_pipeline(po, ins[k], -1);
+    }
+    st->out_scale = scale;
+    if (!rc)
+      rc = be->pointwise_sum(nin, (const void *const *)ins, filters, out, st->prec, filter_kind, c->osize[0], c->osize[1], c->osize[2],
+                             c->ostride[0], c->ostride[1], c->ostride[2], st->s_compute) ? -1 : 0;
+    if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, out) : execute_single(po, out, +1);
   }
   st->out_scale = scale;
   st->yx_fused = 0;

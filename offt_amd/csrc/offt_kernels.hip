@@ -375,6 +375,56 @@ pointwise_k(typename vec2<T>::type *data, const void *filter, int n1, int n2, lo
   }
 }
 
+// out = sum_k in_k * H_k over a strided box (offt_hipk_pointwise_sum): ONE sweep, 16 B per lane, non-temporal, the terms added
+// in the order k = 0 ... nin-1.  A lane has loaded its element from every input before its only store, and no other lane
+// touches that element: out may be one of the inputs.  The pointers travel by value and are read through compares on
+// compile-time indices (sum_pick, offt_panel.hpp); k is uniform.
+template <typename T, bool CPLX, int EPL>
+__global__ void __launch_bounds__(256)
+pointwise_sum_k(SumArgs sa, typename vec2<T>::type *out, int n1, int n2, long long s0, long long s1, long long s2, long long rows) {
+  using V2 = typename vec2<T>::type;
+  const int i2 = (blockIdx.x * 256 + threadIdx.x) * EPL;
+  if (i2 >= n2) return;
+  for (long long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const long long i1 = r % n1, i0 = r / n1;
+    const long long o = i0 * s0 + i1 * s1 + (long long)i2 * s2;
+    if constexpr (EPL == 2) {  // (s2 == 1, n2 even, 16-B aligned rows: two float2 as one float4)
+      typedef float f4 __attribute__((ext_vector_type(4)));
+      typedef float f2v __attribute__((ext_vector_type(2)));
+      f4 acc = f4{0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < sa.nin; k++) {
+        const V2 *in = reinterpret_cast<const V2 *>(sum_pick(sa.src, k));
+        const void *filter = sum_pick(sa.filter, k);
+        const f4 x = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(in + o));
+        if constexpr (CPLX) {
+          const f4 h = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(reinterpret_cast<const V2 *>(filter) + o));
+          acc += f4{x.x * h.x - x.y * h.y, x.x * h.y + x.y * h.x, x.z * h.z - x.w * h.w, x.z * h.w + x.w * h.z};
+        } else {
+          const f2v h = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(reinterpret_cast<const T *>(filter) + o));
+          acc += f4{x.x * h.x, x.y * h.x, x.z * h.y, x.w * h.y};
+        }
+      }
+      __builtin_nontemporal_store(acc, reinterpret_cast<f4 *>(out + o));
+    } else {
+      V2 acc;
+      acc.x = 0; acc.y = 0;
+      for (int k = 0; k < sa.nin; k++) {
+        const V2 *in = reinterpret_cast<const V2 *>(sum_pick(sa.src, k));
+        const void *filter = sum_pick(sa.filter, k);
+        const V2 x = gload(in + o);
+        if constexpr (CPLX) {
+          const V2 h = gload(reinterpret_cast<const V2 *>(filter) + o);
+          acc.x += x.x * h.x - x.y * h.y; acc.y += x.x * h.y + x.y * h.x;
+        } else {
+          const T h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + o);
+          acc.x += x.x * h; acc.y += x.y * h;
+        }
+      }
+      gstore(out + o, acc);
+    }
+  }
+}
+
 // zero a strided 3-D block outside the kept sub-box [0,k0) x [0,k1) x [0,k2) (offt_hipk_zero_outside): rows along i2, one
 // workgroup row per (i0, i1).  W = scalars of type S per 16-B store; VEC: the rows are unit-stride and 16-B aligned, a lane
 // clears 16 B at W-scalar boundaries (the first store of a row that starts inside the kept part is split into scalars)
@@ -507,6 +557,8 @@ void build_registry() {
   reg_conv_mixed_f32();
   reg_conv_oop_mixed_f64();
   reg_conv_oop_mixed_f32();
+  reg_conv_sum_f64();
+  reg_conv_sum_f32();
   reg_half_f64();
   reg_half_f32();
   reg_half_real_f64();
@@ -1961,6 +2013,66 @@ int pointwise_launch(const char *who, const void *in, void *out, bool oop, const
   HIPK_CHECK(hipGetLastError());
   return 0;
 }
+
+// the multi-input instance for (fwd, f), or nullptr: pick_conv's conditions; the power-of-two lengths only, whatever
+// f->mixed says (no mixed-radix instance exists)
+Variant *pick_conv_sum(const offt_pass_desc *d, const offt_filter_desc *f, bool keep) {
+  if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
+  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
+  if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || f->axis_stride != 1)
+    return nullptr;
+  if (d->half && d->half != 3) return nullptr;
+  Variant *v = find_variant(VariantKey{d->n, d->precision, true, true, Role::ConvSum, keep, d->half});
+  return v && !v->mixed ? v : nullptr;
+}
+
+bool fill_sum_args(const char *who, SumArgs &sa, int nin, const void *const *srcs, const void *const *filters) {
+  if (nin < 1 || nin > OFFT_CONV_SUM_MAX) { snprintf(g_err, sizeof g_err, "%s: nin = %d (1 ... %d inputs)", who, nin, OFFT_CONV_SUM_MAX); return false; }
+  if (!srcs || !filters) { snprintf(g_err, sizeof g_err, "%s: needs the arrays of %d sources and filters (got NULL)", who, nin); return false; }
+  memset(&sa, 0, sizeof sa);
+  sa.nin = nin;
+  for (int k = 0; k < nin; k++) {
+    if (!srcs[k] || !filters[k]) { snprintf(g_err, sizeof g_err, "%s: source or filter %d is NULL", who, k); return false; }
+    sa.src[k] = srcs[k]; sa.filter[k] = filters[k];
+  }
+  return true;
+}
+
+int pointwise_sum_launch(const char *who, int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind,
+                         int n0, int n1, int n2, long long s0, long long s1, long long s2, void *stream) {
+  if (kind != OFFT_FILTER_REAL && kind != OFFT_FILTER_COMPLEX) { snprintf(g_err, sizeof g_err, "%s: bad filter kind %d", who, kind); return -1; }
+  if (precision != OFFT_PREC_F64 && precision != OFFT_PREC_F32) { snprintf(g_err, sizeof g_err, "%s: bad precision %d", who, precision); return -1; }
+  SumArgs sa;
+  if (!fill_sum_args(who, sa, nin, ins, filters)) return -1;
+  if (!out) { snprintf(g_err, sizeof g_err, "%s: out is NULL", who); return -1; }
+  if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
+  // rows along the smallest stride
+  int n[3] = {n0, n1, n2};
+  long long st[3] = {s0, s1, s2};
+  for (int a = 0; a < 2; a++)
+    for (int b = 0; b < 2 - a; b++)
+      if (st[b] < st[b + 1]) { int tn = n[b]; n[b] = n[b + 1]; n[b + 1] = tn; long long ts = st[b]; st[b] = st[b + 1]; st[b + 1] = ts; }
+  const long long rows = (long long)n[0] * n[1];
+  const bool f32 = precision == OFFT_PREC_F32;
+  // two single-precision elements per lane: unit stride, whole pairs, 16-B aligned rows and bases
+  bool pair = f32 && st[2] == 1 && !(n[2] & 1) && !(st[1] & 1) && !(st[0] & 1) && !((uintptr_t)out & 15);
+  for (int k = 0; k < nin; k++)
+    pair = pair && !((uintptr_t)ins[k] & 15) && !((uintptr_t)filters[k] & (kind == OFFT_FILTER_COMPLEX ? 15 : 7));
+  const int epl = pair ? 2 : 1;
+  const unsigned gx = (unsigned)((n[2] / epl + 255) / 256);
+  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
+  hipStream_t sm = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const bool cx = kind == OFFT_FILTER_COMPLEX;
+#define SUM(T, CPLX, EPL) \
+  hipLaunchKernelGGL((pointwise_sum_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, sa, (typename vec2<T>::type *)out, n[1], n[2], st[0], st[1], st[2], rows)
+  if (pair) { if (cx) SUM(float, true, 2); else SUM(float, false, 2); }
+  else if (cx) FOR_PREC(precision, SUM(T, true, 1));
+  else FOR_PREC(precision, SUM(T, false, 1));
+#undef SUM
+  HIPK_CHECK(hipGetLastError());
+  return 0;
+}
 }  // namespace
 
 int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false) != nullptr; }
@@ -1989,6 +2101,40 @@ int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind,
 int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
                             long long s1, long long s2, void *stream) {
   return pointwise_launch("offt_hipk_pointwise_oop", in, out, true, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
+}
+
+// ---- multi-input convolution (offt_hipk.h) ----
+int offt_hipk_conv_has_fused_sum(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv_sum(fwd, f, false) != nullptr; }
+const char *offt_hipk_conv_sum_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) {
+  return conv_kernel_name(pick_conv_sum(fwd, f, false));
+}
+int offt_hipk_conv_pass_sum(const offt_pass_desc *d, const offt_filter_desc *f, int nin, const void *const *filters, const void *const *srcs,
+                            void *dst, void *stream) {
+  const char *who = "offt_hipk_conv_pass_sum";
+  SumArgs sa;
+  if (!fill_sum_args(who, sa, nin, srcs, filters)) return -1;
+  if (!dst) { snprintf(g_err, sizeof g_err, "%s: dst is NULL", who); return -1; }
+  Variant *v = pick_conv_sum(d, f, d && d->out_keep);
+  if (!v && d && d->out_keep) v = pick_conv_sum(d, f, false);
+  if (!v) {
+    snprintf(g_err, sizeof g_err, "%s: no multi-input fused convolution kernel for this descriptor (n=%d)", who, d ? d->n : 0);
+    return -1;
+  }
+  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  PassArgs a = pass_args(d, v->cols, true);
+  ConvArgs fa;
+  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
+  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
+  void *args[5] = {(void *)&a, (void *)&fa, (void *)&sa, (void *)&dst, (void *)&tb.full};
+  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
+                args, (hipStream_t)stream);
+}
+
+int offt_hipk_pointwise_sum(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,
+                            int n2, long long s0, long long s1, long long s2, void *stream) {
+  return pointwise_sum_launch("offt_hipk_pointwise_sum", nin, ins, filters, out, precision, kind, n0, n1, n2, s0, s1, s2, stream);
 }
 
 int offt_hipk_zero_outside(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1,

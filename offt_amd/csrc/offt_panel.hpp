@@ -930,6 +930,296 @@ fft_conv_oop_half_panel_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *
 }
 
 // ---------------------------------------------------------------------------
+// Multi-input spectral convolution (offt_hipk_conv_pass_sum): out = ifft( sum_k H_k . fft(x_k) ) on whole lines.  The
+// transpose of the out-of-place kernels above: several sources, one destination.  By linearity the K inverse transforms are
+// one, and the sum lives in registers between the forward stages and the inverse stages -- conv_body with its first half
+// in a loop over the inputs.  Per workgroup, for k = 0 ... nin-1: load the panel from src[k] (conv_body's loads), forward
+// stages, times H_k in the last stage's register order, added into acc[E] in that order (k ascending: the same bits on
+// every run); then conjugate, the one LDS round trip, the stages again, conjugate, scale, store to dst at the load offsets.
+// In place on any ONE source: a workgroup owns whole lines and has loaded them from every source before its only stores.
+// The pointers travel by value.  k is workgroup-uniform, and the two tables are read through a chain of compares on
+// compile-time indices (sum_pick), so that they stay in scalar registers: indexed by k they would be copied to scratch.
+#define OFFT_CONV_SUM_MAX 8
+struct SumArgs {
+  const void *src[OFFT_CONV_SUM_MAX];
+  const void *filter[OFFT_CONV_SUM_MAX];
+  int nin;
+};
+__device__ __forceinline__ const void *sum_pick(const void *const (&p)[OFFT_CONV_SUM_MAX], int k) {
+  const void *r = p[0];
+  static_for<1, OFFT_CONV_SUM_MAX>([&](auto ii) {
+    if (k == decltype(ii)::value) r = p[decltype(ii)::value];
+  });
+  return r;
+}
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP, bool HALF = false>
+__device__ __forceinline__ void conv_sum_body(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>::type *dst,
+                                              const typename vec2<T>::type *twq) {
+  using V2 = typename vec2<T>::type;
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int TPL = Cfg::TPL, NT = Cfg::NT, NSTAGE = Cfg::NSTAGE;
+  constexpr int LSTRIDE = Cfg::LSTRIDE;
+  constexpr bool SWZ = Cfg::SWZ;
+  constexpr int PS = SWZ ? Cfg::SWZSHIFT : Cfg::PADSHIFT;
+  static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
+  static_assert(E % R0 == 0 && E % R1 == 0 && E % R2 == 0 && N % E == 0, "bad E");
+  static_assert(NSTAGE > 1, "the round trip goes through the exchange image");
+  constexpr int RL = NSTAGE == 3 ? R2 : R1;  // radix of the last stage
+  constexpr int LRL = ilog2(RL);
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T *exs = reinterpret_cast<T *>(smem);
+  V2 *exv = reinterpret_cast<V2 *>(smem);
+  V2 *tw = reinterpret_cast<V2 *>(smem + Cfg::TW_OFF);
+  V2 *tw1 = reinterpret_cast<V2 *>(smem + Cfg::T1_OFF);
+
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Cfg::QT; i += NT) tw[i] = twq[i];
+  if constexpr (Cfg::USE_T1) {
+    constexpr int M1 = N / (R0 * R1);
+    for (int i = tid; i < Cfg::T1N; i += NT) {
+      const int t = i / R0 + 1, k = i - (t - 1) * R0;
+      tw1[i] = twq[k * M1 * t];
+    }
+  }
+  __syncthreads();  // the twiddle tables are visible (once, ahead of the loop over the inputs)
+
+  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const int cp = bid % (unsigned)a.ncp;
+  const unsigned rest = bid / (unsigned)a.ncp;
+  const int b1 = rest % (unsigned)a.nb1;
+  const int b2 = rest / (unsigned)a.nb1;
+  const int c0 = cp * COLS;
+  const int j = tid % TPL, c = tid / TPL;
+  const bool valid = (c0 + c) < a.ncols;
+  const long long lo = (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col + (long long)j * a.in_axis;
+  const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col + (long long)j * f.axis;
+
+  // a wave owns whole columns when TPL divides 64: its exchanges need no workgroup barrier (see panel_body)
+  constexpr bool WAVE_COLS = (64 % TPL == 0) && (NT % 64 == 0);
+  auto xsync = [&]() {
+    if constexpr (WAVE_COLS) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    } else {
+      __syncthreads();
+    }
+  };
+  auto at = [&](int i) { return c * LSTRIDE + padidx<SWZ, PS>(i); };
+
+  cx<T> v[E];
+
+  // conv_body's stages (contiguous / contiguous), ending in the last stage's register order:
+  // v[u RL + bitrev(t)] holds line index j + u TPL + t N/RL
+  auto stages = [&](auto upper_zero) {
+    static_for<0, NSTAGE>([&](auto sidx) {
+      constexpr int s = decltype(sidx)::value;
+      constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
+      constexpr int Ns = (s == 0) ? 1 : ((s == 1) ? R0 : R0 * R1);
+      constexpr int NB = E / R;
+      constexpr int LR = ilog2(R);
+      if constexpr (s > 0) {
+        constexpr int M = N / (Ns * R);
+        static_for<0, NB>([&](auto uu) {
+          constexpr int u = decltype(uu)::value;
+          const int q = j + u * TPL;
+          const int km = (q & (Ns - 1)) * M;
+          static_for<1, R>([&](auto tt) {
+            constexpr int t = decltype(tt)::value;
+            T cr, ci;
+            if constexpr (s == 1 && Cfg::USE_T1) {
+              const V2 w = tw1[(t - 1) * R0 + (q & (R0 - 1))];
+              cr = w.x; ci = w.y;
+            } else if constexpr (Cfg::USE_HALF) {
+              const int e = km * t;
+              const V2 w = tw[e & (N / 2 - 1)];
+              const unsigned sm = ((unsigned)e << (32 - ilog2(N))) & 0x80000000u;
+              cr = xor_sign(w.x, sm); ci = xor_sign(w.y, sm);
+            } else {
+              const int e = km * t;
+              const int qd = e / (N / 4);
+              const V2 w = tw[e & (N / 4 - 1)];
+              cr = (qd & 1) ? w.y : w.x;
+              ci = (qd & 1) ? -w.x : w.y;
+              if (qd & 2) { cr = -cr; ci = -ci; }
+            }
+            const cx<T> x = v[u * R + t];
+            v[u * R + t] = cx<T>{x.x * cr - x.y * ci, x.x * ci + x.y * cr};
+          });
+        });
+      }
+      static_for<0, NB>([&](auto uu) { dft_reg<T, R, s == 0 && decltype(upper_zero)::value>(&v[decltype(uu)::value * R]); });
+      if constexpr (s < NSTAGE - 1) {
+        constexpr int Rn = (s == 0) ? R1 : R2;
+        auto wr_idx = [&](int u, int t) {
+          const int q = j + u * TPL;
+          const int k = q & (Ns - 1);
+          return at((q - k) * R + k + t * Ns);
+        };
+        auto rd_idx = [&](int u, int t) { return at(j + u * TPL + t * (N / Rn)); };
+        if constexpr (s > 0) xsync();  // previous exchange's reads done
+        if constexpr (SPLIT) {
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].x;
+          });
+          xsync();
+          T re[E];
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            re[decltype(ii)::value] = exs[rd_idx(u, t)];
+          });
+          xsync();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].y;
+          });
+          xsync();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], exs[rd_idx(u, t)]};
+          });
+        } else {
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            const cx<T> x = v[u * R + bitrev(t, LR)];
+            V2 w; w.x = x.x; w.y = x.y;
+            exv[wr_idx(u, t)] = w;
+          });
+          xsync();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            const V2 w = exv[rd_idx(u, t)];
+            v[decltype(ii)::value] = cx<T>{w.x, w.y};
+          });
+        }
+      }
+    });
+  };
+
+  // acc[r] += v[r] * H_k[n], r the last stage's register order; filter values are read once: non-temporal
+  cx<T> acc[E];
+  static_for<0, E>([&](auto ii) { acc[decltype(ii)::value] = cx<T>{0, 0}; });
+  auto filt = [&](const void *filter, auto complex_filter) {
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int cn = u * TPL + t * (N / RL);
+      constexpr int r = u * RL + bitrev(t, LRL);
+      const long long off = fb + (long long)cn * f.axis;
+      const cx<T> x = v[r];
+      if constexpr (decltype(complex_filter)::value) {
+        V2 h;
+        h.x = 0; h.y = 0;
+        if (valid) h = gload(reinterpret_cast<const V2 *>(filter) + off);
+        const T pr = x.x * h.x - x.y * h.y, pi = x.x * h.y + x.y * h.x;
+        acc[r] = cx<T>{acc[r].x + pr, acc[r].y + pi};
+      } else {
+        T h = 0;
+        if (valid) h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + off);
+        acc[r] = cx<T>{acc[r].x + x.x * h, acc[r].y + x.y * h};
+      }
+    });
+  };
+
+#pragma nounroll
+  for (int k = 0; k < sa.nin; k++) {
+    const V2 *line = reinterpret_cast<const V2 *>(sum_pick(sa.src, k)) + lo;
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      constexpr int cn = u * TPL + t * (N / R0);
+      V2 val;
+      val.x = 0; val.y = 0;
+      if constexpr (!(HALF && cn >= N / 2)) {
+        if (valid) val = gload(line + (long long)cn * a.in_axis);
+      }
+      v[decltype(ii)::value] = cx<T>{val.x, val.y};
+    });
+    stages(std::integral_constant<bool, HALF>{});
+    const void *filter = sum_pick(sa.filter, k);
+    if (f.cplx) filt(filter, std::true_type{});
+    else filt(filter, std::false_type{});
+    xsync();  // this input's last exchange reads done: before the next input's first exchange write, or the round trip's
+  }
+
+  // the sum, conjugated (the inverse as conj(F(conj(.)))), through the exchange image: from the last stage's order back
+  // into the load distribution
+  if constexpr (SPLIT) {
+    T re[E];
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      exs[at(j + u * TPL + t * (N / RL))] = acc[u * RL + bitrev(t, LRL)].x;
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      re[decltype(ii)::value] = exs[at(j + u * TPL + t * (N / R0))];
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      exs[at(j + u * TPL + t * (N / RL))] = -acc[u * RL + bitrev(t, LRL)].y;
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], exs[at(j + u * TPL + t * (N / R0))]};
+    });
+  } else {
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      const cx<T> x = acc[u * RL + bitrev(t, LRL)];
+      V2 w; w.x = x.x; w.y = -x.y;
+      exv[at(j + u * TPL + t * (N / RL))] = w;
+    });
+    xsync();
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      const V2 w = exv[at(j + u * TPL + t * (N / R0))];
+      v[decltype(ii)::value] = cx<T>{w.x, w.y};
+    });
+  }
+  xsync();  // the round trip's reads done before the first exchange of the second half writes
+
+  stages(std::false_type{});
+
+  V2 *sline = dst + lo;
+  const T sc = (T)a.scale;
+  static_for<0, E>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+    constexpr int cn = u * TPL + t * (N / RL);
+    if constexpr (HALF && cn >= N / 2) return;
+    const cx<T> x = v[u * RL + bitrev(t, LRL)];
+    V2 w;
+    w.x = x.x * sc;
+    w.y = -x.y * sc;
+    if (valid) gstore_p<KEEP>(sline + (long long)cn * a.in_axis, w);
+  });
+}
+
+// (v[E] and acc[E] live together, under the butterfly temporaries: with 64 data VGPRs -- 16 points in double, 32 in single
+//  precision -- an instance compiled for 2 waves per SIMD spills (8 ... 570 B per lane), so those are compiled for the fewest
+//  waves their workgroup admits, 1 per SIMD at up to 256 threads, and take the accumulator from the 512 registers a lone wave
+//  has; the smaller ones are bounded like the fused convolution)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+constexpr int conv_sum_wps() {
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  return Cfg::DATA_VGPR >= 64 ? Cfg::WPS_MIN : conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>();
+}
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (conv_sum_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_sum_panel_k(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>::type *dst, const typename vec2<T>::type *twq) {
+  conv_sum_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP>(a, f, sa, dst, twq);
+}
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (conv_sum_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_sum_half_panel_k(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>::type *dst, const typename vec2<T>::type *twq) {
+  conv_sum_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP, true>(a, f, sa, dst, twq);
+}
+
+// ---------------------------------------------------------------------------
 // Mixed-radix panel kernel: the same three-stage register/LDS Stockham scheme for
 // lengths N = R0 * R1 * R2 whose radices are products of small primes (2, 3, 5 with hand-written
 // butterflies, 7, 11, 13 as direct DFTs): 768 = 12 x 8 x 8, 1000 = 10 x 10 x 10, 896 = 8 x 8 x 14, ...  Differences from fft_panel_k:
@@ -1622,6 +1912,7 @@ enum class Role {
   TW4,      // four-step twiddles on the stores (offt_pass_desc::tw4): the first sub-pass of a long line
   Conv,     // fused convolution in place (offt_hipk_conv_pass): fft_conv_panel_k, fft_conv_half_panel_k and their panelx twins
   ConvOop,  // ... with a separate store base (offt_hipk_conv_pass_oop): fft_conv_oop_panel_k, fft_conv_oop_half_panel_k, ...
+  ConvSum,  // several sources summed into one destination (offt_hipk_conv_pass_sum): fft_conv_sum_panel_k, fft_conv_sum_half_panel_k
 };
 // column-pair instances (T = f32x2) are kept under their own precision so that the one-column variants and their ids stay
 // what they were
@@ -1638,7 +1929,7 @@ struct VariantKey {
   Role role;
   bool keep;       // KEEP instantiation (offt_pass_desc::out_keep): default-policy stores.  (The TW4 instance is compiled with
                    // TW4_KEEP but registered without: nobody asks for a TW4 twin.)
-  int half;        // the offt_pass_desc::half it implements: 0 full lines; 1, 2; Conv / ConvOop: 3
+  int half;        // the offt_pass_desc::half it implements: 0 full lines; 1, 2; Conv / ConvOop / ConvSum: 3
   bool operator==(const VariantKey &o) const {
     return n == o.n && prec == o.prec && inc == o.inc && outc == o.outc && role == o.role && keep == o.keep && half == o.half;
   }
@@ -1819,6 +2110,22 @@ void reg_variant_conv_oop() {
   add(true, 3, (const void *)fft_conv_oop_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
 }
 
+// multi-input fused convolution (fft_conv_sum_panel_k, fft_conv_sum_half_panel_k; offt_reg_conv_sum_*.hip): shapes of their
+// own (the accumulator doubles the data registers: fewer columns where that buys the register budget), full lines and half
+// lines, each plain and with cache-keeping stores
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variant_conv_sum() {
+  const VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
+  auto add = [&](bool keep, int half, const void *fn) {
+    add_variant(VariantKey{N, prec_of<T>(), true, true, Role::ConvSum, keep, half}, s, fn, half ? "fft_conv_sum_half_panel_k" : "fft_conv_sum_panel_k",
+                half ? " multi-input convolution on half lines" : " multi-input convolution");
+  };
+  add(false, 0, (const void *)fft_conv_sum_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
+  add(true, 0, (const void *)fft_conv_sum_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
+  add(false, 3, (const void *)fft_conv_sum_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
+  add(true, 3, (const void *)fft_conv_sum_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
+}
+
 // mixed-radix (2^a 3^b 5^c) panel kernel: TPL threads per line instead of elements per thread.
 // FLAV limits which (in_contig, out_contig) flavours are instantiated at all (compile time), defmask says for
 // which of them this variant is the default.
@@ -1928,6 +2235,8 @@ void reg_conv_mixed_f64();
 void reg_conv_mixed_f32();
 void reg_conv_oop_mixed_f64();
 void reg_conv_oop_mixed_f32();
+void reg_conv_sum_f64();
+void reg_conv_sum_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();

@@ -22,11 +22,20 @@ offt_hip_execute_convolve calls and with the multi call with the option at 0 (th
 option existed), MIXED_REPS times each after a warm-up.  The line reports min and median of all three, the ratios against
 both baselines, each baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5 (376 / 504 for K = 3,
 against either baseline).  multi:mixed:half:N does so on a pruned half-box plan (OFFT_HIP_OPT_HALF_MIXED, an N/2 box).
-usage: conv_probe.py [mixed:|multi:|multi:mixed:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+A spec with the prefix sum: measures offt_hip_execute_convolve_sum with K = 3 real filters and out = ins[0] against what a
+caller does without it (three offt_hip_execute_convolve calls on the same plan and buffers plus two in-place torch adds) and
+against the call's own generic route (a second plan made under the HIP backend with conv_pass_sum withheld, a seam of
+tests/liboffthip_test.so, which the probe then loads instead of the product; not a public option).  The three ALTERNATE
+after a warm-up, MIXED_REPS times each, and the line reports min and median of all three, the ratios against both, each
+baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5 (344 / 600 and 344 / 472 for K = 3).
+sum:half:N does so on a pruned half-box plan (an N/2 box).
+usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
        (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768;
         the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512;
         the multi:mixed: set of profiles/conv_multi_mixed.txt: multi:mixed:768 multi:mixed:f32:768 multi:mixed:1000
-        multi:mixed:f32:1000 multi:mixed:half:768)"""
+        multi:mixed:f32:1000 multi:mixed:half:768;
+        the sum: set of profiles/conv_sum.txt: sum:512 sum:1024 sum:f32:1024 sum:r2c:512 sum:half:512, and for the shorter
+        x lengths sum:64 sum:128 sum:256 sum:f32:256 sum:f32:512)"""
 import ctypes as C
 import os
 import sys
@@ -37,6 +46,9 @@ import torch  # noqa: E402
 
 from offt_amd import api  # noqa: E402
 
+if any(a.startswith("sum:") for a in sys.argv[1:]):
+    # the sum: specs time the generic route as well, which needs the build with the test seams (the same kernel objects)
+    api.use_library(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "liboffthip_test.so"))
 L = api.lib()
 REPS = int(os.environ.get("CONV_PROBE_REPS", "5"))
 MIXED_REPS = int(os.environ.get("CONV_PROBE_MIXED_REPS", "20"))
@@ -58,6 +70,82 @@ def model(n, esz, r2c):
     return a, a + mul, 2 * z + 2 * 2 * vh + mul
 
 
+def probe_sum(rest, zg):
+    """sum:[half:][f64|f32|r2c:]N -- offt_hip_execute_convolve_sum with K = 3 real filters and out = ins[0]"""
+    K = 3
+    half = rest.startswith("half:")
+    kind, _, n_s = rest[(5 if half else 0):].rpartition(":")
+    n = int(n_s)
+    prec = api.F32 if kind == "f32" else api.F64
+    r2c = kind == "r2c"
+    T = api.lib()
+    T.offt_hip_test_hip_backend_no_conv_sum.restype = C.c_void_p
+    T.offt_hip_test_set_backend.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    plans = {}
+    for name in ("generic", "sum"):  # the plan made under the table without conv_pass_sum first, then the product's own
+        T.offt_hip_test_set_backend(T.offt_hip_test_hip_backend_no_conv_sum() if name == "generic" else None, 0, 1)
+        po = plans[name] = api.offt_3d_init(n, n, n, precision=prec, is_r2c=int(r2c))
+        if zg is not None:
+            T.offt_hip_set_option(po, OPT_ZGROUP_MIB, zg)
+        if half:
+            api.offt_hip_set_half_box(po, True)
+    po = plans["sum"]
+    td = torch.float32 if prec == api.F32 else torch.float64
+    ne = api.local_elems(po)
+    ins = [torch.zeros(ne * 2, dtype=td, device="cuda") for _ in range(K)]
+    for x in ins:
+        T.offt_hip_fill_input(po, x.data_ptr(), 1)
+    Hs = [torch.rand(ne, dtype=td, device="cuda") * (1.0 / (K * float(n) ** 3)) for _ in range(K)]  # keeps the field bounded
+    ip, fp = [x.data_ptr() for x in ins], [h.data_ptr() for h in Hs]
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def run(fn):
+        ev[0].record()
+        fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) * 1e-3
+
+    def base():  # what a caller does without the call: K convolves and K - 1 add sweeps of their own
+        for x, h in zip(ip, fp):
+            api.offt_hip_execute_convolve(po, x, h, api.FILTER_REAL)
+        for x in ins[1:]:
+            ins[0].add_(x)
+
+    def sm():
+        api.offt_hip_execute_convolve_sum(po, ip, fp, ip[0], api.FILTER_REAL)
+
+    def gen():
+        api.offt_hip_execute_convolve_sum(plans["generic"], ip, fp, ip[0], api.FILTER_REAL)
+
+    t = {"sum": [], "base": [], "generic": []}
+    for rep_i in range(2 + MIXED_REPS):
+        for name, fn in (("sum", sm), ("base", base), ("generic", gen)):
+            dt = run(fn)
+            if rep_i >= 2:
+                t[name].append(dt)
+    mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+    fused1, fusedk, fusedg = api.offt_hip_convolve_fused(po), api.offt_hip_convolve_sum_fused(po), api.offt_hip_convolve_sum_fused(plans["generic"])
+    tag = f"{'r2c f64' if r2c else ('f32' if prec == api.F32 else 'f64')} {n}^3 K={K}"
+    if half:
+        tag += f" half box {n // 2}^3 [{'pruned' if api.offt_hip_half_box_pruned(po) else 'fallback'}]"
+    # bytes per point, f64, complex plan, full lines (DESIGN.md 4.5): baseline 168 K + 48 (K - 1), generic 120 K + 112, fused 88 K + 80
+    mb, mg, mf = 168 * K + 48 * (K - 1), 120 * K + 112, 88 * K + 80
+    print(f"sum: {tag}: sum [{'fused' if fusedk else 'generic'}] min {mn['sum'] * 1e3:.3f} ms median {md['sum'] * 1e3:.3f} ms  "
+          f"{K} calls + {K - 1} adds [{'fused' if fused1 else 'unfused'}] min {mn['base'] * 1e3:.3f} ms median {md['base'] * 1e3:.3f} ms  "
+          f"sum without conv_pass_sum [{'fused' if fusedg else 'generic'}] min {mn['generic'] * 1e3:.3f} ms median {md['generic'] * 1e3:.3f} ms  "
+          f"sum/base min {mn['sum'] / mn['base']:.3f} median {md['sum'] / md['base']:.3f}  "
+          f"sum/generic min {mn['sum'] / mn['generic']:.3f} median {md['sum'] / md['generic']:.3f}  "
+          f"base spread {md['base'] / mn['base'] - 1:.3f}  generic spread {md['generic'] / mn['generic'] - 1:.3f}  "
+          f"byte model (complex, full lines) fused/base {mf / mb:.3f} fused/generic {mf / mg:.3f} generic/base {mg / mb:.3f}  "
+          f"n {MIXED_REPS}  zgroup_mib {T.offt_hip_get_option(po, OPT_ZGROUP_MIB)}", flush=True)
+    for p in plans.values():
+        api.offt_3d_fin(p)
+    del ins, Hs
+    torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     zg = None
@@ -68,6 +156,9 @@ def main():
     specs = args or ["1024", "f32:1024", "r2c:512", "mixed:768", "mixed:f32:768", "mixed:1000", "mixed:f32:1000", "mixed:half:768"]
     torch.cuda.set_device(0)
     for spec in specs:
+        if spec.startswith("sum:"):
+            probe_sum(spec[4:], zg)
+            continue
         multi = spec.startswith("multi:")
         mixed = spec.startswith("mixed:") or multi  # (the same grammar behind the prefix)
         multi_mixed = multi and spec[6:].startswith("mixed:")
