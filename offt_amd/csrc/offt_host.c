@@ -1651,7 +1651,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
       if (st->half_box) st->half_pruned = half_can_prune(po);
       break;
     case OFFT_HIP_OPT_CONV_MIXED: st->opt.conv_mixed = value != 0; break; /* read by every convolve (conv_fused_route) */
-    case OFFT_HIP_OPT_CONV_MULTI_MIXED: st->opt.conv_multi_mixed = value != 0; break; /* read by every multi-output convolve (conv_multi_fused_route) */
+    case OFFT_HIP_OPT_CONV_MULTI_MIXED: st->opt.conv_multi_mixed = value != 0; break; /* read by every multi-output convolve (conv_fused_route, CONV_OOP) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
@@ -2982,15 +2982,112 @@ void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int directi
 /* ------------------------------------------------------------------------- */
 /* spectral convolution: forward, filter, inverse in one call                 */
 /* ------------------------------------------------------------------------- */
+/* Three calls share everything here but their multiply: offt_hip_execute_convolve (in place), ..._convolve_multi (one
+ * forward, an out-of-place multiply and an inverse per output) and ..._convolve_sum (a forward per input, one
+ * multiply-and-sum, one inverse).  A call is: conv_begin, its refusals, conv_ready, conv_enter, the fused route of one rank
+ * (execute_convolve_single, execute_convolve_sum_single: conv_fused_route decides, conv_plane_groups runs the y / fused / y launches) or else the generic
+ * one (conv_forward, the call's own multiply, conv_inverse), conv_leave. */
+typedef enum { CONV_INPLACE, CONV_OOP, CONV_SUM } conv_flavour;
+
+/* the fused launch of one plane group: in place on `dst` (filters[0]); from srcs[0] into `dst` (filters[0]); or the gather of
+ * nin sources, each times its filter, into `dst` */
+typedef struct conv_launch {
+  conv_flavour flavour;
+  int nin;
+  const void *const *srcs;
+  void *dst;
+  const void *const *filters;
+} conv_launch;
+
+#define CONV_REFUSE(po, ...) do { SET_ERR(__VA_ARGS__); (po)->t[ALL] = 99999999.0; return -1; } while (0)
+
+static void conv_begin(struct _offt_plan *po) {
+  memset(po->t, 0, GES * sizeof(double));
+  TEST_NOTE_MESH(po);
+}
+
+static int conv_check_kind(struct _offt_plan *po, const char *who, int filter_kind) {
+  if (filter_kind != OFFT_HIP_FILTER_REAL && filter_kind != OFFT_HIP_FILTER_COMPLEX)
+    CONV_REFUSE(po, "%s: unknown filter_kind %d (OFFT_HIP_FILTER_REAL or OFFT_HIP_FILTER_COMPLEX)", who, filter_kind);
+  return 0;
+}
+
+/* refuse an array of the caller's that is NULL or host memory: `role` ("the data", or "filter" with its index k >= 0), `note`
+ * after the sentence, and whether a NULL is named as such */
+#define CONV_NO_STAGING " (no host staging for a convolve)"
+static int conv_need_device(struct _offt_plan *po, const char *who, const void *p, const char *role, int k, const char *note, int say_null) {
+  if (p && (g_backend || is_device_ptr(p))) return 0;
+  char what[32];
+  if (k < 0) snprintf(what, sizeof what, "%s", role);
+  else snprintf(what, sizeof what, "%s %d", role, k);
+  CONV_REFUSE(po, "%s: %s must be device memory%s%s", who, what, note, say_null && !p ? " (got NULL)" : "");
+}
+
+/* the n filters and the n arrays of `role` ("output", "input") of the multi calls: device memory, no array twice */
+static int conv_need_arrays(struct _offt_plan *po, const char *who, int n, const void *const *filters, void *const *arrs, const char *role) {
+  for (int k = 0; k < n; k++) {
+    if (conv_need_device(po, who, filters[k], "filter", k, "", 1) || conv_need_device(po, who, arrs[k], role, k, "", 1)) return -1;
+    for (int j = 0; j < k; j++)
+      if (arrs[j] == arrs[k]) CONV_REFUSE(po, "%s: %ss %d and %d are the same array", who, role, j, k);
+  }
+  return 0;
+}
+
+/* the last refusals: a backend without the call's multiply (`multiply` names it), a communicator that failed earlier */
+static int conv_ready(struct _offt_plan *po, const char *who, int has_multiply, const char *multiply) {
+  hip_state *st = (hip_state *)po->hip_state;
+  if (!has_multiply) CONV_REFUSE(po, "%s: this backend has no %s", who, multiply);
+  if ((st->uses_rccl || st->p2p) && G.comm_failed)
+    CONV_REFUSE(po, "%s: the communicator failed earlier; make a new world (offt_hip_set_world) and plan", who);
+  return 0;
+}
+
+/* from here to conv_leave the call launches: the clock (returned), and unless the plan is asynchronous the first of the two
+ * events of offt_hip_last_device_seconds */
+static double conv_enter(struct _offt_plan *po) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const double t0 = wall_seconds();
+  st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros after a convolve */
+  if (!st->async) st->be->event_record(st->ev0, st->s_compute);
+  return t0;
+}
+
+/* t0: of conv_enter; rc: what the launches returned.  The call's return value, t[ALL] set either way. */
+static int conv_leave(struct _offt_plan *po, double t0, int rc) {
+  hip_state *st = (hip_state *)po->hip_state;
+  double *t = po->t;
+  st->yx_fused = 0;
+  if (!st->async) st->be->event_record(st->ev1, st->s_compute);
+  if (rc) {
+    if (st->uses_rccl) comm_fail(st);
+    t[ALL] = 99999999.0;
+    return -1;
+  }
+  if (st->async) { t[ALL] = wall_seconds() - t0; return 0; }
+  if (wait_compute(st)) { t[ALL] = 99999999.0; return -1; }
+  st->last_dev_s = 1e-3 * st->be->event_ms(st->ev0, st->ev1);
+  for (int i = 0; i < 3; i++) st->pass_s[i] = 0.0;
+  t[ALL] = wall_seconds() - t0;
+  return 0;
+}
+
 /* The single-rank fused route: the forward's first two launches, ONE launch for the forward's last pass + the filter + the
  * inverse's first pass (they work on the same lines: the caller's array in z-y-x, the scratch volume V in the rotated
  * y-z-x layout), the inverse's last two launches.  *fd receives the fused launch's descriptor (the forward's last pass;
  * loads and stores through its input side) and *fl the filter's addressing (that pass's output side).  0: this plan and
- * backend have no fused route (the caller takes the unfused one). */
-static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, offt_pass_desc *fd,
-                            offt_filter_desc *fl) {
+ * backend have no fused route of this flavour (the caller takes the generic one).
+ * The out-of-place and the gather launch need the z-y-x layout, their own backend entry and their own kernel on top of the
+ * in-place one's conditions (the single-input kernel is asked for as well: every length with one of the others has it).
+ * Out of place: powers of two from 64 to 1024, and a mixed-radix x extent that has a fused kernel where
+ * OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_MULTI_MIXED are BOTH set (bits 1 and 2 of offt_filter_desc::mixed; the
+ * in-place launch of an output that is `data` reads bit 1 alone).  Gather: powers of two from 64 to 1024 (a mixed-radix x
+ * extent has no such kernel, whatever the plan's options say). */
+static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, conv_flavour flavour,
+                            offt_pass_desc *fd, offt_filter_desc *fl) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_pass_desc *l = &fw->d[2], *f0 = &iv->d[0];
+  if (flavour == CONV_OOP && (!fw->zyx || !st->be->conv_pass_oop)) return 0;
+  if (flavour == CONV_SUM && (!fw->zyx || !st->be->conv_pass_sum)) return 0;
   if (st->use_pipeline || !st->be->conv_pass) return 0;
   *fd = *l;
   fd->scale = 1.0;
@@ -3008,63 +3105,19 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
       f0->out_axis_stride != l->in_axis_stride || f0->out_col_stride != l->in_col_stride || f0->out_b1_stride != l->in_b1_stride ||
       f0->out_b2_stride != l->in_b2_stride)
     return 0;
-  return offt_hipk_conv_has_fused(fd, fl);
-}
-
-static int execute_convolve_single(struct _offt_plan *po, void *data, const void *filter, int kind) {
-  hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
-  void *s = st->s_compute;
-  single_sched fw, iv;
-  single_schedule(po, data, -1, &fw);
-  single_schedule(po, data, +1, &iv);
-  offt_pass_desc fd;
-  offt_filter_desc fl;
-  if (!conv_fused_route(po, &fw, &iv, kind, &fd, &fl)) return 1;
-  const size_t fesz = kind == OFFT_FILTER_COMPLEX ? st->esz : st->esz / 2; /* filter bytes per element */
-  /* z-y-x: the forward's y pass, the fused launch and the inverse's y pass all work on z-planes of the caller's array
-   * (nb1 = Nz, one z-plane per batch entry): they alternate over groups of planes that fit the Infinity Cache, as the y and
-   * x launches of a plain transform do (execute_single) -- y(group) keeps its stores, the fused launch re-reads and keeps,
-   * the inverse's y pass re-reads.  Same group size rule and option (OFFT_HIP_OPT_ZGROUP_MIB, 0 = plain launches). */
-  const offt_pass_desc *py = &fw.d[1], *qy = &iv.d[1];
-  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
-  int ng = 0;
-  if (fw.zyx && py->nb1 == cnt && fd.nb1 == cnt && qy->nb1 == cnt)
-    ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, py);
-  if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
-  if (ng >= 1) {
-    for (int z0 = 0; z0 < cnt; z0 += ng) {
-      const int g = cnt - z0 < ng ? cnt - z0 : ng;
-      offt_pass_desc a = *py, b = fd, q = *qy;
-      a.nb1 = b.nb1 = q.nb1 = g;
-      a.out_keep = b.out_keep = 1;
-      if (be->pass(&a, (const char *)fw.src[1] + (size_t)z0 * (size_t)a.in_b1_stride * st->esz,
-                   (char *)fw.dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * st->esz, s))
-        return -1;
-      if (be->conv_pass(&b, &fl, (const char *)filter + (size_t)z0 * (size_t)fl.b1_stride * fesz,
-                        (char *)fw.src[2] + (size_t)z0 * (size_t)b.in_b1_stride * st->esz, s))
-        return -1;
-      if (be->pass(&q, (const char *)iv.src[1] + (size_t)z0 * (size_t)q.in_b1_stride * st->esz,
-                   (char *)iv.dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * st->esz, s))
-        return -1;
-    }
-  } else {
-    if (be->pass(&fw.d[1], fw.src[1], fw.dst[1], s)) return -1;
-    if (be->conv_pass(&fd, &fl, filter, (void *)fw.src[2], s)) return -1;
-    if (be->pass(&iv.d[1], iv.src[1], iv.dst[1], s)) return -1;
+  const int inplace = offt_hipk_conv_has_fused(fd, fl);
+  switch (flavour) {
+  case CONV_OOP:
+    if (!inplace) return 0;
+    if (st->opt.conv_mixed && st->opt.conv_multi_mixed) fl->mixed |= 2;
+    return offt_hipk_conv_has_fused_oop(fd, fl);
+  case CONV_SUM: return inplace ? offt_hipk_conv_has_fused_sum(fd, fl) : 0;
+  default: return inplace;
   }
-  return be->pass(&iv.d[2], iv.src[2], iv.dst[2], s) ? -1 : 0;
 }
 
-/* the multiply of the unfused route: this rank's output block (osize box, ostride addressing) times H */
-static int conv_pointwise(struct _offt_plan *po, void *data, const void *filter, int kind) {
-  hip_state *st = (hip_state *)po->hip_state;
-  const struct _offt_comm *c = po->comm;
-  return st->be->pointwise(data, filter, st->prec, kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0], c->ostride[1],
-                           c->ostride[2], st->s_compute) ? -1 : 0;
-}
-
-int offt_hip_convolve_fused(const struct _offt_plan *po) {
+/* behind offt_hip_convolve_fused, offt_hip_convolve_multi_fused and offt_hip_convolve_sum_fused */
+static int conv_fused_query(const struct _offt_plan *po, conv_flavour flavour) {
   if (!po || !po->hip_state) return 0;
   single_sched fw, iv;
   offt_pass_desc fd;
@@ -3073,89 +3126,70 @@ int offt_hip_convolve_fused(const struct _offt_plan *po) {
   if (((hip_state *)po->hip_state)->use_pipeline) return 0;
   single_schedule(p, NULL, -1, &fw);
   single_schedule(p, NULL, +1, &iv);
-  return conv_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, &fd, &fl);
+  return conv_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, flavour, &fd, &fl);
 }
+int offt_hip_convolve_fused(const struct _offt_plan *po) { return conv_fused_query(po, CONV_INPLACE); }
+int offt_hip_convolve_multi_fused(const struct _offt_plan *po) { return conv_fused_query(po, CONV_OOP); }
+int offt_hip_convolve_sum_fused(const struct _offt_plan *po) { return conv_fused_query(po, CONV_SUM); }
 
-int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *filter, int filter_kind) {
+/* The middle of every fused route: the forward's y pass (fw->d[1]; left out with with_y = 0, for the later outputs of the
+ * multi call), the fused launch `cl` with the descriptors of conv_fused_route, the inverse's y pass (iv->d[1]).
+ * z-y-x: all three work on z-planes of the caller's arrays (nb1 = Nz in single_schedule, pruned or not: one z-plane per batch
+ * entry), so they alternate over groups of planes that fit the Infinity Cache, as the y and x launches of a plain transform
+ * do (execute_single) -- y(group) keeps its stores, the fused launch re-reads and keeps, the inverse's y pass re-reads.  Same
+ * group size rule and option (OFFT_HIP_OPT_ZGROUP_MIB, 0 = plain launches).  A group's planes sit at the same offset in
+ * every source and in the destination of the fused launch.  Every other layout, and z-y-x without groups, launches the
+ * three descriptors as they are. */
+static int conv_plane_groups(struct _offt_plan *po, const single_sched *fw, int with_y, const offt_pass_desc *fd,
+                             const offt_filter_desc *fl, const conv_launch *cl, const single_sched *iv) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
-  double *t = po->t;
-  memset(t, 0, GES * sizeof(double));
-  TEST_NOTE_MESH(po);
-  if (filter_kind != OFFT_HIP_FILTER_REAL && filter_kind != OFFT_HIP_FILTER_COMPLEX) {
-    SET_ERR("offt_hip_execute_convolve: unknown filter_kind %d (OFFT_HIP_FILTER_REAL or OFFT_HIP_FILTER_COMPLEX)", filter_kind);
-    t[ALL] = 99999999.0;
-    return -1;
+  void *s = st->s_compute;
+  const offt_pass_desc *py = &fw->d[1], *qy = &iv->d[1];
+  const size_t esz = st->esz, fesz = fl->kind == OFFT_FILTER_COMPLEX ? esz : esz / 2; /* filter bytes per element */
+  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
+  int ng = 0; /* planes per group; 0: plain launches */
+  if (fw->zyx && py->nb1 == cnt && fd->nb1 == cnt && qy->nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, py);
+  const int step = ng >= 1 ? ng : cnt;
+  for (int z0 = 0; z0 < cnt; z0 += step) {
+    offt_pass_desc a = *py, b = *fd, q = *qy;
+    if (ng >= 1) {
+      a.nb1 = b.nb1 = q.nb1 = cnt - z0 < ng ? cnt - z0 : ng;
+      a.out_keep = b.out_keep = 1;
+    }
+    const size_t off = (size_t)z0 * (size_t)b.in_b1_stride * esz, foff = (size_t)z0 * (size_t)fl->b1_stride * fesz;
+    if (with_y && be->pass(&a, (const char *)fw->src[1] + (size_t)z0 * (size_t)a.in_b1_stride * esz,
+                           (char *)fw->dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * esz, s))
+      return -1;
+    int rc = -1;
+    switch (cl->flavour) {
+    case CONV_INPLACE: rc = be->conv_pass(&b, fl, (const char *)cl->filters[0] + foff, (char *)cl->dst + off, s); break;
+    case CONV_OOP:
+      rc = be->conv_pass_oop(&b, fl, (const char *)cl->filters[0] + foff, (const char *)cl->srcs[0] + off, (char *)cl->dst + off, s);
+      break;
+    case CONV_SUM: {
+      const void *srcs[OFFT_HIP_CONV_MAX_IN], *fg[OFFT_HIP_CONV_MAX_IN];
+      for (int k = 0; k < cl->nin; k++) {
+        srcs[k] = (const char *)cl->srcs[k] + off;
+        fg[k] = (const char *)cl->filters[k] + foff;
+      }
+      rc = be->conv_pass_sum(&b, fl, cl->nin, fg, srcs, (char *)cl->dst + off, s);
+      break;
+    }
+    }
+    if (rc) return -1;
+    if (be->pass(&q, (const char *)iv->src[1] + (size_t)z0 * (size_t)q.in_b1_stride * esz,
+                 (char *)iv->dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * esz, s))
+      return -1;
   }
-  if (!filter || (!g_backend && !is_device_ptr(filter))) {
-    SET_ERR("offt_hip_execute_convolve: the filter must be device memory%s", filter ? "" : " (got NULL)");
-    t[ALL] = 99999999.0;
-    return -1;
-  }
-  if (!data || (!g_backend && !is_device_ptr(data))) {
-    SET_ERR("offt_hip_execute_convolve: the data must be device memory (no host staging for a convolve)");
-    t[ALL] = 99999999.0;
-    return -1;
-  }
-  if (!be->pointwise) {
-    SET_ERR("offt_hip_execute_convolve: this backend has no pointwise multiply");
-    t[ALL] = 99999999.0;
-    return -1;
-  }
-  if ((st->uses_rccl || st->p2p) && G.comm_failed) {
-    SET_ERR("offt_hip_execute_convolve: the communicator failed earlier; make a new world (offt_hip_set_world) and plan");
-    t[ALL] = 99999999.0;
-    return -1;
-  }
-  const double t0 = wall_seconds();
-  const int timed = st->async ? 0 : 1;
-  st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros after a convolve */
-  if (timed) be->event_record(st->ev0, st->s_compute);
-  const double scale = st->out_scale;
-  int rc = half_box_clear(po, data);
-  if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_single(po, data, filter, filter_kind);
-  if (rc > 0) {
-    /* unfused: forward (unscaled), multiply on the stream the forward ends on, inverse (the output scale on its last store) */
-    st->out_scale = 1.0;
-    if (!st->use_pipeline) rc = execute_single(po, data, -1);
-    else rc = st->slab_zyx ? execute_slab(po, data) : execute_pipeline(po, data, -1);
-    st->out_scale = scale;
-    if (!rc) rc = conv_pointwise(po, data, filter, filter_kind);
-    if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, data) : execute_single(po, data, +1);
-  }
-  st->out_scale = scale;
-  st->yx_fused = 0;
-  if (timed) be->event_record(st->ev1, st->s_compute);
-  if (rc) {
-    if (st->uses_rccl) comm_fail(st);
-    t[ALL] = 99999999.0;
-    return -1;
-  }
-  if (st->async) { t[ALL] = wall_seconds() - t0; return 0; }
-  if (wait_compute(st)) { t[ALL] = 99999999.0; return -1; }
-  st->last_dev_s = 1e-3 * be->event_ms(st->ev0, st->ev1);
-  for (int i = 0; i < 3; i++) st->pass_s[i] = 0.0;
-  t[ALL] = wall_seconds() - t0;
   return 0;
 }
 
-/* ------------------------------------------------------------------------- */
-/* multi-output spectral convolution: one forward, several filters             */
-/* ------------------------------------------------------------------------- */
-/* The fused multi-output route: one rank, the z-y-x layout, the conditions of conv_fused_route, and a backend and a kernel
- * for the out-of-place fused launch: powers of two from 64 to 1024, and a mixed-radix x extent that has a fused kernel where
- * OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_MULTI_MIXED are BOTH set (bits 1 and 2 of offt_filter_desc::mixed; the
- * in-place launch of an output that is `data` reads bit 1 alone).  Fills what conv_fused_route fills. */
-static int conv_multi_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, offt_pass_desc *fd,
-                                  offt_filter_desc *fl) {
-  hip_state *st = (hip_state *)po->hip_state;
-  if (!fw->zyx || !st->be->conv_pass_oop) return 0;
-  if (!conv_fused_route(po, fw, iv, kind, fd, fl)) return 0;
-  if (st->opt.conv_mixed && st->opt.conv_multi_mixed) fl->mixed |= 2;
-  return offt_hipk_conv_has_fused_oop(fd, fl);
-}
-
-/* z-y-x: the forward is data -> W -> data with the x pass in place, the inverse x in place, y: buf -> W, z: W -> buf.  The
+/* The fused route of the single-output and the multi-output call on one rank.  1: no such route (the caller takes the generic
+ * one).  The single-output call is nout = 1 with outs[0] = data: the forward's first launch, the plane groups with the
+ * in-place fused launch on the forward's last buffer, the inverse's last launch -- in z-y-x, and in the rotating y-z-x layout,
+ * where that buffer is the scratch volume V.  Anything else needs the out-of-place launch, hence z-y-x.
+ * z-y-x: the forward is data -> W -> data with the x pass in place, the inverse x in place, y: buf -> W, z: W -> buf.  The
  * spectrum ahead of the x pass stays in `data` while every output but the last is made from it:
  *   P1 (z) once;
  *   first output:  per plane group  forward y (W -> data, kept), out-of-place fused launch (data -> out, kept), inverse y
@@ -3163,10 +3197,9 @@ static int conv_multi_fused_route(struct _offt_plan *po, const single_sched *fw,
  *   later outputs: the same without the forward y;
  *   an output that IS `data` comes last (order[]) and runs the in-place fused launch.
  * W is one volume, so the outputs are the outer loop: the inverse y of a group writes the part of W that the forward y of
- * that group has read, and the next output's inverse y overwrites W only behind this output's inverse z.
- * 1: no such route (the caller takes the generic one). */
-static int execute_convolve_multi_single(struct _offt_plan *po, void *data, int nout, const int *order, void *const *outs,
-                                         const void *const *filters, int kind) {
+ * that group has read, and the next output's inverse y overwrites W only behind this output's inverse z. */
+static int execute_convolve_single(struct _offt_plan *po, void *data, int nout, const int *order, void *const *outs,
+                                   const void *const *filters, int kind) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
   void *s = st->s_compute;
@@ -3175,103 +3208,121 @@ static int execute_convolve_multi_single(struct _offt_plan *po, void *data, int 
   single_schedule(po, data, +1, &iv);
   offt_pass_desc fd;
   offt_filter_desc fl;
-  if (!conv_multi_fused_route(po, &fw, &iv, kind, &fd, &fl)) return 1;
-  const size_t fesz = kind == OFFT_FILTER_COMPLEX ? st->esz : st->esz / 2; /* filter bytes per element */
-  const offt_pass_desc *py = &fw.d[1];
-  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
-  int ng = 0; /* planes per group, as in execute_convolve_single; 0: plain launches */
-  if (py->nb1 == cnt && fd.nb1 == cnt && iv.d[1].nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, py);
-  const int step = ng >= 1 ? ng : (cnt > 0 ? cnt : 1);
+  if (!conv_fused_route(po, &fw, &iv, kind, nout == 1 && outs[0] == data ? CONV_INPLACE : CONV_OOP, &fd, &fl)) return 1;
   if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
   for (int i = 0; i < nout; i++) {
     void *out = outs[order[i]];
-    const void *filter = filters[order[i]];
-    single_schedule(po, out, +1, &iv); /* x in place on out, y: out -> W, z: W -> out, the output scale on the z pass */
-    for (int z0 = 0; z0 < cnt; z0 += step) {
-      const int g = cnt - z0 < step ? cnt - z0 : step;
-      offt_pass_desc a = *py, b = fd, q = iv.d[1];
-      a.nb1 = b.nb1 = q.nb1 = g;
-      a.out_keep = b.out_keep = ng >= 1;
-      const size_t off = (size_t)z0 * (size_t)b.in_b1_stride * st->esz; /* the group's planes, in data and in out alike */
-      const char *fg = (const char *)filter + (size_t)z0 * (size_t)fl.b1_stride * fesz;
-      if (i == 0 && be->pass(&a, (const char *)fw.src[1] + (size_t)z0 * (size_t)a.in_b1_stride * st->esz,
-                             (char *)fw.dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * st->esz, s))
-        return -1;
-      if (out == data ? be->conv_pass(&b, &fl, fg, (char *)data + off, s)
-                      : be->conv_pass_oop(&b, &fl, fg, (const char *)data + off, (char *)out + off, s))
-        return -1;
-      if (be->pass(&q, (const char *)iv.src[1] + (size_t)z0 * (size_t)q.in_b1_stride * st->esz,
-                   (char *)iv.dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * st->esz, s))
-        return -1;
-    }
+    single_schedule(po, out, +1, &iv); /* z-y-x: x in place on out, y: out -> W, z: W -> out, the output scale on the z pass */
+    const conv_launch cl = {out == data ? CONV_INPLACE : CONV_OOP, 1, &fw.src[2], iv.dst[0], &filters[order[i]]};
+    if (conv_plane_groups(po, &fw, i == 0, &fd, &fl, &cl, &iv)) return -1;
     if (be->pass(&iv.d[2], iv.src[2], iv.dst[2], s)) return -1;
   }
   return 0;
 }
 
-int offt_hip_convolve_multi_fused(const struct _offt_plan *po) {
-  if (!po || !po->hip_state) return 0;
+/* z-y-x: the forward of an input is in -> W -> in with the x pass in place.  W is one volume, so the inputs are the outer
+ * loop of the forward:
+ *   inputs 0 ... nin-2:  forward z (ins[k] -> W), forward y (W -> ins[k]), plain launches;
+ *   the last input:      forward z, then per plane group  forward y (W -> ins[nin-1], kept), the gather launch (forward x pass
+ *                        of every input . filter . sum . inverse x pass, all ins -> out, kept), inverse y (out -> W);
+ *   inverse z (W -> out), with the output scale.
+ * The inverse y of a group writes the part of W that the last input's forward y of that group has read.  `out` may be one
+ * of the inputs: the gather launch loads a line from every input before it stores it. */
+static int execute_convolve_sum_single(struct _offt_plan *po, int nin, void *const *ins, const void *const *filters, int kind, void *out) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  void *s = st->s_compute;
   single_sched fw, iv;
+  single_schedule(po, out, -1, &fw);
+  single_schedule(po, out, +1, &iv); /* x in place on out, y: out -> W, z: W -> out, the output scale on the z pass */
   offt_pass_desc fd;
   offt_filter_desc fl;
-  struct _offt_plan *p = (struct _offt_plan *)po;
-  if (((hip_state *)po->hip_state)->use_pipeline) return 0;
-  single_schedule(p, NULL, -1, &fw);
-  single_schedule(p, NULL, +1, &iv);
-  return conv_multi_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, &fd, &fl);
+  if (!conv_fused_route(po, &fw, &iv, kind, CONV_SUM, &fd, &fl)) return 1;
+  for (int k = 0; k < nin; k++) {
+    single_schedule(po, ins[k], -1, &fw);
+    if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
+    if (k < nin - 1 && be->pass(&fw.d[1], fw.src[1], fw.dst[1], s)) return -1;
+  }
+  const conv_launch cl = {CONV_SUM, nin, (const void *const *)ins, out, filters};
+  if (conv_plane_groups(po, &fw, 1, &fd, &fl, &cl, &iv)) return -1; /* (fw: of the last input) */
+  return be->pass(&iv.d[2], iv.src[2], iv.dst[2], s) ? -1 : 0;
 }
 
+/* The generic route, on one rank or several: the forward in place on `buf`, unscaled; the call's multiply on the stream
+ * the forward ends on; the inverse in place on `buf`, the output scale on its last store.  Neither transform ties its buffer
+ * to the other's: execute_single builds its launches from the array it is given, and execute_inverse_multi records the
+ * forward schedule against that array (inv_data) -- what else a step touches, under the staged and the direct-store exchange
+ * alike, is the plan's own send, receive and work volumes (peers map those, never the caller's array). */
+static int conv_forward(struct _offt_plan *po, void *buf) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const double scale = st->out_scale;
+  int rc;
+  st->out_scale = 1.0;
+  if (!st->use_pipeline) rc = execute_single(po, buf, -1);
+  else rc = st->slab_zyx ? execute_slab(po, buf) : execute_pipeline(po, buf, -1);
+  st->out_scale = scale;
+  return rc;
+}
+
+static int conv_inverse(struct _offt_plan *po, void *buf) {
+  return ((hip_state *)po->hip_state)->use_pipeline ? execute_inverse_multi(po, buf) : execute_single(po, buf, +1);
+}
+
+/* the in-place multiply: this rank's output block (osize box, ostride addressing) times H */
+static int conv_pointwise(struct _offt_plan *po, void *data, const void *filter, int kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const struct _offt_comm *c = po->comm;
+  return st->be->pointwise(data, filter, st->prec, kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0], c->ostride[1],
+                           c->ostride[2], st->s_compute) ? -1 : 0;
+}
+
+int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *filter, int filter_kind) {
+  static const char who[] = "offt_hip_execute_convolve";
+  hip_state *st = (hip_state *)po->hip_state;
+  conv_begin(po);
+  if (conv_check_kind(po, who, filter_kind) || conv_need_device(po, who, filter, "the filter", -1, "", 1) ||
+      conv_need_device(po, who, data, "the data", -1, CONV_NO_STAGING, 0) ||
+      conv_ready(po, who, st->be->pointwise != NULL, "pointwise multiply"))
+    return -1;
+  const double t0 = conv_enter(po);
+  int rc = half_box_clear(po, data);
+  static const int first = 0;
+  if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_single(po, data, 1, &first, &data, &filter, filter_kind);
+  if (rc > 0) {
+    rc = conv_forward(po, data);
+    if (!rc) rc = conv_pointwise(po, data, filter, filter_kind);
+    if (!rc) rc = conv_inverse(po, data);
+  }
+  return conv_leave(po, t0, rc);
+}
+
+/* multi-output: one forward, several filters */
 int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout, void *const *outs, const void *const *filters,
                                     int filter_kind) {
+  static const char who[] = "offt_hip_execute_convolve_multi";
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
   const struct _offt_comm *c = po->comm;
-  double *t = po->t;
-  memset(t, 0, GES * sizeof(double));
-  TEST_NOTE_MESH(po);
-#define MULTI_REFUSE(...) do { SET_ERR(__VA_ARGS__); t[ALL] = 99999999.0; return -1; } while (0)
+  conv_begin(po);
   if (nout < 1 || nout > OFFT_HIP_CONV_MAX_OUT)
-    MULTI_REFUSE("offt_hip_execute_convolve_multi: nout = %d (1 ... OFFT_HIP_CONV_MAX_OUT = %d outputs)", nout, OFFT_HIP_CONV_MAX_OUT);
-  if (filter_kind != OFFT_HIP_FILTER_REAL && filter_kind != OFFT_HIP_FILTER_COMPLEX)
-    MULTI_REFUSE("offt_hip_execute_convolve_multi: unknown filter_kind %d (OFFT_HIP_FILTER_REAL or OFFT_HIP_FILTER_COMPLEX)", filter_kind);
-  if (!outs || !filters) MULTI_REFUSE("offt_hip_execute_convolve_multi: outs and filters must be arrays of nout pointers (got NULL)");
-  if (!data || (!g_backend && !is_device_ptr(data)))
-    MULTI_REFUSE("offt_hip_execute_convolve_multi: the data must be device memory (no host staging for a convolve)");
-  for (int k = 0; k < nout; k++) {
-    if (!filters[k] || (!g_backend && !is_device_ptr(filters[k])))
-      MULTI_REFUSE("offt_hip_execute_convolve_multi: filter %d must be device memory%s", k, filters[k] ? "" : " (got NULL)");
-    if (!outs[k] || (!g_backend && !is_device_ptr(outs[k])))
-      MULTI_REFUSE("offt_hip_execute_convolve_multi: output %d must be device memory%s", k, outs[k] ? "" : " (got NULL)");
-    for (int j = 0; j < k; j++)
-      if (outs[j] == outs[k]) MULTI_REFUSE("offt_hip_execute_convolve_multi: outputs %d and %d are the same array", j, k);
-  }
-  if (!be->pointwise) MULTI_REFUSE("offt_hip_execute_convolve_multi: this backend has no pointwise multiply");
-  if ((st->uses_rccl || st->p2p) && G.comm_failed)
-    MULTI_REFUSE("offt_hip_execute_convolve_multi: the communicator failed earlier; make a new world (offt_hip_set_world) and plan");
-#undef MULTI_REFUSE
+    CONV_REFUSE(po, "%s: nout = %d (1 ... OFFT_HIP_CONV_MAX_OUT = %d outputs)", who, nout, OFFT_HIP_CONV_MAX_OUT);
+  if (conv_check_kind(po, who, filter_kind)) return -1;
+  if (!outs || !filters) CONV_REFUSE(po, "%s: outs and filters must be arrays of nout pointers (got NULL)", who);
+  if (conv_need_device(po, who, data, "the data", -1, CONV_NO_STAGING, 0) || conv_need_arrays(po, who, nout, filters, outs, "output") ||
+      conv_ready(po, who, be->pointwise != NULL, "pointwise multiply"))
+    return -1;
   /* one output, in place: the single-output call itself, bit for bit */
   if (nout == 1 && outs[0] == data) return offt_hip_execute_convolve(po, data, filters[0], filter_kind);
   /* the output that is `data` (at most one: the entries differ) is computed last: until then `data` holds the spectrum */
   int order[OFFT_HIP_CONV_MAX_OUT], n = 0;
   for (int k = 0; k < nout; k++) if (outs[k] != data) order[n++] = k;
   for (int k = 0; k < nout; k++) if (outs[k] == data) order[n++] = k;
-  const double t0 = wall_seconds();
-  const int timed = st->async ? 0 : 1;
-  st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros, as after a convolve */
-  if (timed) be->event_record(st->ev0, st->s_compute);
-  const double scale = st->out_scale;
+  const double t0 = conv_enter(po);
   int rc = half_box_clear(po, data);
-  if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_multi_single(po, data, nout, order, outs, filters, filter_kind);
+  if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_single(po, data, nout, order, outs, filters, filter_kind);
   if (rc > 0) {
-    /* generic: forward in place on data (unscaled), then per output the multiply data -> out and the inverse in place on out,
-     * the output scale on its last store.  Neither inverse ties its buffer to the forward's: execute_single builds its launches
-     * from the array it is given, and execute_inverse_multi records the forward schedule against that array (inv_data) --
-     * what else a step touches, under the staged and the direct-store exchange alike, is the plan's own send, receive and
-     * work volumes (peers map those, never the caller's array). */
-    st->out_scale = 1.0;
-    if (!st->use_pipeline) rc = execute_single(po, data, -1);
-    else rc = st->slab_zyx ? execute_slab(po, data) : execute_pipeline(po, data, -1);
-    st->out_scale = scale;
+    /* generic: one forward on data, then per output the multiply data -> out and the inverse on out */
+    rc = conv_forward(po, data);
     for (int i = 0; i < nout && !rc; i++) {
       void *out = outs[order[i]];
       const void *filter = filters[order[i]];
@@ -3283,171 +3334,42 @@ int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout,
         rc = be->memcpy_dd(out, data, local_elems(c) * st->esz, st->s_compute) ? -1 : 0;
         if (!rc) rc = conv_pointwise(po, out, filter, filter_kind);
       }
-      if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, out) : execute_single(po, out, +1);
+      if (!rc) rc = conv_inverse(po, out);
     }
   }
-  st->out_scale = scale;
-  st->yx_fused = 0;
-  if (timed) be->event_record(st->ev1, st->s_compute);
-  if (rc) {
-    if (st->uses_rccl) comm_fail(st);
-    t[ALL] = 99999999.0;
-    return -1;
-  }
-  if (st->async) { t[ALL] = wall_seconds() - t0; return 0; }
-  if (wait_compute(st)) { t[ALL] = 99999999.0; return -1; }
-  st->last_dev_s = 1e-3 * be->event_ms(st->ev0, st->ev1);
-  for (int i = 0; i < 3; i++) st->pass_s[i] = 0.0;
-  t[ALL] = wall_seconds() - t0;
-  return 0;
+  return conv_leave(po, t0, rc);
 }
 
-/* ------------------------------------------------------------------------- */
-/* multi-input spectral convolution: several forwards, one inverse             */
-/* ------------------------------------------------------------------------- */
-/* The fused multi-input route: one rank, the z-y-x layout, the conditions of conv_fused_route, and a backend and a kernel for
- * the launch that gathers several sources: powers of two from 64 to 1024 (a mixed-radix x extent has no such kernel, whatever
- * the plan's options say).  conv_fused_route asks for the single-input kernel as well, which every such length has.  Fills
- * what conv_fused_route fills. */
-static int conv_sum_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, offt_pass_desc *fd,
-                                offt_filter_desc *fl) {
-  hip_state *st = (hip_state *)po->hip_state;
-  if (!fw->zyx || !st->be->conv_pass_sum) return 0;
-  if (!conv_fused_route(po, fw, iv, kind, fd, fl)) return 0;
-  return offt_hipk_conv_has_fused_sum(fd, fl);
-}
-
-/* z-y-x: the forward of an input is in -> W -> in with the x pass in place.  W is one volume, so the inputs are the outer
- * loop of the forward:
- *   inputs 0 ... nin-2:  forward z (ins[k] -> W), forward y (W -> ins[k]), plain launches;
- *   the last input:      forward z, then per plane group  forward y (W -> ins[nin-1], kept), the gather launch (forward x pass
- *                        of every input . filter . sum . inverse x pass, all ins -> out, kept), inverse y (out -> W);
- *   inverse z (W -> out), with the output scale.
- * The inverse y of a group writes the part of W that the last input's forward y of that group has read.  `out` may be one
- * of the inputs: the gather launch loads a line from every input before it stores it.
- * 1: no such route (the caller takes the generic one). */
-static int execute_convolve_sum_single(struct _offt_plan *po, int nin, void *const *ins, const void *const *filters, int kind, void *out) {
-  hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
-  void *s = st->s_compute;
-  single_sched fw, iv;
-  single_schedule(po, out, -1, &fw);
-  single_schedule(po, out, +1, &iv); /* x in place on out, y: out -> W, z: W -> out, the output scale on the z pass */
-  offt_pass_desc fd;
-  offt_filter_desc fl;
-  if (!conv_sum_fused_route(po, &fw, &iv, kind, &fd, &fl)) return 1;
-  const size_t fesz = kind == OFFT_FILTER_COMPLEX ? st->esz : st->esz / 2; /* filter bytes per element */
-  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
-  int ng = 0; /* planes per group, as in execute_convolve_multi_single; 0: plain launches */
-  if (fw.d[1].nb1 == cnt && fd.nb1 == cnt && iv.d[1].nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, &fw.d[1]);
-  const int step = ng >= 1 ? ng : (cnt > 0 ? cnt : 1);
-  for (int k = 0; k < nin; k++) {
-    single_schedule(po, ins[k], -1, &fw);
-    if (be->pass(&fw.d[0], fw.src[0], fw.dst[0], s)) return -1;
-    if (k < nin - 1 && be->pass(&fw.d[1], fw.src[1], fw.dst[1], s)) return -1;
-  }
-  const offt_pass_desc *py = &fw.d[1]; /* of the last input */
-  for (int z0 = 0; z0 < cnt; z0 += step) {
-    const int g = cnt - z0 < step ? cnt - z0 : step;
-    offt_pass_desc a = *py, b = fd, q = iv.d[1];
-    a.nb1 = b.nb1 = q.nb1 = g;
-    a.out_keep = b.out_keep = ng >= 1;
-    const size_t off = (size_t)z0 * (size_t)b.in_b1_stride * st->esz; /* the group's planes, in every input and in out alike */
-    const void *srcs[OFFT_HIP_CONV_MAX_IN], *fg[OFFT_HIP_CONV_MAX_IN];
-    for (int k = 0; k < nin; k++) {
-      srcs[k] = (const char *)ins[k] + off;
-      fg[k] = (const char *)filters[k] + (size_t)z0 * (size_t)fl.b1_stride * fesz;
-    }
-    if (be->pass(&a, (const char *)fw.src[1] + (size_t)z0 * (size_t)a.in_b1_stride * st->esz,
-                 (char *)fw.dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * st->esz, s))
-      return -1;
-    if (be->conv_pass_sum(&b, &fl, nin, fg, srcs, (char *)out + off, s)) return -1;
-    if (be->pass(&q, (const char *)iv.src[1] + (size_t)z0 * (size_t)q.in_b1_stride * st->esz,
-                 (char *)iv.dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * st->esz, s))
-      return -1;
-  }
-  return be->pass(&iv.d[2], iv.src[2], iv.dst[2], s) ? -1 : 0;
-}
-
-int offt_hip_convolve_sum_fused(const struct _offt_plan *po) {
-  if (!po || !po->hip_state) return 0;
-  single_sched fw, iv;
-  offt_pass_desc fd;
-  offt_filter_desc fl;
-  struct _offt_plan *p = (struct _offt_plan *)po;
-  if (((hip_state *)po->hip_state)->use_pipeline) return 0;
-  single_schedule(p, NULL, -1, &fw);
-  single_schedule(p, NULL, +1, &iv);
-  return conv_sum_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, &fd, &fl);
-}
-
+/* multi-input: several forwards, one inverse */
 int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *ins, const void *const *filters, int filter_kind, void *out) {
+  static const char who[] = "offt_hip_execute_convolve_sum";
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
   const struct _offt_comm *c = po->comm;
-  double *t = po->t;
-  memset(t, 0, GES * sizeof(double));
-  TEST_NOTE_MESH(po);
-#define SUM_REFUSE(...) do { SET_ERR(__VA_ARGS__); t[ALL] = 99999999.0; return -1; } while (0)
+  conv_begin(po);
   if (nin < 1 || nin > OFFT_HIP_CONV_MAX_IN)
-    SUM_REFUSE("offt_hip_execute_convolve_sum: nin = %d (1 ... OFFT_HIP_CONV_MAX_IN = %d inputs)", nin, OFFT_HIP_CONV_MAX_IN);
-  if (filter_kind != OFFT_HIP_FILTER_REAL && filter_kind != OFFT_HIP_FILTER_COMPLEX)
-    SUM_REFUSE("offt_hip_execute_convolve_sum: unknown filter_kind %d (OFFT_HIP_FILTER_REAL or OFFT_HIP_FILTER_COMPLEX)", filter_kind);
-  if (!ins || !filters) SUM_REFUSE("offt_hip_execute_convolve_sum: ins and filters must be arrays of nin pointers (got NULL)");
-  if (!out || (!g_backend && !is_device_ptr(out)))
-    SUM_REFUSE("offt_hip_execute_convolve_sum: the output must be device memory (no host staging for a convolve)%s", out ? "" : " (got NULL)");
-  for (int k = 0; k < nin; k++) {
-    if (!filters[k] || (!g_backend && !is_device_ptr(filters[k])))
-      SUM_REFUSE("offt_hip_execute_convolve_sum: filter %d must be device memory%s", k, filters[k] ? "" : " (got NULL)");
-    if (!ins[k] || (!g_backend && !is_device_ptr(ins[k])))
-      SUM_REFUSE("offt_hip_execute_convolve_sum: input %d must be device memory%s", k, ins[k] ? "" : " (got NULL)");
-    for (int j = 0; j < k; j++)
-      if (ins[j] == ins[k]) SUM_REFUSE("offt_hip_execute_convolve_sum: inputs %d and %d are the same array", j, k);
-  }
-  if (!be->pointwise_sum) SUM_REFUSE("offt_hip_execute_convolve_sum: this backend has no pointwise multiply-and-sum");
-  if ((st->uses_rccl || st->p2p) && G.comm_failed)
-    SUM_REFUSE("offt_hip_execute_convolve_sum: the communicator failed earlier; make a new world (offt_hip_set_world) and plan");
-#undef SUM_REFUSE
+    CONV_REFUSE(po, "%s: nin = %d (1 ... OFFT_HIP_CONV_MAX_IN = %d inputs)", who, nin, OFFT_HIP_CONV_MAX_IN);
+  if (conv_check_kind(po, who, filter_kind)) return -1;
+  if (!ins || !filters) CONV_REFUSE(po, "%s: ins and filters must be arrays of nin pointers (got NULL)", who);
+  if (conv_need_device(po, who, out, "the output", -1, CONV_NO_STAGING, 1) || conv_need_arrays(po, who, nin, filters, ins, "input") ||
+      conv_ready(po, who, be->pointwise_sum != NULL, "pointwise multiply-and-sum"))
+    return -1;
   /* one input, in place: the single-output call itself, bit for bit */
   if (nin == 1 && out == ins[0]) return offt_hip_execute_convolve(po, out, filters[0], filter_kind);
-  const double t0 = wall_seconds();
-  const int timed = st->async ? 0 : 1;
-  st->timed = 0; /* no per-pass events: offt_hip_last_pass_seconds reports zeros, as after a convolve */
-  if (timed) be->event_record(st->ev0, st->s_compute);
-  const double scale = st->out_scale;
+  const double t0 = conv_enter(po);
   int rc = 0;
   for (int k = 0; k < nin && !rc; k++) rc = half_box_clear(po, ins[k]);
   if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_sum_single(po, nin, ins, filters, filter_kind, out);
   if (rc > 0) {
-    /* generic: the forward in place on every input (unscaled), ONE multiply-and-sum sweep into out, the inverse in place on
-     * out with the output scale on its last store.  As in the multi-output call, neither transform ties its buffer to
-     * another's: what a step touches besides the array it is given is the plan's own send, receive and work volumes. */
-    st->out_scale = 1.0;
+    /* generic: the forward on every input, ONE multiply-and-sum sweep into out, the inverse on out */
     rc = 0;
-    for (int k = 0; k < nin && !rc; k++) {
-      if (!st->use_pipeline) rc = execute_single(po, ins[k], -1);
-      else rc = st->slab_zyx ? execute_slab(po, ins[k]) : execute_pipeline(po, ins[k], -1);
-    }
-    st->out_scale = scale;
+    for (int k = 0; k < nin && !rc; k++) rc = conv_forward(po, ins[k]);
     if (!rc)
       rc = be->pointwise_sum(nin, (const void *const *)ins, filters, out, st->prec, filter_kind, c->osize[0], c->osize[1], c->osize[2],
                              c->ostride[0], c->ostride[1], c->ostride[2], st->s_compute) ? -1 : 0;
-    if (!rc) rc = st->use_pipeline ? execute_inverse_multi(po, out) : execute_single(po, out, +1);
+    if (!rc) rc = conv_inverse(po, out);
   }
-  st->out_scale = scale;
-  st->yx_fused = 0;
-  if (timed) be->event_record(st->ev1, st->s_compute);
-  if (rc) {
-    if (st->uses_rccl) comm_fail(st);
-    t[ALL] = 99999999.0;
-    return -1;
-  }
-  if (st->async) { t[ALL] = wall_seconds() - t0; return 0; }
-  if (wait_compute(st)) { t[ALL] = 99999999.0; return -1; }
-  st->last_dev_s = 1e-3 * be->event_ms(st->ev0, st->ev1);
-  for (int i = 0; i < 3; i++) st->pass_s[i] = 0.0;
-  t[ALL] = wall_seconds() - t0;
-  return 0;
+  return conv_leave(po, t0, rc);
 }
 
 /* asynchronous mode (offt_hip_set_async): wait for everything enqueued so far -- the same bounded, error-polling

@@ -55,10 +55,12 @@ SIGNATURES = {"dmalloc": C.CFUNCTYPE(V, C.c_size_t),
 class Recorder:
     """a copy of a backend table whose logged entries append to self.log and forward to the original's"""
 
+    table_type, signatures = Table, SIGNATURES  # (a subclass that logs more entries names a longer table: test_conv_launches.py)
+
     def __init__(self, table_addr):
-        self.table = Table.from_buffer_copy(C.string_at(table_addr, C.sizeof(Table)))
+        self.table = self.table_type.from_buffer_copy(C.string_at(table_addr, C.sizeof(self.table_type)))
         self._callbacks = []  # (the copied struct and its callbacks must outlive the installation)
-        for name, sig in SIGNATURES.items():
+        for name, sig in self.signatures.items():
             orig = getattr(self.table, name)
             if not orig:
                 continue  # (the plain table has no conv_pass / pointwise: they stay NULL)
