@@ -110,7 +110,8 @@ int offt_hip_convolve_multi_fused(const struct _offt_plan *po);
  * offt_hip_local_bytes(po) bytes.  EVERY ins[k] is consumed: its contents are undefined afterwards, unless it is `out`.  The
  * terms are added in the order k = 0 ... nin-1 on every route (a call is reproducible bit for bit); the output scale applies
  * once, on the final store.  Stream, async, half box and OFFT_HIP_OPT_ZGROUP_MIB are honoured as in
- * offt_hip_execute_convolve_multi.  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and
+ * offt_hip_execute_convolve_multi; a plan whose x extent is no power of two takes the generic route unless
+ * OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_SUM_MIXED are both set.  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and
  * offt_hip_last_error(), and nothing launched, for nin < 1 or nin > OFFT_HIP_CONV_MAX_IN, NULL ins or filters arrays, a NULL
  * or host-memory ins[k], filters[k] or out, two equal ins entries, an unknown filter_kind, a backend without the
  * multiply-and-sum, a failed communicator.  With nin == 1 and out == ins[0] the call IS offt_hip_execute_convolve: the same
@@ -119,7 +120,8 @@ int offt_hip_convolve_multi_fused(const struct _offt_plan *po);
 int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *ins, const void *const *filters, int filter_kind, void *out);
 /* 1 if the call runs the fused multi-input route: the forward's z and y passes per input, then ONE launch that runs the
  * forward x pass of every input, multiplies, sums in registers and runs the inverse x pass (all ins -> out), and the
- * inverse's y and z passes once -- one rank, the default z-y-x layout, an x extent that is a power of two from 64 to 1024;
+ * inverse's y and z passes once -- one rank, the default z-y-x layout, an x extent that is a power of two from 64 to 1024
+ * or, with OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_SUM_MIXED both set, one of the mixed-radix lengths listed there;
  * 0: the generic route (a forward per input, one multiply-and-sum sweep, one inverse) */
 int offt_hip_convolve_sum_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
@@ -191,6 +193,14 @@ int offt_hip_wait(struct _offt_plan *po);
                                           box), 0 (default) = one forward, then a multiply and an inverse per output.  Alone it changes
                                           nothing.  Read by every multi-output convolve; the results agree to rounding
                                           (OFFT_CONV_MULTI_MIXED) */
+/* (15 is not assigned: offt_hip_set_option answers -1 for it, as for every unknown number) */
+#define OFFT_HIP_OPT_CONV_SUM_MIXED 16 /* multi-input convolve on a plan whose x extent is no power of two: 1 = together with
+                                          OFFT_HIP_OPT_CONV_MIXED (both set) the fused multi-input route where that extent has a
+                                          mixed-radix gather kernel (the lengths listed at OFFT_HIP_OPT_CONV_MIXED; complex and r2c
+                                          plans, one rank, the z-y-x layout; with OFFT_HIP_OPT_HALF_MIXED also a pruned half box),
+                                          0 (default) = a forward per input, one multiply-and-sum sweep, one inverse.  Alone it
+                                          changes nothing.  Read by every multi-input convolve; the results agree to rounding
+                                          (OFFT_CONV_SUM_MIXED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -22,6 +22,7 @@ PARAM_NAMES = ["P1", "T1", "W1", "Px1", "Py1", "Fz", "FP1", "Ux1", "Uz1", "FU1",
 FFTW_ESTIMATE = 1 << 6
 F64, F32 = 0, 1
 FILTER_REAL, FILTER_COMPLEX = 0, 1  # offt_hip.h OFFT_HIP_FILTER_REAL / OFFT_HIP_FILTER_COMPLEX
+OPT_CONV_SUM_MIXED = 16  # offt_hip.h OFFT_HIP_OPT_CONV_SUM_MIXED: with OPT_CONV_MIXED, the multi-input convolve of such a plan may run the fused gather route (15 is unassigned)
 OPT_CONV_MULTI_MIXED = 14  # offt_hip.h OFFT_HIP_OPT_CONV_MULTI_MIXED: with OPT_CONV_MIXED, the multi-output convolve of such a plan may run the fused multi route
 OPT_HALF_R2C_MIXED = 13  # offt_hip.h OFFT_HIP_OPT_HALF_R2C_MIXED: with the two below, a real-input half-box plan with mixed-radix extents may skip the padding
 OPT_CONV_MIXED = 12  # offt_hip.h OFFT_HIP_OPT_CONV_MIXED: the convolve of a plan whose x extent is no power of two may run the fused route

@@ -159,7 +159,10 @@ typedef struct offt_filter_desc {
    * single precision), 0 = such a length has no fused kernel (plan option OFFT_HIP_OPT_CONV_MIXED).  Bit 2 (value 2) = such a
    * length may run the out-of-place kernel too (fft_conv_oop_panelx_k, fft_conv_oop_half_panelx_k, the same lengths;
    * offt_hipk_conv_pass_oop; plan option OFFT_HIP_OPT_CONV_MULTI_MIXED): it counts only together with bit 1 (mixed = 3), and
-   * the in-place launch does not look at it.  A power-of-two length resolves to the same kernel whatever the field says. */
+   * the in-place launch does not look at it.  Bit 3 (value 4) = such a length may run the multi-input gather kernel
+   * (fft_conv_sum_panelx_k, fft_conv_sum_half_panelx_k, the same lengths; offt_hipk_conv_pass_sum; plan option
+   * OFFT_HIP_OPT_CONV_SUM_MIXED): it too counts only together with bit 1 ((mixed & 5) == 5), and no other launch looks at
+   * it.  A power-of-two length resolves to the same kernel whatever the field says. */
   int mixed;
   long long axis_stride, col_stride, b1_stride, b2_stride;
 } offt_filter_desc;
@@ -211,15 +214,19 @@ int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int p
  * filters[k] (all addressed by f) and added in the order k = 0 ... nin-1 in registers; ONE inverse transform of the sum,
  * times fwd->scale, is stored to `dst` at the same offsets.  `dst` may be one of the sources (a workgroup has loaded its lines
  * from every source before its only stores); no other source is written.  fwd->half: 0 or 3; fwd->out_keep: the cache-keeping
- * twin (every instance has one).  Power-of-two lines of 64 ... 1024 points; a mixed-radix length has no kernel whatever
- * f->mixed says.  -1, and nothing launched, for nin < 1, nin > OFFT_HIPK_CONV_MAX_IN, a NULL pointer or no kernel. */
+ * twin (every power-of-two instance has one).  Power-of-two lines of 64 ... 1024 points; with bits 1 and 3 of f->mixed
+ * both set ((f->mixed & 5) == 5) also the mixed-radix lengths listed at offt_filter_desc::mixed, whose instances have no
+ * cache-keeping twin (fwd->out_keep is ignored there); with any other f->mixed such a length finds no kernel.  -1, and
+ * nothing launched, for nin < 1, nin > OFFT_HIPK_CONV_MAX_IN, a NULL pointer or no kernel. */
 #define OFFT_HIPK_CONV_MAX_IN 8
 int offt_hipk_conv_pass_sum(const offt_pass_desc *fwd, const offt_filter_desc *f, int nin, const void *const *filters,
                             const void *const *srcs, void *dst, void *stream);
 /* 1 if offt_hipk_conv_pass_sum has a kernel for (fwd, f): pick_conv's conditions (contiguous lines, unit-stride filter axis,
- * no split, half 0 or 3) at a power of two; the registry lookup needs no device */
+ * no split, half 0 or 3) at a power of two or, with bits 1 and 3 of f->mixed, at one of the mixed-radix lengths; the
+ * registry lookup needs no device */
 int offt_hipk_conv_has_fused_sum(const offt_pass_desc *fwd, const offt_filter_desc *f);
-/* "fft_conv_sum_panel_k", "fft_conv_sum_half_panel_k" (fwd->half = 3) or "no fused kernel" */
+/* "fft_conv_sum_panel_k", "fft_conv_sum_half_panel_k" (fwd->half = 3), with (f->mixed & 5) == 5 at a mixed-radix length
+ * "fft_conv_sum_panelx_k", "fft_conv_sum_half_panelx_k" (fwd->half = 3), or "no fused kernel" */
 const char *offt_hipk_conv_sum_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f);
 /* out[i0 s0 + i1 s1 + i2 s2] = sum_k ins[k][same] * filters[k][same] over the box n0 x n1 x n2, the terms added in the order
  * k = 0 ... nin-1: ONE sweep, non-temporal, 16 B per lane along the smallest stride.  `out` may be one of the inputs. */

@@ -448,6 +448,8 @@ typedef struct hip_state {
                             length that is no power of two takes the unfused route */
     int conv_multi_mixed; /* multi-output convolve: 1 = together with conv_mixed the out-of-place fused launch may run on the
                             mixed-radix kernels too (bit 2 of offt_filter_desc::mixed), 0 = such a length takes the generic route */
+    int conv_sum_mixed;  /* multi-input convolve: 1 = together with conv_mixed the gather launch may run on the mixed-radix
+                            kernels too (bit 3 of offt_filter_desc::mixed), 0 = such a length takes the generic route */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -1172,6 +1174,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.half_r2c_mixed = getenv("OFFT_HALF_R2C_MIXED") && atoi(getenv("OFFT_HALF_R2C_MIXED")) != 0;
   st->opt.conv_mixed = getenv("OFFT_CONV_MIXED") && atoi(getenv("OFFT_CONV_MIXED")) != 0;
   st->opt.conv_multi_mixed = getenv("OFFT_CONV_MULTI_MIXED") && atoi(getenv("OFFT_CONV_MULTI_MIXED")) != 0;
+  st->opt.conv_sum_mixed = getenv("OFFT_CONV_SUM_MIXED") && atoi(getenv("OFFT_CONV_SUM_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
   st->opt.block_pad = getenv("OFFT_BLOCK_PAD") && atoi(getenv("OFFT_BLOCK_PAD")) != 0;
@@ -1652,6 +1655,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
       break;
     case OFFT_HIP_OPT_CONV_MIXED: st->opt.conv_mixed = value != 0; break; /* read by every convolve (conv_fused_route) */
     case OFFT_HIP_OPT_CONV_MULTI_MIXED: st->opt.conv_multi_mixed = value != 0; break; /* read by every multi-output convolve (conv_fused_route, CONV_OOP) */
+    case OFFT_HIP_OPT_CONV_SUM_MIXED: st->opt.conv_sum_mixed = value != 0; break; /* read by every multi-input convolve (conv_fused_route, CONV_SUM) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
@@ -1691,6 +1695,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_HALF_R2C_MIXED: return st->opt.half_r2c_mixed;
     case OFFT_HIP_OPT_CONV_MIXED: return st->opt.conv_mixed;
     case OFFT_HIP_OPT_CONV_MULTI_MIXED: return st->opt.conv_multi_mixed;
+    case OFFT_HIP_OPT_CONV_SUM_MIXED: return st->opt.conv_sum_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
     case OFFT_HIP_OPT_P2P_TIMEOUT_S: return (long long)st->opt.p2p_timeout_s;
@@ -3080,8 +3085,9 @@ static int conv_leave(struct _offt_plan *po, double t0, int rc) {
  * in-place one's conditions (the single-input kernel is asked for as well: every length with one of the others has it).
  * Out of place: powers of two from 64 to 1024, and a mixed-radix x extent that has a fused kernel where
  * OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_MULTI_MIXED are BOTH set (bits 1 and 2 of offt_filter_desc::mixed; the
- * in-place launch of an output that is `data` reads bit 1 alone).  Gather: powers of two from 64 to 1024 (a mixed-radix x
- * extent has no such kernel, whatever the plan's options say). */
+ * in-place launch of an output that is `data` reads bit 1 alone).  Gather: powers of two from 64 to 1024, and a mixed-radix x
+ * extent that has a gather kernel where OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_SUM_MIXED are BOTH set (bits 1 and 3
+ * of offt_filter_desc::mixed). */
 static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, int kind, conv_flavour flavour,
                             offt_pass_desc *fd, offt_filter_desc *fl) {
   hip_state *st = (hip_state *)po->hip_state;
@@ -3111,7 +3117,10 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
     if (!inplace) return 0;
     if (st->opt.conv_mixed && st->opt.conv_multi_mixed) fl->mixed |= 2;
     return offt_hipk_conv_has_fused_oop(fd, fl);
-  case CONV_SUM: return inplace ? offt_hipk_conv_has_fused_sum(fd, fl) : 0;
+  case CONV_SUM:
+    if (!inplace) return 0;
+    if (st->opt.conv_mixed && st->opt.conv_sum_mixed) fl->mixed |= 4;
+    return offt_hipk_conv_has_fused_sum(fd, fl);
   default: return inplace;
   }
 }

@@ -557,6 +557,8 @@ void build_registry() {
   reg_conv_mixed_f32();
   reg_conv_oop_mixed_f64();
   reg_conv_oop_mixed_f32();
+  reg_conv_sum_mixed_f64();
+  reg_conv_sum_mixed_f32();
   reg_conv_sum_f64();
   reg_conv_sum_f32();
   reg_half_f64();
@@ -2014,8 +2016,8 @@ int pointwise_launch(const char *who, const void *in, void *out, bool oop, const
   return 0;
 }
 
-// the multi-input instance for (fwd, f), or nullptr: pick_conv's conditions; the power-of-two lengths only, whatever
-// f->mixed says (no mixed-radix instance exists)
+// the multi-input instance for (fwd, f), or nullptr: pick_conv's conditions.  The power-of-two lengths whatever f->mixed
+// says; the mixed-radix instances (fft_conv_sum_panelx_k, no keeping twin) only with bits 1 and 3 of f->mixed both set
 Variant *pick_conv_sum(const offt_pass_desc *d, const offt_filter_desc *f, bool keep) {
   if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
   if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
@@ -2023,7 +2025,8 @@ Variant *pick_conv_sum(const offt_pass_desc *d, const offt_filter_desc *f, bool 
     return nullptr;
   if (d->half && d->half != 3) return nullptr;
   Variant *v = find_variant(VariantKey{d->n, d->precision, true, true, Role::ConvSum, keep, d->half});
-  return v && !v->mixed ? v : nullptr;
+  if (v && v->mixed && (f->mixed & 5) != 5) return nullptr;
+  return v;
 }
 
 bool fill_sum_args(const char *who, SumArgs &sa, int nin, const void *const *srcs, const void *const *filters) {

@@ -1901,6 +1901,273 @@ fft_conv_oop_half_panelx_k(PassArgs a, ConvArgs f, const typename vec2<T>::type 
   convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, src, dst, filter, twt);
 }
 
+// Multi-input spectral convolution of whole lines of a mixed-radix length (offt_hipk_conv_pass_sum with bits 1 and 3 of
+// offt_filter_desc::mixed): to convx_body what conv_sum_body is to conv_body -- its first half in a loop over the inputs.
+// Per workgroup, for k = 0 ... nin-1: load the panel from src[k] (convx_body's loads), forward stages, times H_k in the last
+// stage's register order, added into acc[EMAX] in that order (k ascending: the same bits on every run); then conjugate, the
+// one round trip through the exchange image, the stages again, conjugate, scale, store to dst at the load offsets.  The
+// sources and filters travel by value and are read through sum_pick (see conv_sum_body).  A butterfly that is predicated
+// off holds zeros in v and adds zeros.  In place on any ONE source: a workgroup owns whole lines and has loaded them from
+// every source before its only stores.  HALF and the limits (contiguous lines, no split, complex data) as in convx_body.
+// A __syncthreads() closes every pass of the loop: the first exchange of `stages` has no barrier in front of it, and input
+// k's last exchange reads must be done before input k+1's first exchange (or the round trip) writes the image.
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT, bool HALF = false>
+__device__ __forceinline__ void convx_sum_body(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>::type *dst,
+                                               const typename vec2<T>::type *twt) {
+  using V2 = typename vec2<T>::type;
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int NT = Cfg::NT, NSTAGE = Cfg::NSTAGE, LSTRIDE = Cfg::LSTRIDE, EMAX = Cfg::EMAX;
+  constexpr int PADDIV = Cfg::PADDIV;
+  static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
+  static_assert(smooth235(R0) && smooth235(R1) && smooth235(R2), "radices must be products of primes <= 13, or primes <= 31");
+  static_assert(R0 <= 32 && R1 <= 32 && R2 <= 32, "register radix <= 32");
+  static_assert(NSTAGE > 1, "the round trip goes through the exchange image");
+  static_assert(Cfg::QUARTER, "quarter-wave twiddle table: N is a multiple of 4");
+  constexpr int RL = NSTAGE == 3 ? R2 : R1;  // radix of the last stage
+  static_assert(!HALF || (R0 % 2 == 0 && RL % 2 == 0), "half lines: first and last radix even");
+  constexpr int NBF0 = N / R0, NB0 = cdiv(NBF0, TPL);  // butterflies per line / per thread, first stage
+  constexpr int NBFL = N / RL, NBL = cdiv(NBFL, TPL);  // ... last stage
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T *exs = reinterpret_cast<T *>(smem);
+  V2 *exv = reinterpret_cast<V2 *>(smem);
+  V2 *tw = reinterpret_cast<V2 *>(smem + Cfg::TW_OFF);
+
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Cfg::QT; i += NT) tw[i] = twt[i];  // (visible after the first exchange's barrier)
+  auto pad = [](int i) {
+    if constexpr (Cfg::SWZ) return i ^ ((i / R0) & 15);
+    else if constexpr (PADDIV > 0) return i + i / PADDIV;
+    else return i;
+  };
+
+  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const int cp = bid % (unsigned)a.ncp;
+  const unsigned rest = bid / (unsigned)a.ncp;
+  const int b1 = rest % (unsigned)a.nb1;
+  const int b2 = rest / (unsigned)a.nb1;
+  const int c0 = cp * COLS;
+  const int j = tid % TPL, c = tid / TPL;
+  const bool valid = (c0 + c) < a.ncols;
+  const long long lo = (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col;
+  const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col;
+  // butterfly u of a stage with NBF butterflies per line is live for this thread (compile-time true but for the last one)
+  auto live0 = [&](int u) { return (u + 1) * TPL <= NBF0 || j + u * TPL < NBF0; };
+  auto liveL = [&](int u) { return (u + 1) * TPL <= NBFL || j + u * TPL < NBFL; };
+  auto at = [&](int i) { return c * LSTRIDE + pad(i); };
+
+  cx<T> v[EMAX];
+
+  // convx_body's stages (contiguous / contiguous), ending in the last stage's register order:
+  // v[u RL + perm_mixed(RL, t)] holds line index j + u TPL + t N/RL
+  auto stages = [&](auto upper_zero) {
+    static_for<0, NSTAGE>([&](auto sidx) {
+      constexpr int s = decltype(sidx)::value;
+      constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
+      constexpr int Ns = (s == 0) ? 1 : ((s == 1) ? R0 : R0 * R1);
+      constexpr int NBF = N / R;
+      constexpr int NB = cdiv(NBF, TPL);
+      if constexpr (s > 0) {
+        constexpr int M = N / (Ns * R);
+        static_for<0, NB>([&](auto uu) {
+          constexpr int u = decltype(uu)::value;
+          const int q = j + u * TPL;
+          const int km = (q % Ns) * M;
+          static_for<1, R>([&](auto tt) {
+            constexpr int t = decltype(tt)::value;
+            const int e = km * t;            // <= (Ns-1)(R-1)M < N, also for a predicated-off butterfly
+            const int qd = e / (N / 4);
+            const V2 w = tw[e - qd * (N / 4)];
+            T cr = (qd & 1) ? w.y : w.x;     // times (-i)^qd
+            T ci = (qd & 1) ? -w.x : w.y;
+            if (qd & 2) { cr = -cr; ci = -ci; }
+            const cx<T> x = v[u * R + t];
+            v[u * R + t] = cx<T>{x.x * cr - x.y * ci, x.x * ci + x.y * cr};
+          });
+        });
+      }
+      static_for<0, NB>([&](auto uu) { dft_mixed<T, R, s == 0 && decltype(upper_zero)::value>(&v[decltype(uu)::value * R]); });
+      if constexpr (s < NSTAGE - 1) {
+        constexpr int Rn = (s == 0) ? R1 : R2;
+        constexpr int NBFn = N / Rn, NBn = cdiv(NBFn, TPL);
+        auto wr_idx = [&](int u, int t) {
+          const int q = j + u * TPL;
+          const int k = q % Ns;
+          return at((q - k) * R + k + t * Ns);
+        };
+        auto wr_live = [&](int u) { return (u + 1) * TPL <= NBF || j + u * TPL < NBF; };
+        auto rd_idx = [&](int u, int t) { return at(j + u * TPL + t * NBFn); };
+        auto rd_live = [&](int u) { return (u + 1) * TPL <= NBFn || j + u * TPL < NBFn; };
+        if constexpr (s > 0) __syncthreads();  // previous exchange's reads done
+        if constexpr (SPLIT) {
+          static_for<0, NB * R>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            constexpr int src = u * R + perm_mixed(R, t);
+            if (wr_live(u)) exs[wr_idx(u, t)] = v[src].x;
+          });
+          __syncthreads();
+          T re[NBn * Rn];
+          static_for<0, NBn * Rn>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            re[decltype(ii)::value] = rd_live(u) ? exs[rd_idx(u, t)] : (T)0;
+          });
+          __syncthreads();
+          static_for<0, NB * R>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            constexpr int src = u * R + perm_mixed(R, t);
+            if (wr_live(u)) exs[wr_idx(u, t)] = v[src].y;
+          });
+          __syncthreads();
+          static_for<0, NBn * Rn>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], rd_live(u) ? exs[rd_idx(u, t)] : (T)0};
+          });
+        } else {
+          static_for<0, NB * R>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            constexpr int src = u * R + perm_mixed(R, t);
+            const cx<T> x = v[src];
+            V2 w; w.x = x.x; w.y = x.y;
+            if (wr_live(u)) exv[wr_idx(u, t)] = w;
+          });
+          __syncthreads();
+          static_for<0, NBn * Rn>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            V2 w; w.x = 0; w.y = 0;
+            if (rd_live(u)) w = exv[rd_idx(u, t)];
+            v[decltype(ii)::value] = cx<T>{w.x, w.y};
+          });
+        }
+      }
+    });
+  };
+
+  // acc[r] += v[r] * H_k[n], r the last stage's register order; filter values are read once: non-temporal.  (A butterfly
+  // that is off holds zeros in v, and its filter value is a zero too: it adds zeros.)
+  cx<T> acc[EMAX];
+  static_for<0, EMAX>([&](auto ii) { acc[decltype(ii)::value] = cx<T>{0, 0}; });
+  auto filt = [&](const void *filter, auto complex_filter) {
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int r = u * RL + perm_mixed(RL, t);
+      const int n = j + u * TPL + t * NBFL;
+      const long long off = fb + (long long)n * f.axis;
+      const bool on = valid && liveL(u);
+      const cx<T> x = v[r];
+      if constexpr (decltype(complex_filter)::value) {
+        V2 h;
+        h.x = 0; h.y = 0;
+        if (on) h = gload(reinterpret_cast<const V2 *>(filter) + off);
+        const T pr = x.x * h.x - x.y * h.y, pi = x.x * h.y + x.y * h.x;
+        acc[r] = cx<T>{acc[r].x + pr, acc[r].y + pi};
+      } else {
+        T h = 0;
+        if (on) h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + off);
+        acc[r] = cx<T>{acc[r].x + x.x * h, acc[r].y + x.y * h};
+      }
+    });
+  };
+
+#pragma nounroll
+  for (int k = 0; k < sa.nin; k++) {
+    const V2 *line = reinterpret_cast<const V2 *>(sum_pick(sa.src, k)) + lo;
+    static_for<0, NB0 * R0>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      if constexpr (HALF && 2 * t >= R0) {
+        v[decltype(ii)::value] = cx<T>{T{}, T{}};  // the padding: a literal zero (and the first butterfly knows it)
+        return;
+      }
+      const int n = j + u * TPL + t * NBF0;
+      V2 val;
+      val.x = 0; val.y = 0;
+      if (valid && live0(u)) val = gload(line + (long long)n * a.in_axis);
+      v[decltype(ii)::value] = cx<T>{val.x, val.y};
+    });
+    stages(std::integral_constant<bool, HALF>{});
+    const void *filter = sum_pick(sa.filter, k);
+    if (f.cplx) filt(filter, std::true_type{});
+    else filt(filter, std::false_type{});
+    __syncthreads();  // this input's last exchange reads done: before the next input's first exchange write, or the round trip's
+  }
+
+  // the sum, conjugated (the inverse as conj(F(conj(.)))), through the exchange image: from the last stage's order back
+  // into the load distribution
+  if constexpr (SPLIT) {
+    T re[NB0 * R0];
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int src = u * RL + perm_mixed(RL, t);
+      if (liveL(u)) exs[at(j + u * TPL + t * NBFL)] = acc[src].x;
+    });
+    __syncthreads();
+    static_for<0, NB0 * R0>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      re[decltype(ii)::value] = live0(u) ? exs[at(j + u * TPL + t * NBF0)] : (T)0;
+    });
+    __syncthreads();
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int src = u * RL + perm_mixed(RL, t);
+      if (liveL(u)) exs[at(j + u * TPL + t * NBFL)] = -acc[src].y;
+    });
+    __syncthreads();
+    static_for<0, NB0 * R0>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], live0(u) ? exs[at(j + u * TPL + t * NBF0)] : (T)0};
+    });
+  } else {
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int src = u * RL + perm_mixed(RL, t);
+      const cx<T> x = acc[src];
+      V2 w; w.x = x.x; w.y = -x.y;
+      if (liveL(u)) exv[at(j + u * TPL + t * NBFL)] = w;
+    });
+    __syncthreads();
+    static_for<0, NB0 * R0>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      V2 w; w.x = 0; w.y = 0;
+      if (live0(u)) w = exv[at(j + u * TPL + t * NBF0)];
+      v[decltype(ii)::value] = cx<T>{w.x, w.y};
+    });
+  }
+  __syncthreads();  // the round trip's reads done before the first exchange of the second half writes
+
+  stages(std::false_type{});
+
+  V2 *sline = dst + lo;
+  const T sc = (T)a.scale;
+  static_for<0, NBL * RL>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+    if constexpr (HALF && 2 * t >= RL) return;  // the upper half of the output is not wanted
+    const int n = j + u * TPL + t * NBFL;
+    constexpr int src = u * RL + perm_mixed(RL, t);
+    const cx<T> x = v[src];
+    V2 w;
+    w.x = x.x * sc;
+    w.y = -x.y * sc;
+    if (valid && liveL(u)) gstore(sline + (long long)n * a.in_axis, w);
+  });
+}
+
+// (v[EMAX] and acc[EMAX] live together under the butterfly temporaries: the instances are compiled for the fewest waves per
+//  SIMD their workgroup admits -- 1 at up to 256 threads, 512 registers a lane -- as the power-of-two gather kernels with 64
+//  data VGPRs are (conv_sum_wps); their shapes, offt_reg_conv_sum_mixed_*.hip, are chosen so that nothing spills there)
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+constexpr int convx_sum_wps() { return PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>::WPS_MIN; }
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_sum_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_sum_panelx_k(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>::type *dst, const typename vec2<T>::type *twt) {
+  convx_sum_body<T, N, TPL, R0, R1, R2, COLS, SPLIT>(a, f, sa, dst, twt);
+}
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_sum_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_conv_sum_half_panelx_k(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>::type *dst, const typename vec2<T>::type *twt) {
+  convx_sum_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, sa, dst, twt);
+}
+
 // ---------------------------------------------------------------------------
 // variant registry: every instantiation registers itself under a VariantKey (which kernel it is) and an id
 // ---------------------------------------------------------------------------
@@ -1913,6 +2180,7 @@ enum class Role {
   Conv,     // fused convolution in place (offt_hipk_conv_pass): fft_conv_panel_k, fft_conv_half_panel_k and their panelx twins
   ConvOop,  // ... with a separate store base (offt_hipk_conv_pass_oop): fft_conv_oop_panel_k, fft_conv_oop_half_panel_k, ...
   ConvSum,  // several sources summed into one destination (offt_hipk_conv_pass_sum): fft_conv_sum_panel_k, fft_conv_sum_half_panel_k
+            // and their panelx twins
 };
 // column-pair instances (T = f32x2) are kept under their own precision so that the one-column variants and their ids stay
 // what they were
@@ -2211,6 +2479,18 @@ void reg_variantx_conv_oop() {
               "fft_conv_oop_half_panelx_k", " out-of-place convolution on half lines");
 }
 
+// multi-input fused convolution at a mixed-radix length (fft_conv_sum_panelx_k, fft_conv_sum_half_panelx_k;
+// offt_reg_conv_sum_mixed_*.hip; picked only with bits 1 and 3 of offt_filter_desc::mixed): shapes of their own (the
+// accumulator on top of convx_body's registers), full lines and half lines, no cache-keeping twin
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variantx_conv_sum() {
+  const VariantShape s = panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>();
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::ConvSum, false, 0}, s, (const void *)fft_conv_sum_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_conv_sum_panelx_k", " multi-input convolution");
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::ConvSum, false, 3}, s, (const void *)fft_conv_sum_half_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_conv_sum_half_panelx_k", " multi-input convolution on half lines");
+}
+
 // instantiation groups (offt_reg_*.hip)
 void reg_pow2_f64();
 void reg_pow2_f64_1024();
@@ -2237,6 +2517,8 @@ void reg_conv_oop_mixed_f64();
 void reg_conv_oop_mixed_f32();
 void reg_conv_sum_f64();
 void reg_conv_sum_f32();
+void reg_conv_sum_mixed_f64();
+void reg_conv_sum_mixed_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();

@@ -29,13 +29,22 @@ tests/liboffthip_test.so, which the probe then loads instead of the product; not
 after a warm-up, MIXED_REPS times each, and the line reports min and median of all three, the ratios against both, each
 baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5 (344 / 600 and 344 / 472 for K = 3).
 sum:half:N does so on a pruned half-box plan (an N/2 box).
-usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+A spec with the prefix sum:mixed: measures OFFT_HIP_OPT_CONV_SUM_MIXED (the fused multi-input route at x lengths that are no
+powers of two), with OFFT_HIP_OPT_CONV_MIXED on throughout, K = 3 real filters and out = ins[0]: the call with the option at 1
+ALTERNATES with the call with the option at 0 (the generic route: the code of before the option existed) and with three
+offt_hip_execute_convolve calls plus two in-place torch adds, on the same plan and buffers, MIXED_REPS times each after a
+warm-up.  The line reports min and median of all three, the ratios against both baselines, each baseline's own spread
+(median / min - 1) and the byte model of DESIGN.md 4.5 (344 / 472 and 344 / 600 for K = 3).  sum:mixed:half:N does so on a
+pruned half-box plan (OFFT_HIP_OPT_HALF_MIXED, an N/2 box).
+usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
        (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768;
         the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512;
         the multi:mixed: set of profiles/conv_multi_mixed.txt: multi:mixed:768 multi:mixed:f32:768 multi:mixed:1000
         multi:mixed:f32:1000 multi:mixed:half:768;
         the sum: set of profiles/conv_sum.txt: sum:512 sum:1024 sum:f32:1024 sum:r2c:512 sum:half:512, and for the shorter
-        x lengths sum:64 sum:128 sum:256 sum:f32:256 sum:f32:512)"""
+        x lengths sum:64 sum:128 sum:256 sum:f32:256 sum:f32:512;
+        the sum:mixed: set of profiles/conv_sum_mixed.txt: sum:mixed:768 sum:mixed:f32:768 sum:mixed:1000 sum:mixed:f32:1000
+        sum:mixed:half:768)"""
 import ctypes as C
 import os
 import sys
@@ -46,7 +55,7 @@ import torch  # noqa: E402
 
 from offt_amd import api  # noqa: E402
 
-if any(a.startswith("sum:") for a in sys.argv[1:]):
+if any(a.startswith("sum:") and not a.startswith("sum:mixed:") for a in sys.argv[1:]):
     # the sum: specs time the generic route as well, which needs the build with the test seams (the same kernel objects)
     api.use_library(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "liboffthip_test.so"))
 L = api.lib()
@@ -146,6 +155,77 @@ def probe_sum(rest, zg):
     torch.cuda.empty_cache()
 
 
+def probe_sum_mixed(rest, zg):
+    """sum:mixed:[half:][f64|f32|r2c:]N -- OFFT_HIP_OPT_CONV_SUM_MIXED at 1 and at 0 and the caller's route, on one plan"""
+    K = 3
+    half = rest.startswith("half:")
+    kind, _, n_s = rest[(5 if half else 0):].rpartition(":")
+    n = int(n_s)
+    prec = api.F32 if kind == "f32" else api.F64
+    r2c = kind == "r2c"
+    po = api.offt_3d_init(n, n, n, precision=prec, is_r2c=int(r2c))
+    if zg is not None:
+        L.offt_hip_set_option(po, OPT_ZGROUP_MIB, zg)
+    L.offt_hip_set_option(po, api.OPT_CONV_MIXED, 1)
+    if half:
+        L.offt_hip_set_option(po, api.OPT_HALF_MIXED, 1)
+        api.offt_hip_set_half_box(po, True)
+    td = torch.float32 if prec == api.F32 else torch.float64
+    ne = api.local_elems(po)
+    ins = [torch.zeros(ne * 2, dtype=td, device="cuda") for _ in range(K)]
+    for x in ins:
+        L.offt_hip_fill_input(po, x.data_ptr(), 1)
+    Hs = [torch.rand(ne, dtype=td, device="cuda") * (1.0 / (K * float(n) ** 3)) for _ in range(K)]  # keeps the field bounded
+    ip, fp = [x.data_ptr() for x in ins], [h.data_ptr() for h in Hs]
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def run(fn):
+        ev[0].record()
+        fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) * 1e-3
+
+    def base():  # what a caller does without the call: K convolves and K - 1 add sweeps of their own
+        for x, h in zip(ip, fp):
+            api.offt_hip_execute_convolve(po, x, h, api.FILTER_REAL)
+        for x in ins[1:]:
+            ins[0].add_(x)
+
+    def sm():
+        api.offt_hip_execute_convolve_sum(po, ip, fp, ip[0], api.FILTER_REAL)
+
+    t = {"on": [], "off": [], "base": []}
+    route = {}
+    for rep_i in range(2 + MIXED_REPS):
+        for name, fn, v in (("on", sm, 1), ("off", sm, 0), ("base", base, 1)):
+            L.offt_hip_set_option(po, api.OPT_CONV_SUM_MIXED, v)  # (outside the timed region)
+            route[name] = api.offt_hip_convolve_sum_fused(po)
+            dt = run(fn)
+            if rep_i >= 2:
+                t[name].append(dt)
+    L.offt_hip_set_option(po, api.OPT_CONV_SUM_MIXED, 0)
+    mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+    fused1 = api.offt_hip_convolve_fused(po)
+    tag = f"{'r2c f64' if r2c else ('f32' if prec == api.F32 else 'f64')} {n}^3 K={K}"
+    if half:
+        tag += f" half box {n // 2}^3 [{'pruned' if api.offt_hip_half_box_pruned(po) else 'fallback'}]"
+    # bytes per point, f64, complex plan, full lines (DESIGN.md 4.5): baseline 168 K + 48 (K - 1), generic 120 K + 112, fused 88 K + 80
+    mb, mg, mf = 168 * K + 48 * (K - 1), 120 * K + 112, 88 * K + 80
+    print(f"sum:mixed: {tag}: option 1 [{'fused' if route['on'] else 'generic'}] min {mn['on'] * 1e3:.3f} ms median {md['on'] * 1e3:.3f} ms  "
+          f"option 0 [{'fused' if route['off'] else 'generic'}] min {mn['off'] * 1e3:.3f} ms median {md['off'] * 1e3:.3f} ms  "
+          f"{K} calls + {K - 1} adds [{'fused' if fused1 else 'unfused'}] min {mn['base'] * 1e3:.3f} ms median {md['base'] * 1e3:.3f} ms  "
+          f"1/0 min {mn['on'] / mn['off']:.3f} median {md['on'] / md['off']:.3f}  "
+          f"1/base min {mn['on'] / mn['base']:.3f} median {md['on'] / md['base']:.3f}  "
+          f"option-0 spread {md['off'] / mn['off'] - 1:.3f}  base spread {md['base'] / mn['base'] - 1:.3f}  "
+          f"byte model (complex, full lines) fused/generic {mf / mg:.3f} fused/base {mf / mb:.3f}  "
+          f"n {MIXED_REPS}  zgroup_mib {L.offt_hip_get_option(po, OPT_ZGROUP_MIB)}", flush=True)
+    api.offt_3d_fin(po)
+    del ins, Hs
+    torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
     zg = None
@@ -156,6 +236,9 @@ def main():
     specs = args or ["1024", "f32:1024", "r2c:512", "mixed:768", "mixed:f32:768", "mixed:1000", "mixed:f32:1000", "mixed:half:768"]
     torch.cuda.set_device(0)
     for spec in specs:
+        if spec.startswith("sum:mixed:"):
+            probe_sum_mixed(spec[10:], zg)
+            continue
         if spec.startswith("sum:"):
             probe_sum(spec[4:], zg)
             continue
