@@ -124,6 +124,29 @@ int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *i
  * or, with OFFT_HIP_OPT_CONV_MIXED and OFFT_HIP_OPT_CONV_SUM_MIXED both set, one of the mixed-radix lengths listed there;
  * 0: the generic route (a forward per input, one multiply-and-sum sweep, one inverse) */
 int offt_hip_convolve_sum_fused(const struct _offt_plan *po);
+/* Filtered forward and filtered inverse: the two halves of a convolve as calls of their own, for a solver that keeps its
+ * state as a spectrum (pseudo-spectral Navier-Stokes, Cahn-Hilliard, spectral field solves).  Filters are laid out and
+ * typed as for offt_hip_execute_convolve.
+ * Forward: data (input layout) becomes H . fftn(data) in the forward's OUTPUT layout, in place -- what offt_3d_execute
+ * followed by a multiply with H leaves, offt_hip_set_output_scale included (a dealiasing mask or projector on the
+ * nonlinear term).
+ * Inverse: outs[k] = unnormalised inverse transform of filters[k] . spec, k = 0 ... nout-1, each in the INPUT layout with
+ * the output scale on its final store (real values for an r2c plan) -- the velocity and its derivatives, i k_j u^, from
+ * one stored spectrum.  spec is in the forward's output layout and is NOT written, unless it is one of outs[]: at most
+ * one may be, and the library makes it last whatever its position.  Every outs[k] has offt_hip_local_bytes bytes;
+ * 1 <= nout <= OFFT_HIP_CONV_MAX_OUT.
+ * With scale 1, inverse_filtered(forward_filtered(x, H1), [H2]) equals offt_hip_execute_convolve(x, H1 . H2) to rounding.
+ * On one rank, in the z-y-x layout, with a power-of-two x extent from 64 to 1024 and no half box, the x pass carries the
+ * multiply where OFFT_HIP_OPT_SPEC_FUSED is set (off by default); every other plan transforms and multiplies in separate launches.  Stream, async,
+ * offt_hip_last_device_seconds and OFFT_HIP_OPT_ZGROUP_MIB are honoured as in offt_hip_execute_convolve_multi.
+ * Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and offt_hip_last_error(), and nothing launched,
+ * for a NULL or host-memory argument, a bad nout, two equal outs entries, an unknown filter_kind, a backend without the
+ * multiply, a failed communicator. */
+int offt_hip_execute_forward_filtered(struct _offt_plan *po, void *data, const void *filter, int filter_kind);
+int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, int nout, void *const *outs, const void *const *filters,
+                                      int filter_kind);
+/* 1 if both calls take the fused route on this plan, else 0 */
+int offt_hip_spectral_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
  *   full spectrum of the zero-padded field, in the usual output layout.
@@ -201,6 +224,11 @@ int offt_hip_wait(struct _offt_plan *po);
                                           0 (default) = a forward per input, one multiply-and-sum sweep, one inverse.  Alone it
                                           changes nothing.  Read by every multi-input convolve; the results agree to rounding
                                           (OFFT_CONV_SUM_MIXED) */
+/* (17 is not assigned either) */
+#define OFFT_HIP_OPT_SPEC_FUSED 18     /* filtered forward / inverse: 1 = the x pass carries the multiply where the plan has that route
+                                          (offt_hip_spectral_fused: one rank, z-y-x, a power-of-two x extent from 64 to 1024, no half
+                                          box), 0 (default) = transform and multiply as separate launches.  Read by every filtered
+                                          call; the results agree to rounding (OFFT_SPEC_FUSED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -22,6 +22,7 @@ PARAM_NAMES = ["P1", "T1", "W1", "Px1", "Py1", "Fz", "FP1", "Ux1", "Uz1", "FU1",
 FFTW_ESTIMATE = 1 << 6
 F64, F32 = 0, 1
 FILTER_REAL, FILTER_COMPLEX = 0, 1  # offt_hip.h OFFT_HIP_FILTER_REAL / OFFT_HIP_FILTER_COMPLEX
+OPT_SPEC_FUSED = 18  # (17 is unassigned) offt_hip.h OFFT_HIP_OPT_SPEC_FUSED: the filtered forward / inverse may run the route whose x pass carries the multiply
 OPT_CONV_SUM_MIXED = 16  # offt_hip.h OFFT_HIP_OPT_CONV_SUM_MIXED: with OPT_CONV_MIXED, the multi-input convolve of such a plan may run the fused gather route (15 is unassigned)
 OPT_CONV_MULTI_MIXED = 14  # offt_hip.h OFFT_HIP_OPT_CONV_MULTI_MIXED: with OPT_CONV_MIXED, the multi-output convolve of such a plan may run the fused multi route
 OPT_HALF_R2C_MIXED = 13  # offt_hip.h OFFT_HIP_OPT_HALF_R2C_MIXED: with the two below, a real-input half-box plan with mixed-radix extents may skip the padding
@@ -110,6 +111,12 @@ def bind(L):
     L.offt_hip_execute_convolve_sum.argtypes = [PP, i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i, C.c_void_p]
     L.offt_hip_convolve_sum_fused.restype = i
     L.offt_hip_convolve_sum_fused.argtypes = [PP]
+    L.offt_hip_execute_forward_filtered.restype = i
+    L.offt_hip_execute_forward_filtered.argtypes = [PP, C.c_void_p, C.c_void_p, i]
+    L.offt_hip_execute_inverse_filtered.restype = i
+    L.offt_hip_execute_inverse_filtered.argtypes = [PP, C.c_void_p, i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i]
+    L.offt_hip_spectral_fused.restype = i
+    L.offt_hip_spectral_fused.argtypes = [PP]
     L.offt_hip_set_half_box.restype = i
     L.offt_hip_set_half_box.argtypes = [PP, i]
     L.offt_hip_half_box_pruned.restype = i
@@ -254,6 +261,32 @@ def offt_hip_convolve_sum_fused(po):
 
 
 CONV_MAX_IN = 8  # offt_hip.h OFFT_HIP_CONV_MAX_IN
+
+
+def offt_hip_execute_forward_filtered(po, data, filt, filter_kind=FILTER_REAL):
+    """in place: this rank's block (input layout) becomes scale * H * fftn(x) in the forward's output layout (rfftn for r2c
+    plans) -- offt_3d_execute and the multiply with H (device memory, laid out like that block) in one call (include/offt_hip.h)"""
+    L = lib()
+    if L.offt_hip_execute_forward_filtered(po, data, filt, filter_kind) != 0:
+        raise RuntimeError("offt_hip_execute_forward_filtered failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_execute_inverse_filtered(po, spec, outs, filts, filter_kind=FILTER_REAL):
+    """outs[k] = scale * N * ifftn(filts[k] * spec) for every k (irfftn for r2c plans), each in the input layout (lists of device
+    pointers of equal length, every output offt_hip_local_bytes bytes).  `spec`, in the forward's output layout, is not
+    written unless it is one of the outputs (at most one; it is made last) (include/offt_hip.h)"""
+    L = lib()
+    if len(outs) != len(filts):
+        raise ValueError("offt_hip_execute_inverse_filtered: %d outputs, %d filters" % (len(outs), len(filts)))
+    n = len(outs)
+    po_, pf_ = (C.c_void_p * max(n, 1))(*outs), (C.c_void_p * max(n, 1))(*filts)
+    if L.offt_hip_execute_inverse_filtered(po, spec, n, po_, pf_, filter_kind) != 0:
+        raise RuntimeError("offt_hip_execute_inverse_filtered failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_spectral_fused(po):
+    """True if both filtered calls run the route whose x pass carries the multiply"""
+    return lib().offt_hip_spectral_fused(po) == 1
 
 
 def offt_hip_set_half_box(po, on=True):

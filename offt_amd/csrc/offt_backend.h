@@ -77,12 +77,20 @@ typedef struct offt_backend {
                        void *dst, void *stream);
   int (*pointwise_sum)(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,
                        int n2, long long s0, long long s1, long long s2, void *stream);
+  /* ---- filtered forward / inverse (offt_hip_execute_forward_filtered, offt_hip_execute_inverse_filtered); appended once more,
+   * so that an older table leaves both NULL and gets the generic route ----
+   * filt_pass_fwd: offt_hipk_filt_pass_fwd -- the forward x pass with the filter on its stores, in place.
+   * filt_pass_inv: offt_hipk_filt_pass_inv -- the inverse x pass with the filter on its loads, src -> dst (dst may be src). */
+  int (*filt_pass_fwd)(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream);
+  int (*filt_pass_inv)(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);
 /* the HIP backend itself with conv_pass_sum withheld (a table for offt_hip_test_set_backend): the generic multi-input route
  * on the device, for timing it against the fused one */
 const offt_backend *offt_hip_test_hip_backend_no_conv_sum(void);
+/* ... and with filt_pass_fwd and filt_pass_inv withheld: the generic route of the two filtered calls on the device */
+const offt_backend *offt_hip_test_hip_backend_no_filt(void);
 
 /* keep the HIP backend but route the exchange through `fn` (called with the comm stream
  * drained; device pointers): several test ranks can then share one GPU */

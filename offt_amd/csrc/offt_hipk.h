@@ -232,6 +232,22 @@ const char *offt_hipk_conv_sum_kernel_name(const offt_pass_desc *fwd, const offt
  * k = 0 ... nin-1: ONE sweep, non-temporal, 16 B per lane along the smallest stride.  `out` may be one of the inputs. */
 int offt_hipk_pointwise_sum(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,
                             int n2, long long s0, long long s1, long long s2, void *stream);
+/* ---- filtered forward and filtered inverse (offt_hip_execute_forward_filtered, offt_hip_execute_inverse_filtered): the two
+ * halves of offt_hipk_conv_pass as launches of their own, for a caller whose state is a spectrum ----
+ * `d` is the x pass of a forward transform: contiguous complex lines (in_contig, in_axis_stride 1, no split, no half lines),
+ * addressed through its in_* side on both launches; `f` addresses the filter like that pass's output, axis stride 1.
+ * Power-of-two lines of 64 ... 1024 points, each with a cache-keeping twin (d->out_keep).
+ * offt_hipk_filt_pass_fwd: data = H . FFT(data) . d->scale along the lines, forward (exp(-i...)), in place.
+ * offt_hipk_filt_pass_inv: dst = d->scale . IFFT(H . src) along the lines, unnormalised inverse (exp(+i...)) whatever
+ * d->direction says, stored at the offsets it loaded from; `src` is not written unless dst == src, which is allowed.
+ * -1 if no such kernel exists or a pointer is NULL. */
+int offt_hipk_filt_pass_fwd(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream);
+int offt_hipk_filt_pass_inv(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream);
+/* 1 if BOTH launches have a kernel for (d, f); the registry lookup needs no device */
+int offt_hipk_filt_has_fused(const offt_pass_desc *d, const offt_filter_desc *f);
+/* "fft_filt_fwd_panel_k" / "fft_filt_inv_panel_k", or "no fused kernel" */
+const char *offt_hipk_filt_fwd_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f);
+const char *offt_hipk_filt_inv_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f);
 /* zero a strided 3-D block n0 x n1 x n2 OUTSIDE the kept sub-box [0,k0) x [0,k1) x [0,k2) (0 <= k <= n); the kept part is
  * not touched.  Elements are complex values of `precision`, or, with OFFT_HIPK_ZERO_REAL or-ed into it, real scalars (the
  * rows of an r2c plan; strides and extents then count scalars).  Vector stores, 16 B per lane along a unit stride s2. */

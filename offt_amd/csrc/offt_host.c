@@ -41,6 +41,9 @@
 /* ------------------------------------------------------------------------- */
 static char g_err[1024] = "";
 const char *offt_hip_last_error(void) { return g_err; }
+/* default of OFFT_HIP_OPT_SPEC_FUSED: 0, because the single-precision filtered forward lost to the generic route on every
+ * measured line (profiles/spec_filtered.txt) */
+#define OFFT_SPEC_FUSED_DEFAULT 0
 #define SET_ERR(...)                                 \
   do {                                               \
     snprintf(g_err, sizeof g_err, __VA_ARGS__);      \
@@ -450,6 +453,8 @@ typedef struct hip_state {
                             mixed-radix kernels too (bit 2 of offt_filter_desc::mixed), 0 = such a length takes the generic route */
     int conv_sum_mixed;  /* multi-input convolve: 1 = together with conv_mixed the gather launch may run on the mixed-radix
                             kernels too (bit 3 of offt_filter_desc::mixed), 0 = such a length takes the generic route */
+    int spec_fused;      /* filtered forward / inverse: 1 = the fused route (the x pass carries the multiply) where the plan has one
+                          * (spec_fused_route), 0 = transform and multiply as separate launches (OFFT_HIP_OPT_SPEC_FUSED) */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -689,6 +694,16 @@ static int hb_pointwise_sum(int nin, const void *const *ins, const void *const *
   if (rc) SET_ERR("pointwise multiply-and-sum failed: %s", offt_hipk_last_error());
   return rc;
 }
+static int hb_filt_pass_fwd(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream) {
+  const int rc = offt_hipk_filt_pass_fwd(d, f, filter, data, stream);
+  if (rc) SET_ERR("filtered forward launch failed: %s", offt_hipk_last_error());
+  return rc;
+}
+static int hb_filt_pass_inv(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream) {
+  const int rc = offt_hipk_filt_pass_inv(d, f, filter, src, dst, stream);
+  if (rc) SET_ERR("filtered inverse launch failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static int hb_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
                             long long s1, long long s2, void *stream) {
   const int rc = offt_hipk_pointwise_oop(in, out, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
@@ -705,7 +720,7 @@ static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
     hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside,
-    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum};
+    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv};
 #ifdef OFFT_TEST_SEAMS
 /* the HIP backend without its fused multi-input launch, for offt_hip_test_set_backend: a plan made under it takes the generic
  * route of offt_hip_execute_convolve_sum on the device (tools/conv_probe.py times that route with it) */
@@ -713,6 +728,15 @@ const offt_backend *offt_hip_test_hip_backend_no_conv_sum(void) {
   static offt_backend b;
   b = k_hip_backend;
   b.conv_pass_sum = NULL;
+  return &b;
+}
+/* ... and without the two filtered launches: the generic route of offt_hip_execute_forward_filtered and
+ * offt_hip_execute_inverse_filtered on the device (tests compare the two routes, tools/conv_probe.py times them) */
+const offt_backend *offt_hip_test_hip_backend_no_filt(void) {
+  static offt_backend b;
+  b = k_hip_backend;
+  b.filt_pass_fwd = NULL;
+  b.filt_pass_inv = NULL;
   return &b;
 }
 #endif
@@ -1175,6 +1199,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.conv_mixed = getenv("OFFT_CONV_MIXED") && atoi(getenv("OFFT_CONV_MIXED")) != 0;
   st->opt.conv_multi_mixed = getenv("OFFT_CONV_MULTI_MIXED") && atoi(getenv("OFFT_CONV_MULTI_MIXED")) != 0;
   st->opt.conv_sum_mixed = getenv("OFFT_CONV_SUM_MIXED") && atoi(getenv("OFFT_CONV_SUM_MIXED")) != 0;
+  st->opt.spec_fused = getenv("OFFT_SPEC_FUSED") ? atoi(getenv("OFFT_SPEC_FUSED")) != 0 : OFFT_SPEC_FUSED_DEFAULT;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
   st->opt.block_pad = getenv("OFFT_BLOCK_PAD") && atoi(getenv("OFFT_BLOCK_PAD")) != 0;
@@ -1656,6 +1681,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
     case OFFT_HIP_OPT_CONV_MIXED: st->opt.conv_mixed = value != 0; break; /* read by every convolve (conv_fused_route) */
     case OFFT_HIP_OPT_CONV_MULTI_MIXED: st->opt.conv_multi_mixed = value != 0; break; /* read by every multi-output convolve (conv_fused_route, CONV_OOP) */
     case OFFT_HIP_OPT_CONV_SUM_MIXED: st->opt.conv_sum_mixed = value != 0; break; /* read by every multi-input convolve (conv_fused_route, CONV_SUM) */
+    case OFFT_HIP_OPT_SPEC_FUSED: st->opt.spec_fused = value != 0; break; /* read by every filtered forward / inverse (spec_fused_route) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
@@ -1696,6 +1722,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_CONV_MIXED: return st->opt.conv_mixed;
     case OFFT_HIP_OPT_CONV_MULTI_MIXED: return st->opt.conv_multi_mixed;
     case OFFT_HIP_OPT_CONV_SUM_MIXED: return st->opt.conv_sum_mixed;
+    case OFFT_HIP_OPT_SPEC_FUSED: return st->opt.spec_fused;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
     case OFFT_HIP_OPT_P2P_TIMEOUT_S: return (long long)st->opt.p2p_timeout_s;
@@ -3262,13 +3289,17 @@ static int execute_convolve_sum_single(struct _offt_plan *po, int nin, void *con
  * to the other's: execute_single builds its launches from the array it is given, and execute_inverse_multi records the
  * forward schedule against that array (inv_data) -- what else a step touches, under the staged and the direct-store exchange
  * alike, is the plan's own send, receive and work volumes (peers map those, never the caller's array). */
+static int conv_forward_scaled(struct _offt_plan *po, void *buf) { /* ... with the plain forward's scale rule (the filtered forward) */
+  hip_state *st = (hip_state *)po->hip_state;
+  if (!st->use_pipeline) return execute_single(po, buf, -1);
+  return st->slab_zyx ? execute_slab(po, buf) : execute_pipeline(po, buf, -1);
+}
+
 static int conv_forward(struct _offt_plan *po, void *buf) {
   hip_state *st = (hip_state *)po->hip_state;
   const double scale = st->out_scale;
-  int rc;
   st->out_scale = 1.0;
-  if (!st->use_pipeline) rc = execute_single(po, buf, -1);
-  else rc = st->slab_zyx ? execute_slab(po, buf) : execute_pipeline(po, buf, -1);
+  const int rc = conv_forward_scaled(po, buf);
   st->out_scale = scale;
   return rc;
 }
@@ -3377,6 +3408,162 @@ int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *i
       rc = be->pointwise_sum(nin, (const void *const *)ins, filters, out, st->prec, filter_kind, c->osize[0], c->osize[1], c->osize[2],
                              c->ostride[0], c->ostride[1], c->ostride[2], st->s_compute) ? -1 : 0;
     if (!rc) rc = conv_inverse(po, out);
+  }
+  return conv_leave(po, t0, rc);
+}
+
+/* ---- filtered forward and filtered inverse: the two halves of a convolve as calls of their own, for a caller whose state
+ * is a spectrum (pseudo-spectral solvers).  Same entry, exit and refusals as the convolve calls above. ----
+ * The fused route: one rank, the z-y-x layout, no half box, both backend entries and a kernel pair for the x extent (powers
+ * of two from 64 to 1024), OFFT_HIP_OPT_SPEC_FUSED set.  *fd receives the x pass's descriptor (lines through its input side,
+ * scale 1) and *fl the filter's addressing (its output side).  0: the generic route. */
+static int spec_fused_route(struct _offt_plan *po, const single_sched *fw, int kind, offt_pass_desc *fd, offt_filter_desc *fl) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_pass_desc *l = &fw->d[2];
+  if (st->use_pipeline || !fw->zyx || st->half_box || !st->opt.spec_fused || !st->be->filt_pass_fwd || !st->be->filt_pass_inv) return 0;
+  *fd = *l;
+  fd->scale = 1.0;
+  fd->out_keep = 0;
+  memset(fl, 0, sizeof *fl);
+  fl->kind = kind;
+  fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
+  fl->b1_stride = l->out_b1_stride; fl->b2_stride = l->out_b2_stride;
+  /* in place on the caller's array: the x pass loads and stores the same lines */
+  if (fw->src[2] != fw->dst[2] || l->out_axis_stride != l->in_axis_stride || l->out_col_stride != l->in_col_stride ||
+      l->out_b1_stride != l->in_b1_stride || l->out_b2_stride != l->in_b2_stride)
+    return 0;
+  return offt_hipk_filt_has_fused(fd, fl);
+}
+
+int offt_hip_spectral_fused(const struct _offt_plan *po) {
+  if (!po || !po->hip_state) return 0;
+  single_sched fw;
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  struct _offt_plan *p = (struct _offt_plan *)po;
+  if (((hip_state *)po->hip_state)->use_pipeline) return 0;
+  single_schedule(p, NULL, -1, &fw);
+  return spec_fused_route(p, &fw, OFFT_FILTER_REAL, &fd, &fl);
+}
+
+/* Plane groups of a fused filtered call, conv_plane_groups' rule (OFFT_HIP_OPT_ZGROUP_MIB, 0 = plain launches; a remainder
+ * group): per group the producer, then the consumer, the producer's stores kept.
+ *   forward (inv = 0): y pass of the forward (fw->d[1]: W -> data), then the filtered x launch in place on `data`;
+ *   inverse (inv = 1): the filtered x launch spec -> out, then the y pass of the inverse (iv->d[1]: out -> W). */
+static int spec_plane_groups(struct _offt_plan *po, const single_sched *ss, int inv, const offt_pass_desc *fd, const offt_filter_desc *fl,
+                             const void *filter, const void *src, void *dst) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  void *s = st->s_compute;
+  const offt_pass_desc *py = &ss->d[1];
+  const size_t esz = st->esz, fesz = fl->kind == OFFT_FILTER_COMPLEX ? esz : esz / 2; /* filter bytes per element */
+  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
+  int ng = 0; /* planes per group; 0: plain launches */
+  /* (the producer the rule asks about: the forward's y pass, or the plain x pass the filtered inverse launch stands in for) */
+  if (py->nb1 == cnt && fd->nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, inv ? &ss->d[0] : py);
+  const int step = ng >= 1 ? ng : cnt;
+  for (int z0 = 0; z0 < cnt; z0 += step) {
+    offt_pass_desc y = *py, x = *fd;
+    if (ng >= 1) {
+      y.nb1 = x.nb1 = cnt - z0 < ng ? cnt - z0 : ng;
+      if (inv) x.out_keep = 1;
+      else y.out_keep = 1;
+    }
+    const size_t off = (size_t)z0 * (size_t)x.in_b1_stride * esz, foff = (size_t)z0 * (size_t)fl->b1_stride * fesz;
+    const char *ysrc = (const char *)ss->src[1] + (size_t)z0 * (size_t)y.in_b1_stride * esz;
+    char *ydst = (char *)ss->dst[1] + (size_t)z0 * (size_t)y.out_b1_stride * esz;
+    if (!inv) {
+      if (be->pass(&y, ysrc, ydst, s)) return -1;
+      if (be->filt_pass_fwd(&x, fl, (const char *)filter + foff, (char *)dst + off, s)) return -1;
+    } else {
+      if (be->filt_pass_inv(&x, fl, (const char *)filter + foff, (const char *)src + off, (char *)dst + off, s)) return -1;
+      if (be->pass(&y, ysrc, ydst, s)) return -1;
+    }
+  }
+  return 0;
+}
+
+/* this rank's output block times H: in place, or src -> dst (pointwise_oop; on a table from before it, a copy and the in-place
+ * multiply) */
+static int spec_multiply(struct _offt_plan *po, const void *src, void *dst, const void *filter, int kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const struct _offt_comm *c = po->comm;
+  if (src == dst) return conv_pointwise(po, dst, filter, kind);
+  if (be->pointwise_oop)
+    return be->pointwise_oop(src, dst, filter, st->prec, kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0], c->ostride[1],
+                             c->ostride[2], st->s_compute) ? -1 : 0;
+  if (be->memcpy_dd(dst, src, local_elems(c) * st->esz, st->s_compute)) return -1;
+  return conv_pointwise(po, dst, filter, kind);
+}
+
+/* data (input layout) -> H . fftn(data) in the forward's output layout, in place */
+int offt_hip_execute_forward_filtered(struct _offt_plan *po, void *data, const void *filter, int filter_kind) {
+  static const char who[] = "offt_hip_execute_forward_filtered";
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  conv_begin(po);
+  if (conv_check_kind(po, who, filter_kind) || conv_need_device(po, who, filter, "the filter", -1, "", 1) ||
+      conv_need_device(po, who, data, "the data", -1, CONV_NO_STAGING, 1) ||
+      conv_ready(po, who, be->pointwise != NULL, "pointwise multiply"))
+    return -1;
+  const double t0 = conv_enter(po);
+  int rc = half_box_clear(po, data);
+  single_sched fw;
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  if (!st->use_pipeline) single_schedule(po, data, -1, &fw);
+  if (!rc && !st->use_pipeline && spec_fused_route(po, &fw, filter_kind, &fd, &fl)) {
+    /* z pass, then per plane group the y pass (kept) and the x pass with the multiply and the output scale on its stores */
+    fd.scale = fw.d[2].scale;
+    rc = be->pass(&fw.d[0], fw.src[0], fw.dst[0], st->s_compute) ? -1 : 0;
+    if (!rc) rc = spec_plane_groups(po, &fw, 0, &fd, &fl, filter, data, data);
+  } else if (!rc) {
+    rc = conv_forward_scaled(po, data);
+    if (!rc) rc = conv_pointwise(po, data, filter, filter_kind);
+  }
+  return conv_leave(po, t0, rc);
+}
+
+/* outs[k] = unnormalised inverse of filters[k] . spec, each in the input layout; spec (the forward's output layout) is not
+ * written unless it is one of outs[], which is then made last */
+int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, int nout, void *const *outs, const void *const *filters,
+                                      int filter_kind) {
+  static const char who[] = "offt_hip_execute_inverse_filtered";
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  conv_begin(po);
+  if (nout < 1 || nout > OFFT_HIP_CONV_MAX_OUT)
+    CONV_REFUSE(po, "%s: nout = %d (1 ... OFFT_HIP_CONV_MAX_OUT = %d outputs)", who, nout, OFFT_HIP_CONV_MAX_OUT);
+  if (conv_check_kind(po, who, filter_kind)) return -1;
+  if (!outs || !filters) CONV_REFUSE(po, "%s: outs and filters must be arrays of nout pointers (got NULL)", who);
+  if (conv_need_device(po, who, spec, "the spectrum", -1, CONV_NO_STAGING, 1) || conv_need_arrays(po, who, nout, filters, outs, "output") ||
+      conv_ready(po, who, be->pointwise != NULL, "pointwise multiply"))
+    return -1;
+  /* the output that is `spec` (at most one: the entries differ) comes last: until then `spec` holds the spectrum */
+  int order[OFFT_HIP_CONV_MAX_OUT], n = 0;
+  for (int k = 0; k < nout; k++) if (outs[k] != spec) order[n++] = k;
+  for (int k = 0; k < nout; k++) if (outs[k] == spec) order[n++] = k;
+  const double t0 = conv_enter(po);
+  int rc = 0;
+  single_sched fw, iv;
+  offt_pass_desc fd;
+  offt_filter_desc fl;
+  if (!st->use_pipeline) single_schedule(po, outs[order[0]], -1, &fw);
+  const int fused = !st->use_pipeline && spec_fused_route(po, &fw, filter_kind, &fd, &fl);
+  for (int i = 0; i < nout && !rc; i++) {
+    void *out = outs[order[i]];
+    const void *filter = filters[order[i]];
+    if (fused) {
+      /* per plane group the x pass with the multiply on its loads (spec -> out, kept) and the inverse's y pass (out -> W); then
+       * the inverse's last pass (W -> out; real output over Nz/2+1 planes on an r2c plan), the output scale on its stores */
+      single_schedule(po, out, +1, &iv);
+      rc = spec_plane_groups(po, &iv, 1, &fd, &fl, filter, spec, out);
+      if (!rc) rc = be->pass(&iv.d[2], iv.src[2], iv.dst[2], st->s_compute) ? -1 : 0;
+    } else {
+      rc = spec_multiply(po, spec, out, filter, filter_kind);
+      if (!rc) rc = conv_inverse(po, out);
+    }
   }
   return conv_leave(po, t0, rc);
 }

@@ -561,6 +561,8 @@ void build_registry() {
   reg_conv_sum_mixed_f32();
   reg_conv_sum_f64();
   reg_conv_sum_f32();
+  reg_spec_f64();
+  reg_spec_f32();
   reg_half_f64();
   reg_half_f32();
   reg_half_real_f64();
@@ -2016,6 +2018,42 @@ int pointwise_launch(const char *who, const void *in, void *out, bool oop, const
   return 0;
 }
 
+// the filtered-forward (inv = false) or filtered-inverse instance for (d, f), or nullptr: pick_conv's conditions on full lines
+// (contiguous complex lines without a split, a unit-stride filter axis), power-of-two lengths only
+Variant *pick_filt(const offt_pass_desc *d, const offt_filter_desc *f, bool keep, bool inv) {
+  if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
+  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
+  if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || d->half || f->axis_stride != 1)
+    return nullptr;
+  return find_variant(VariantKey{d->n, d->precision, true, true, inv ? Role::FiltInv : Role::FiltFwd, keep, 0});
+}
+
+// offt_hipk_filt_pass_fwd (inv = false: (a, f, data, filter, twq)) and offt_hipk_filt_pass_inv ((a, f, src, dst, filter, twq))
+int filt_launch(const char *who, const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, bool inv,
+                void *stream) {
+  if (!filter || !src || !dst) { snprintf(g_err, sizeof g_err, "%s: a NULL array", who); return -1; }
+  Variant *v = pick_filt(d, f, d && d->out_keep, inv);
+  if (!v && d && d->out_keep) v = pick_filt(d, f, false, inv);
+  if (!v) {
+    snprintf(g_err, sizeof g_err, "%s: no filtered %s kernel for this descriptor (n=%d)", who, inv ? "inverse" : "forward", d ? d->n : 0);
+    return -1;
+  }
+  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  PassArgs a = pass_args(d, v->cols, true);
+  ConvArgs fa;
+  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
+  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
+  void *args[6];
+  int na = 0;
+  args[na++] = (void *)&a; args[na++] = (void *)&fa;
+  if (inv) args[na++] = (void *)&src;
+  args[na++] = (void *)&dst; args[na++] = (void *)&filter; args[na++] = (void *)&tb.full;
+  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
+                args, (hipStream_t)stream);
+}
+
 // the multi-input instance for (fwd, f), or nullptr: pick_conv's conditions.  The power-of-two lengths whatever f->mixed
 // says; the mixed-radix instances (fft_conv_sum_panelx_k, no keeping twin) only with bits 1 and 3 of f->mixed both set
 Variant *pick_conv_sum(const offt_pass_desc *d, const offt_filter_desc *f, bool keep) {
@@ -2104,6 +2142,19 @@ int offt_hipk_pointwise(void *data, const void *filter, int precision, int kind,
 int offt_hipk_pointwise_oop(const void *in, void *out, const void *filter, int precision, int kind, int n0, int n1, int n2, long long s0,
                             long long s1, long long s2, void *stream) {
   return pointwise_launch("offt_hipk_pointwise_oop", in, out, true, filter, precision, kind, n0, n1, n2, s0, s1, s2, stream);
+}
+
+// ---- filtered forward and filtered inverse (offt_hipk.h) ----
+int offt_hipk_filt_has_fused(const offt_pass_desc *d, const offt_filter_desc *f) {
+  return pick_filt(d, f, false, false) != nullptr && pick_filt(d, f, false, true) != nullptr;
+}
+const char *offt_hipk_filt_fwd_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f) { return conv_kernel_name(pick_filt(d, f, false, false)); }
+const char *offt_hipk_filt_inv_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f) { return conv_kernel_name(pick_filt(d, f, false, true)); }
+int offt_hipk_filt_pass_fwd(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream) {
+  return filt_launch("offt_hipk_filt_pass_fwd", d, f, filter, data, data, false, stream);
+}
+int offt_hipk_filt_pass_inv(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream) {
+  return filt_launch("offt_hipk_filt_pass_inv", d, f, filter, src, dst, true, stream);
 }
 
 // ---- multi-input convolution (offt_hipk.h) ----

@@ -930,6 +930,236 @@ fft_conv_oop_half_panel_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *
 }
 
 // ---------------------------------------------------------------------------
+// Filtered forward and filtered inverse of whole lines (offt_hipk_filt_pass_fwd, offt_hipk_filt_pass_inv): the two halves of
+// conv_body as kernels of their own, for a caller whose state lives in spectral space.  Contiguous lines, no split, one
+// column per lane, conv_body's thread mapping (column c = tid / TPL, line offset j = tid % TPL in every stage).
+//   INV = false (fft_filt_fwd_panel_k): load, forward stages, H[n] times the register that holds output index n, scale,
+//     store where the line came from -- the x pass of a forward transform with the multiply on its stores.  In place.
+//   INV = true (fft_filt_inv_panel_k): load from `src`, H[n] loaded with the element's own index and multiplied in the load
+//     distribution, conjugate, the stages, conjugate, scale, store to `dst` at the same offsets -- the x pass of an inverse
+//     transform with the multiply on its loads.  `src` is not written unless dst == src (a workgroup owns whole lines and has
+//     loaded all of them before its first exchange, i.e. before any of its stores).
+// No round trip through the exchange image: each half multiplies in the distribution it already has.  Filter values are
+// read once: non-temporal.
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP, bool INV>
+__device__ __forceinline__ void filt_body(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst,
+                                          const void *filter, const typename vec2<T>::type *twq) {
+  using V2 = typename vec2<T>::type;
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int TPL = Cfg::TPL, NT = Cfg::NT, NSTAGE = Cfg::NSTAGE;
+  constexpr int LSTRIDE = Cfg::LSTRIDE;
+  constexpr bool SWZ = Cfg::SWZ;
+  constexpr int PS = SWZ ? Cfg::SWZSHIFT : Cfg::PADSHIFT;
+  static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
+  static_assert(E % R0 == 0 && E % R1 == 0 && E % R2 == 0 && N % E == 0, "bad E");
+  static_assert(NSTAGE > 1, "the twiddle tables are staged for the exchanges");
+  constexpr int RL = NSTAGE == 3 ? R2 : R1;  // radix of the last stage
+  constexpr int LRL = ilog2(RL);
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T *exs = reinterpret_cast<T *>(smem);
+  V2 *exv = reinterpret_cast<V2 *>(smem);
+  V2 *tw = reinterpret_cast<V2 *>(smem + Cfg::TW_OFF);
+  V2 *tw1 = reinterpret_cast<V2 *>(smem + Cfg::T1_OFF);
+
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Cfg::QT; i += NT) tw[i] = twq[i];
+  if constexpr (Cfg::USE_T1) {
+    constexpr int M1 = N / (R0 * R1);
+    for (int i = tid; i < Cfg::T1N; i += NT) {
+      const int t = i / R0 + 1, k = i - (t - 1) * R0;
+      tw1[i] = twq[k * M1 * t];
+    }
+  }
+
+  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const int cp = bid % (unsigned)a.ncp;
+  const unsigned rest = bid / (unsigned)a.ncp;
+  const int b1 = rest % (unsigned)a.nb1;
+  const int b2 = rest / (unsigned)a.nb1;
+  const int c0 = cp * COLS;
+  const int j = tid % TPL, c = tid / TPL;
+  const bool valid = (c0 + c) < a.ncols;
+  const long long lo = (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col + (long long)j * a.in_axis;
+  const V2 *line = src + lo;
+  V2 *sline = dst + lo;
+  const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col + (long long)j * f.axis;
+
+  // a wave owns whole columns when TPL divides 64: its exchanges need no workgroup barrier (see panel_body)
+  constexpr bool WAVE_COLS = (64 % TPL == 0) && (NT % 64 == 0);
+  auto xsync = [&]() {
+    if constexpr (WAVE_COLS) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    } else {
+      __syncthreads();
+    }
+  };
+  auto at = [&](int i) { return c * LSTRIDE + padidx<SWZ, PS>(i); };
+
+  // register r holds line index j + cn: times H at that index (a lane past the last column multiplies by zero and stores nothing)
+  auto times_h = [&](cx<T> x, int cn, auto complex_filter) {
+    const long long off = fb + (long long)cn * f.axis;
+    if constexpr (decltype(complex_filter)::value) {
+      V2 h;
+      h.x = 0; h.y = 0;
+      if (valid) h = gload(reinterpret_cast<const V2 *>(filter) + off);
+      return cx<T>{x.x * h.x - x.y * h.y, x.x * h.y + x.y * h.x};
+    } else {
+      T h = 0;
+      if (valid) h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + off);
+      return cx<T>{x.x * h, x.y * h};
+    }
+  };
+
+  cx<T> v[E];
+  static_for<0, E>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+    constexpr int cn = u * TPL + t * (N / R0);
+    V2 val;
+    val.x = 0; val.y = 0;
+    if (valid) val = gload(line + (long long)cn * a.in_axis);
+    v[decltype(ii)::value] = cx<T>{val.x, val.y};
+  });
+  if constexpr (INV) {
+    // H in the load distribution, then conjugated (the inverse as conj(F(conj(.))))
+    auto filt = [&](auto complex_filter) {
+      static_for<0, E>([&](auto ii) {
+        constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+        constexpr int cn = u * TPL + t * (N / R0);
+        const cx<T> x = times_h(v[decltype(ii)::value], cn, complex_filter);
+        v[decltype(ii)::value] = cx<T>{x.x, -x.y};
+      });
+    };
+    if (f.cplx) filt(std::true_type{});
+    else filt(std::false_type{});
+  }
+
+  // the forward stages of panel_body (contiguous / contiguous), ending in the last stage's register order:
+  // v[u RL + bitrev(t)] holds line index j + u TPL + t N/RL
+  static_for<0, NSTAGE>([&](auto sidx) {
+    constexpr int s = decltype(sidx)::value;
+    constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
+    constexpr int Ns = (s == 0) ? 1 : ((s == 1) ? R0 : R0 * R1);
+    constexpr int NB = E / R;
+    constexpr int LR = ilog2(R);
+    if constexpr (s > 0) {
+      constexpr int M = N / (Ns * R);
+      if constexpr (s == 1 && WAVE_COLS) __syncthreads();  // the twiddle tables staged at entry are visible
+      static_for<0, NB>([&](auto uu) {
+        constexpr int u = decltype(uu)::value;
+        const int q = j + u * TPL;
+        const int km = (q & (Ns - 1)) * M;
+        static_for<1, R>([&](auto tt) {
+          constexpr int t = decltype(tt)::value;
+          T cr, ci;
+          if constexpr (s == 1 && Cfg::USE_T1) {
+            const V2 w = tw1[(t - 1) * R0 + (q & (R0 - 1))];
+            cr = w.x; ci = w.y;
+          } else if constexpr (Cfg::USE_HALF) {
+            const int e = km * t;
+            const V2 w = tw[e & (N / 2 - 1)];
+            const unsigned sm = ((unsigned)e << (32 - ilog2(N))) & 0x80000000u;
+            cr = xor_sign(w.x, sm); ci = xor_sign(w.y, sm);
+          } else {
+            const int e = km * t;
+            const int qd = e / (N / 4);
+            const V2 w = tw[e & (N / 4 - 1)];
+            cr = (qd & 1) ? w.y : w.x;
+            ci = (qd & 1) ? -w.x : w.y;
+            if (qd & 2) { cr = -cr; ci = -ci; }
+          }
+          const cx<T> x = v[u * R + t];
+          v[u * R + t] = cx<T>{x.x * cr - x.y * ci, x.x * ci + x.y * cr};
+        });
+      });
+    }
+    static_for<0, NB>([&](auto uu) { dft_reg<T, R>(&v[decltype(uu)::value * R]); });
+    if constexpr (s < NSTAGE - 1) {
+      constexpr int Rn = (s == 0) ? R1 : R2;
+      auto wr_idx = [&](int u, int t) {
+        const int q = j + u * TPL;
+        const int k = q & (Ns - 1);
+        return at((q - k) * R + k + t * Ns);
+      };
+      auto rd_idx = [&](int u, int t) { return at(j + u * TPL + t * (N / Rn)); };
+      if constexpr (s > 0) xsync();  // previous exchange's reads done
+      if constexpr (SPLIT) {
+        static_for<0, E>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+          exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].x;
+        });
+        xsync();
+        T re[E];
+        static_for<0, E>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+          re[decltype(ii)::value] = exs[rd_idx(u, t)];
+        });
+        xsync();
+        static_for<0, E>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+          exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].y;
+        });
+        xsync();
+        static_for<0, E>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+          v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], exs[rd_idx(u, t)]};
+        });
+      } else {
+        static_for<0, E>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+          const cx<T> x = v[u * R + bitrev(t, LR)];
+          V2 w; w.x = x.x; w.y = x.y;
+          exv[wr_idx(u, t)] = w;
+        });
+        xsync();
+        static_for<0, E>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+          const V2 w = exv[rd_idx(u, t)];
+          v[decltype(ii)::value] = cx<T>{w.x, w.y};
+        });
+      }
+    }
+  });
+
+  // the last stage's order: forward times H[n] at the output index; inverse conjugated back; scale; store
+  const T sc = (T)a.scale;
+  auto store_all = [&](auto complex_filter) {
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int cn = u * TPL + t * (N / RL);
+      cx<T> x = v[u * RL + bitrev(t, LRL)];
+      V2 w;
+      if constexpr (INV) {
+        w.x = x.x * sc;
+        w.y = -x.y * sc;
+      } else {
+        x = times_h(x, cn, complex_filter);
+        w.x = x.x * sc;
+        w.y = x.y * sc;
+      }
+      if (valid) gstore_p<KEEP>(sline + (long long)cn * a.in_axis, w);
+    });
+  };
+  if (!INV && f.cplx) store_all(std::true_type{});
+  else store_all(std::false_type{});
+}
+
+// (one transform plus the filter values: the plain pass's waves per SIMD, no instance spills -- the VGPR table is in DESIGN.md 4.5)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_filt_fwd_panel_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twq) {
+  filt_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP, false>(a, f, data, data, filter, twq);
+}
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool KEEP = false>
+__global__ void __launch_bounds__((N / E) * COLS, (PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>::WPS_E))
+fft_filt_inv_panel_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst, const void *filter,
+                     const typename vec2<T>::type *twq) {
+  filt_body<T, N, E, R0, R1, R2, COLS, SPLIT, KEEP, true>(a, f, src, dst, filter, twq);
+}
+
+// ---------------------------------------------------------------------------
 // Multi-input spectral convolution (offt_hipk_conv_pass_sum): out = ifft( sum_k H_k . fft(x_k) ) on whole lines.  The
 // transpose of the out-of-place kernels above: several sources, one destination.  By linearity the K inverse transforms are
 // one, and the sum lives in registers between the forward stages and the inverse stages -- conv_body with its first half
@@ -2181,6 +2411,8 @@ enum class Role {
   ConvOop,  // ... with a separate store base (offt_hipk_conv_pass_oop): fft_conv_oop_panel_k, fft_conv_oop_half_panel_k, ...
   ConvSum,  // several sources summed into one destination (offt_hipk_conv_pass_sum): fft_conv_sum_panel_k, fft_conv_sum_half_panel_k
             // and their panelx twins
+  FiltFwd,  // forward x pass with the filter on its stores, in place (offt_hipk_filt_pass_fwd): fft_filt_fwd_panel_k
+  FiltInv,  // inverse x pass with the filter on its loads, src -> dst (offt_hipk_filt_pass_inv): fft_filt_inv_panel_k
 };
 // column-pair instances (T = f32x2) are kept under their own precision so that the one-column variants and their ids stay
 // what they were
@@ -2394,6 +2626,21 @@ void reg_variant_conv_sum() {
   add(true, 3, (const void *)fft_conv_sum_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
 }
 
+// filtered forward and filtered inverse (fft_filt_fwd_panel_k, fft_filt_inv_panel_k; offt_reg_spec_*.hip): the shapes of
+// reg_variant_conv, each plain and with cache-keeping stores
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variant_filt() {
+  const VariantShape s = panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>();
+  auto add = [&](Role role, bool keep, const void *fn) {
+    add_variant(VariantKey{N, prec_of<T>(), true, true, role, keep, 0}, s, fn, role == Role::FiltFwd ? "fft_filt_fwd_panel_k" : "fft_filt_inv_panel_k",
+                role == Role::FiltFwd ? " filtered forward" : " filtered inverse");
+  };
+  add(Role::FiltFwd, false, (const void *)fft_filt_fwd_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
+  add(Role::FiltFwd, true, (const void *)fft_filt_fwd_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
+  add(Role::FiltInv, false, (const void *)fft_filt_inv_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, false>);
+  add(Role::FiltInv, true, (const void *)fft_filt_inv_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
+}
+
 // mixed-radix (2^a 3^b 5^c) panel kernel: TPL threads per line instead of elements per thread.
 // FLAV limits which (in_contig, out_contig) flavours are instantiated at all (compile time), defmask says for
 // which of them this variant is the default.
@@ -2519,6 +2766,8 @@ void reg_conv_sum_f64();
 void reg_conv_sum_f32();
 void reg_conv_sum_mixed_f64();
 void reg_conv_sum_mixed_f32();
+void reg_spec_f64();
+void reg_spec_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();

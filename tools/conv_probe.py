@@ -36,7 +36,14 @@ offt_hip_execute_convolve calls plus two in-place torch adds, on the same plan a
 warm-up.  The line reports min and median of all three, the ratios against both baselines, each baseline's own spread
 (median / min - 1) and the byte model of DESIGN.md 4.5 (344 / 472 and 344 / 600 for K = 3).  sum:mixed:half:N does so on a
 pruned half-box plan (OFFT_HIP_OPT_HALF_MIXED, an N/2 box).
-usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+A spec with the prefix spec: measures offt_hip_execute_forward_filtered and offt_hip_execute_inverse_filtered (one output, a
+buffer of its own; real filters), a line each, on the same plan and buffers: the fused route, the call's own generic route (a
+second plan made under the HIP backend with filt_pass_fwd / filt_pass_inv withheld, a seam of tests/liboffthip_test.so) and
+the caller's route built from calls that predate the two (offt_3d_execute + offt_hipk_pointwise; offt_hipk_pointwise_oop +
+offt_3d_execute_dir(+1)).  The three ALTERNATE after a warm-up, MIXED_REPS times each, and a line reports min and median of
+all three, the ratios against both, each baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5
+(104 / 136).
+usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
        (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768;
         the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512;
         the multi:mixed: set of profiles/conv_multi_mixed.txt: multi:mixed:768 multi:mixed:f32:768 multi:mixed:1000
@@ -44,7 +51,8 @@ usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:][half:][f64|f32
         the sum: set of profiles/conv_sum.txt: sum:512 sum:1024 sum:f32:1024 sum:r2c:512 sum:half:512, and for the shorter
         x lengths sum:64 sum:128 sum:256 sum:f32:256 sum:f32:512;
         the sum:mixed: set of profiles/conv_sum_mixed.txt: sum:mixed:768 sum:mixed:f32:768 sum:mixed:1000 sum:mixed:f32:1000
-        sum:mixed:half:768)"""
+        sum:mixed:half:768;
+        the spec: set of profiles/spec_filtered.txt: spec:512 spec:f32:512 spec:1024 spec:f32:1024 spec:r2c:512 spec:r2c:f32:512)"""
 import ctypes as C
 import os
 import sys
@@ -55,8 +63,8 @@ import torch  # noqa: E402
 
 from offt_amd import api  # noqa: E402
 
-if any(a.startswith("sum:") and not a.startswith("sum:mixed:") for a in sys.argv[1:]):
-    # the sum: specs time the generic route as well, which needs the build with the test seams (the same kernel objects)
+if any((a.startswith("sum:") and not a.startswith("sum:mixed:")) or a.startswith("spec:") for a in sys.argv[1:]):
+    # the sum: and spec: specs time the generic route as well, which needs the build with the test seams (the same kernel objects)
     api.use_library(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "liboffthip_test.so"))
 L = api.lib()
 REPS = int(os.environ.get("CONV_PROBE_REPS", "5"))
@@ -155,6 +163,98 @@ def probe_sum(rest, zg):
     torch.cuda.empty_cache()
 
 
+def probe_spec(rest, zg):
+    """spec:[r2c:][f64|f32:]N -- the filtered forward and the filtered inverse (one output), three routes each"""
+    r2c = rest.startswith("r2c:")
+    kind, _, n_s = rest[(4 if r2c else 0):].rpartition(":")
+    n = int(n_s)
+    prec = api.F32 if kind == "f32" else api.F64
+    T = api.lib()
+    T.offt_hip_test_hip_backend_no_filt.restype = C.c_void_p
+    T.offt_hip_test_set_backend.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    V, I, LL = C.c_void_p, C.c_int, C.c_longlong
+    T.offt_hipk_pointwise.argtypes = [V, V, I, I, I, I, I, LL, LL, LL, V]
+    T.offt_hipk_pointwise_oop.argtypes = [V, V, V, I, I, I, I, I, LL, LL, LL, V]
+    plans = {}
+    for name in ("generic", "fused"):  # the plan made under the table without the two entries first, then the product's own
+        T.offt_hip_test_set_backend(T.offt_hip_test_hip_backend_no_filt() if name == "generic" else None, 0, 1)
+        po = plans[name] = api.offt_3d_init(n, n, n, precision=prec, is_r2c=int(r2c))
+        if zg is not None:
+            T.offt_hip_set_option(po, OPT_ZGROUP_MIB, zg)
+    po = plans["fused"]
+    T.offt_hip_set_option(po, api.OPT_SPEC_FUSED, 1)
+    stream = torch.cuda.Stream()  # one stream for both plans, the caller's multiply and the timing events
+    for p in plans.values():
+        T.offt_hip_set_stream(p, stream.cuda_stream)
+    td = torch.float32 if prec == api.F32 else torch.float64
+    ne = api.local_elems(po)
+    c = api.comm_dict(po)
+    osz, ost = c["osize"], c["ostride"]
+    x = torch.zeros(ne * 2, dtype=td, device="cuda")
+    T.offt_hip_fill_input(po, x.data_ptr(), 1)
+    spec = x.clone()
+    api.offt_3d_execute(po, spec.data_ptr(), spec.data_ptr())
+    out = torch.zeros_like(x)
+    H = torch.rand(ne, dtype=td, device="cuda") * float(n) ** -1.5  # keeps a field that is transformed again and again bounded
+    px, ps, pout, ph = x.data_ptr(), spec.data_ptr(), out.data_ptr(), H.data_ptr()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def run(fn):
+        ev[0].record(stream)
+        fn()
+        ev[1].record(stream)
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) * 1e-3
+
+    def point(src, dst):
+        sp = stream.cuda_stream
+        if src == dst:
+            rc = T.offt_hipk_pointwise(dst, ph, prec, api.FILTER_REAL, osz[0], osz[1], osz[2], ost[0], ost[1], ost[2], sp)
+        else:
+            rc = T.offt_hipk_pointwise_oop(src, dst, ph, prec, api.FILTER_REAL, osz[0], osz[1], osz[2], ost[0], ost[1], ost[2], sp)
+        assert rc == 0
+
+    def caller_fwd():
+        api.offt_3d_execute(po, px, px)
+        point(px, px)
+
+    def caller_inv():
+        point(ps, pout)
+        api.offt_3d_execute_dir(po, pout, pout, +1)
+
+    routes = {
+        "fwd": (("fused", lambda: api.offt_hip_execute_forward_filtered(po, px, ph, api.FILTER_REAL)),
+                ("generic", lambda: api.offt_hip_execute_forward_filtered(plans["generic"], px, ph, api.FILTER_REAL)),
+                ("caller", caller_fwd)),
+        "inv": (("fused", lambda: api.offt_hip_execute_inverse_filtered(po, ps, [pout], [ph], api.FILTER_REAL)),
+                ("generic", lambda: api.offt_hip_execute_inverse_filtered(plans["generic"], ps, [pout], [ph], api.FILTER_REAL)),
+                ("caller", caller_inv)),
+    }
+    fusedp, fusedg = api.offt_hip_spectral_fused(po), api.offt_hip_spectral_fused(plans["generic"])
+    tag = f"{'r2c ' if r2c else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3"
+    for which, rs in routes.items():
+        t = {k: [] for k, _ in rs}
+        for rep_i in range(2 + MIXED_REPS):
+            for name, fn in rs:
+                dt = run(fn)
+                if rep_i >= 2:
+                    t[name].append(dt)
+        mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+        print(f"spec: {which} {tag}: call [{'fused' if fusedp else 'generic'}] min {mn['fused'] * 1e3:.3f} ms median {md['fused'] * 1e3:.3f} ms  "
+              f"call without filt_pass [{'fused' if fusedg else 'generic'}] min {mn['generic'] * 1e3:.3f} ms median {md['generic'] * 1e3:.3f} ms  "
+              f"caller's route min {mn['caller'] * 1e3:.3f} ms median {md['caller'] * 1e3:.3f} ms  "
+              f"fused/generic min {mn['fused'] / mn['generic']:.3f} median {md['fused'] / md['generic']:.3f}  "
+              f"fused/caller min {mn['fused'] / mn['caller']:.3f} median {md['fused'] / md['caller']:.3f}  "
+              f"generic spread {md['generic'] / mn['generic'] - 1:.3f}  caller spread {md['caller'] / mn['caller'] - 1:.3f}  "
+              f"byte model (complex f64, real filter) {104 / 136:.3f}  n {MIXED_REPS}  zgroup_mib {T.offt_hip_get_option(po, OPT_ZGROUP_MIB)}",
+              flush=True)
+    for p in plans.values():
+        api.offt_3d_fin(p)
+    del x, spec, out, H
+    torch.cuda.empty_cache()
+
+
 def probe_sum_mixed(rest, zg):
     """sum:mixed:[half:][f64|f32|r2c:]N -- OFFT_HIP_OPT_CONV_SUM_MIXED at 1 and at 0 and the caller's route, on one plan"""
     K = 3
@@ -236,6 +336,9 @@ def main():
     specs = args or ["1024", "f32:1024", "r2c:512", "mixed:768", "mixed:f32:768", "mixed:1000", "mixed:f32:1000", "mixed:half:768"]
     torch.cuda.set_device(0)
     for spec in specs:
+        if spec.startswith("spec:"):
+            probe_spec(spec[5:], zg)
+            continue
         if spec.startswith("sum:mixed:"):
             probe_sum_mixed(spec[10:], zg)
             continue
