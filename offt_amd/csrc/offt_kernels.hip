@@ -1933,15 +1933,19 @@ int offt_hipk_flag_wait(int n, unsigned long long *const *addr, unsigned long lo
 
 // ---- spectral convolution (offt_hipk.h) ----
 namespace {
-// the fused instance for (fwd, f), or nullptr: contiguous complex lines without a split, a unit-stride filter axis.  The
-// mixed-radix instances (fft_conv_panelx_k; lengths that have no power-of-two instance) only with bit 1 of f->mixed.
+// what every fused whole-line kernel asks of (d, f): contiguous complex lines without a split, a unit-stride filter axis
+bool whole_lines(const offt_pass_desc *d, const offt_filter_desc *f) {
+  if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return false;
+  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return false;
+  return d->in_contig && d->in_axis_stride == 1 && !d->in_split && !d->in_split_nfloor && !d->real_input && !d->tw4 && f->axis_stride == 1;
+}
+
+// the fused instance for (fwd, f), or nullptr.  The mixed-radix instances (fft_conv_panelx_k; lengths that have no
+// power-of-two instance) only with bit 1 of f->mixed.
 // oop: the out-of-place instances (fft_conv_oop_panel_k): the power-of-two lengths, each with a cache-keeping twin, half
 // lines included, and the mixed-radix ones (fft_conv_oop_panelx_k, no keeping twin) only with bits 1 and 2 of f->mixed.
 Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep, bool oop = false) {
-  if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
-  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
-  if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || f->axis_stride != 1)
-    return nullptr;
+  if (!whole_lines(d, f)) return nullptr;
   if (d->half && d->half != 3) return nullptr;  // half lines: loads and stores together, or not at all
   if (d->half && keep && !oop) return nullptr;  // (no cache-keeping twin of the in-place half-line kernels)
   Variant *v = find_variant(VariantKey{d->n, d->precision, true, true, oop ? Role::ConvOop : Role::Conv, keep, d->half});
@@ -1949,6 +1953,25 @@ Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep
   return v;
 }
 const char *conv_kernel_name(const Variant *v) { return v ? v->kernel : "no fused kernel"; }
+
+// the launch of a fused whole-line instance v picked for (d, f): every such kernel takes (a, f, <mid>, twq), `mid` being
+// the nmid arguments that are its own
+int line_launch(const char *who, Variant *v, const offt_pass_desc *d, const offt_filter_desc *f, void *const *mid, int nmid, void *stream) {
+  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  PassArgs a = pass_args(d, v->cols, true);
+  ConvArgs fa;
+  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
+  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
+  void *args[6];
+  int na = 0;
+  args[na++] = (void *)&a; args[na++] = (void *)&fa;
+  for (int i = 0; i < nmid; i++) args[na++] = mid[i];
+  args[na++] = (void *)&tb.full;
+  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
+                args, (hipStream_t)stream);
+}
 
 // offt_hipk_conv_pass (src == dst, oop = false) and offt_hipk_conv_pass_oop: the out-of-place kernels take (a, f, src, dst,
 // filter, twt), the in-place ones (a, f, data, filter, twt)
@@ -1960,21 +1983,28 @@ int conv_launch(const char *who, const offt_pass_desc *d, const offt_filter_desc
     snprintf(g_err, sizeof g_err, "%s: no %sfused convolution kernel for this descriptor (n=%d)", who, oop ? "out-of-place " : "", d ? d->n : 0);
     return -1;
   }
-  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
-  Tables tb;
-  if (get_tables(d->n, d->precision, tb, false)) return -1;
-  PassArgs a = pass_args(d, v->cols, true);
-  ConvArgs fa;
-  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
-  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
-  void *args[6];
-  int na = 0;
-  args[na++] = (void *)&a; args[na++] = (void *)&fa;
-  if (oop) args[na++] = (void *)&src;
-  args[na++] = (void *)&dst; args[na++] = (void *)&filter; args[na++] = (void *)&tb.full;
-  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
-                args, (hipStream_t)stream);
+  void *mid[3];
+  int nmid = 0;
+  if (oop) mid[nmid++] = (void *)&src;
+  mid[nmid++] = (void *)&dst; mid[nmid++] = (void *)&filter;
+  return line_launch(who, v, d, f, mid, nmid, stream);
 }
+
+// rows along the smallest stride, and the grid of the pointwise kernels over them
+struct PointRows {
+  int n[3];
+  long long st[3];
+  long long rows;
+  PointRows(int n0, int n1, int n2, long long s0, long long s1, long long s2) : n{n0, n1, n2}, st{s0, s1, s2} {
+    for (int a = 0; a < 2; a++)
+      for (int b = 0; b < 2 - a; b++)
+        if (st[b] < st[b + 1]) { int tn = n[b]; n[b] = n[b + 1]; n[b + 1] = tn; long long ts = st[b]; st[b] = st[b + 1]; st[b + 1] = ts; }
+    rows = (long long)n[0] * n[1];
+  }
+  // two single-precision elements per lane: unit stride, whole pairs, 16-B aligned rows (and bases: the caller's test)
+  bool pair_rows(int precision) const { return precision == OFFT_PREC_F32 && st[2] == 1 && !(n[2] & 1) && !(st[1] & 1) && !(st[0] & 1); }
+  dim3 grid(bool pair) const { return dim3((unsigned)((n[2] / (pair ? 2 : 1) + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535)); }
+};
 
 // offt_hipk_pointwise (in == out, oop = false) and offt_hipk_pointwise_oop: rows along the smallest stride, the pair test, the grid
 int pointwise_launch(const char *who, const void *in, void *out, bool oop, const void *filter, int precision, int kind, int n0, int n1, int n2,
@@ -1982,20 +2012,9 @@ int pointwise_launch(const char *who, const void *in, void *out, bool oop, const
   if (kind != OFFT_FILTER_REAL && kind != OFFT_FILTER_COMPLEX) { snprintf(g_err, sizeof g_err, "%s: bad filter kind %d", who, kind); return -1; }
   if (oop && (!in || !out || in == out)) { snprintf(g_err, sizeof g_err, "%s: needs two different arrays (in place: offt_hipk_pointwise)", who); return -1; }
   if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
-  // rows along the smallest stride
-  int n[3] = {n0, n1, n2};
-  long long st[3] = {s0, s1, s2};
-  for (int a = 0; a < 2; a++)
-    for (int b = 0; b < 2 - a; b++)
-      if (st[b] < st[b + 1]) { int tn = n[b]; n[b] = n[b + 1]; n[b + 1] = tn; long long ts = st[b]; st[b] = st[b + 1]; st[b + 1] = ts; }
-  const long long rows = (long long)n[0] * n[1];
-  const bool f32 = precision == OFFT_PREC_F32;
-  // two single-precision elements per lane: unit stride, whole pairs, 16-B aligned rows and bases
-  const bool pair = f32 && st[2] == 1 && !(n[2] & 1) && !(st[1] & 1) && !(st[0] & 1) && !((uintptr_t)in & 15) && !((uintptr_t)out & 15) &&
+  const PointRows r(n0, n1, n2, s0, s1, s2);
+  const bool pair = r.pair_rows(precision) && !((uintptr_t)in & 15) && !((uintptr_t)out & 15) &&
                     !((uintptr_t)filter & (kind == OFFT_FILTER_COMPLEX ? 15 : 7));
-  const int epl = pair ? 2 : 1;
-  const unsigned gx = (unsigned)((n[2] / epl + 255) / 256);
-  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
   hipStream_t sm = (hipStream_t)stream;
   (void)hipGetLastError();
   const bool cx = kind == OFFT_FILTER_COMPLEX;
@@ -2006,9 +2025,9 @@ int pointwise_launch(const char *who, const void *in, void *out, bool oop, const
     else FOR_PREC(precision, LAUNCH(T, false, 1));                                   \
   } while (0)
 #define IN_PLACE(T, CPLX, EPL) \
-  hipLaunchKernelGGL((pointwise_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, (typename vec2<T>::type *)out, filter, n[1], n[2], st[0], st[1], st[2], rows)
+  hipLaunchKernelGGL((pointwise_k<T, CPLX, EPL>), r.grid(pair), dim3(256), 0, sm, (typename vec2<T>::type *)out, filter, r.n[1], r.n[2], r.st[0], r.st[1], r.st[2], r.rows)
 #define OUT_OF_PLACE(T, CPLX, EPL) \
-  hipLaunchKernelGGL((pointwise_oop_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, (const typename vec2<T>::type *)in, (typename vec2<T>::type *)out, filter, n[1], n[2], st[0], st[1], st[2], rows)
+  hipLaunchKernelGGL((pointwise_oop_k<T, CPLX, EPL>), r.grid(pair), dim3(256), 0, sm, (const typename vec2<T>::type *)in, (typename vec2<T>::type *)out, filter, r.n[1], r.n[2], r.st[0], r.st[1], r.st[2], r.rows)
   if (!oop) DISPATCH(IN_PLACE);
   else DISPATCH(OUT_OF_PLACE);
 #undef OUT_OF_PLACE
@@ -2018,13 +2037,9 @@ int pointwise_launch(const char *who, const void *in, void *out, bool oop, const
   return 0;
 }
 
-// the filtered-forward (inv = false) or filtered-inverse instance for (d, f), or nullptr: pick_conv's conditions on full lines
-// (contiguous complex lines without a split, a unit-stride filter axis), power-of-two lengths only
+// the filtered-forward (inv = false) or filtered-inverse instance for (d, f), or nullptr: full lines, power-of-two lengths only
 Variant *pick_filt(const offt_pass_desc *d, const offt_filter_desc *f, bool keep, bool inv) {
-  if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
-  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
-  if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || d->half || f->axis_stride != 1)
-    return nullptr;
+  if (!whole_lines(d, f) || d->half) return nullptr;
   return find_variant(VariantKey{d->n, d->precision, true, true, inv ? Role::FiltInv : Role::FiltFwd, keep, 0});
 }
 
@@ -2038,29 +2053,17 @@ int filt_launch(const char *who, const offt_pass_desc *d, const offt_filter_desc
     snprintf(g_err, sizeof g_err, "%s: no filtered %s kernel for this descriptor (n=%d)", who, inv ? "inverse" : "forward", d ? d->n : 0);
     return -1;
   }
-  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
-  Tables tb;
-  if (get_tables(d->n, d->precision, tb, false)) return -1;
-  PassArgs a = pass_args(d, v->cols, true);
-  ConvArgs fa;
-  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
-  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
-  void *args[6];
-  int na = 0;
-  args[na++] = (void *)&a; args[na++] = (void *)&fa;
-  if (inv) args[na++] = (void *)&src;
-  args[na++] = (void *)&dst; args[na++] = (void *)&filter; args[na++] = (void *)&tb.full;
-  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
-                args, (hipStream_t)stream);
+  void *mid[3];
+  int nmid = 0;
+  if (inv) mid[nmid++] = (void *)&src;
+  mid[nmid++] = (void *)&dst; mid[nmid++] = (void *)&filter;
+  return line_launch(who, v, d, f, mid, nmid, stream);
 }
 
-// the multi-input instance for (fwd, f), or nullptr: pick_conv's conditions.  The power-of-two lengths whatever f->mixed
-// says; the mixed-radix instances (fft_conv_sum_panelx_k, no keeping twin) only with bits 1 and 3 of f->mixed both set
+// the multi-input instance for (fwd, f), or nullptr.  The power-of-two lengths whatever f->mixed says; the mixed-radix
+// instances (fft_conv_sum_panelx_k, no keeping twin) only with bits 1 and 3 of f->mixed both set
 Variant *pick_conv_sum(const offt_pass_desc *d, const offt_filter_desc *f, bool keep) {
-  if (!d || !f || (f->kind != OFFT_FILTER_REAL && f->kind != OFFT_FILTER_COMPLEX)) return nullptr;
-  if (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32) return nullptr;
-  if (!d->in_contig || d->in_axis_stride != 1 || d->in_split || d->in_split_nfloor || d->real_input || d->tw4 || f->axis_stride != 1)
-    return nullptr;
+  if (!whole_lines(d, f)) return nullptr;
   if (d->half && d->half != 3) return nullptr;
   Variant *v = find_variant(VariantKey{d->n, d->precision, true, true, Role::ConvSum, keep, d->half});
   if (v && v->mixed && (f->mixed & 5) != 5) return nullptr;
@@ -2087,26 +2090,15 @@ int pointwise_sum_launch(const char *who, int nin, const void *const *ins, const
   if (!fill_sum_args(who, sa, nin, ins, filters)) return -1;
   if (!out) { snprintf(g_err, sizeof g_err, "%s: out is NULL", who); return -1; }
   if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
-  // rows along the smallest stride
-  int n[3] = {n0, n1, n2};
-  long long st[3] = {s0, s1, s2};
-  for (int a = 0; a < 2; a++)
-    for (int b = 0; b < 2 - a; b++)
-      if (st[b] < st[b + 1]) { int tn = n[b]; n[b] = n[b + 1]; n[b + 1] = tn; long long ts = st[b]; st[b] = st[b + 1]; st[b + 1] = ts; }
-  const long long rows = (long long)n[0] * n[1];
-  const bool f32 = precision == OFFT_PREC_F32;
-  // two single-precision elements per lane: unit stride, whole pairs, 16-B aligned rows and bases
-  bool pair = f32 && st[2] == 1 && !(n[2] & 1) && !(st[1] & 1) && !(st[0] & 1) && !((uintptr_t)out & 15);
+  const PointRows r(n0, n1, n2, s0, s1, s2);
+  bool pair = r.pair_rows(precision) && !((uintptr_t)out & 15);
   for (int k = 0; k < nin; k++)
     pair = pair && !((uintptr_t)ins[k] & 15) && !((uintptr_t)filters[k] & (kind == OFFT_FILTER_COMPLEX ? 15 : 7));
-  const int epl = pair ? 2 : 1;
-  const unsigned gx = (unsigned)((n[2] / epl + 255) / 256);
-  const unsigned gy = (unsigned)(rows < 65535 ? rows : 65535);
   hipStream_t sm = (hipStream_t)stream;
   (void)hipGetLastError();
   const bool cx = kind == OFFT_FILTER_COMPLEX;
 #define SUM(T, CPLX, EPL) \
-  hipLaunchKernelGGL((pointwise_sum_k<T, CPLX, EPL>), dim3(gx, gy), dim3(256), 0, sm, sa, (typename vec2<T>::type *)out, n[1], n[2], st[0], st[1], st[2], rows)
+  hipLaunchKernelGGL((pointwise_sum_k<T, CPLX, EPL>), r.grid(pair), dim3(256), 0, sm, sa, (typename vec2<T>::type *)out, r.n[1], r.n[2], r.st[0], r.st[1], r.st[2], r.rows)
   if (pair) { if (cx) SUM(float, true, 2); else SUM(float, false, 2); }
   else if (cx) FOR_PREC(precision, SUM(T, true, 1));
   else FOR_PREC(precision, SUM(T, false, 1));
@@ -2174,16 +2166,8 @@ int offt_hipk_conv_pass_sum(const offt_pass_desc *d, const offt_filter_desc *f, 
     snprintf(g_err, sizeof g_err, "%s: no multi-input fused convolution kernel for this descriptor (n=%d)", who, d ? d->n : 0);
     return -1;
   }
-  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
-  Tables tb;
-  if (get_tables(d->n, d->precision, tb, false)) return -1;
-  PassArgs a = pass_args(d, v->cols, true);
-  ConvArgs fa;
-  fa.axis = f->axis_stride; fa.col = f->col_stride; fa.b1 = f->b1_stride; fa.b2 = f->b2_stride;
-  fa.cplx = f->kind == OFFT_FILTER_COMPLEX;
-  void *args[5] = {(void *)&a, (void *)&fa, (void *)&sa, (void *)&dst, (void *)&tb.full};
-  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
-                args, (hipStream_t)stream);
+  void *mid[2] = {(void *)&sa, (void *)&dst};
+  return line_launch(who, v, d, f, mid, 2, stream);
 }
 
 int offt_hipk_pointwise_sum(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,

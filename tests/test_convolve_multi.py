@@ -400,7 +400,7 @@ def test_multi_half_box_cpu(multi_cpu, case, pruned):
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------
 # ---- 8. random out-of-place descriptors -------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [64, 256, 1024])   # the shortest; a three-stage one; the longest, with the most registers
+@pytest.mark.parametrize("n", [64, 128, 256, 512, 1024])   # every registered length
 def test_multi_random_oop_descriptors(kl, n):
     import torch
     L = kl

@@ -353,7 +353,7 @@ def test_sum_half_box_cpu(sum_cpu, case, pruned):
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------
 # ---- 10. random gather descriptors -----------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [64, 256, 1024])   # the shortest; two-stage 16 x 16 packed; the longest, split images in f64
+@pytest.mark.parametrize("n", [64, 128, 256, 512, 1024])   # every registered length (256: two-stage 16 x 16 packed; 1024: split images in f64)
 def test_sum_random_gather_descriptors(kl, n):
     import torch
     L = kl

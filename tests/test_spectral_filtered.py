@@ -473,7 +473,7 @@ def test_spec_failed_exchange_leaves_the_marker_cpu(built, monkeypatch):
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------
 # ---- 5. random descriptors of both kernels ----------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [64, 256, 1024])   # the shortest (two stages); a three-stage one; the longest, with the most registers
+@pytest.mark.parametrize("n", [64, 128, 256, 512, 1024])   # every registered length
 def test_spec_random_descriptors_gpu(kl, n):
     import torch
     L = kl
