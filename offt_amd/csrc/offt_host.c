@@ -3014,15 +3014,17 @@ void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int directi
 /* ------------------------------------------------------------------------- */
 /* spectral convolution: forward, filter, inverse in one call                 */
 /* ------------------------------------------------------------------------- */
-/* Three calls share everything here but their multiply: offt_hip_execute_convolve (in place), ..._convolve_multi (one
- * forward, an out-of-place multiply and an inverse per output) and ..._convolve_sum (a forward per input, one
- * multiply-and-sum, one inverse).  A call is: conv_begin, its refusals, conv_ready, conv_enter, the fused route of one rank
- * (execute_convolve_single, execute_convolve_sum_single: conv_fused_route decides, conv_plane_groups runs the y / fused / y launches) or else the generic
- * one (conv_forward, the call's own multiply, conv_inverse), conv_leave. */
-typedef enum { CONV_INPLACE, CONV_OOP, CONV_SUM } conv_flavour;
+/* Five calls share everything here but their multiply: offt_hip_execute_convolve (in place), ..._convolve_multi (one
+ * forward, an out-of-place multiply and an inverse per output), ..._convolve_sum (a forward per input, one
+ * multiply-and-sum, one inverse) and the two halves of a convolve as calls of their own, ..._forward_filtered and
+ * ..._inverse_filtered.  A call is: conv_begin, its refusals, conv_ready, conv_enter, the fused route of one rank
+ * (conv_fused_route or spec_fused_route decides, conv_plane_groups runs the y / fused / y launches) or else the generic one
+ * (conv_forward, the call's own multiply, conv_inverse), conv_leave. */
+typedef enum { CONV_INPLACE, CONV_OOP, CONV_SUM, CONV_FILT_FWD, CONV_FILT_INV } conv_flavour;
 
-/* the fused launch of one plane group: in place on `dst` (filters[0]); from srcs[0] into `dst` (filters[0]); or the gather of
- * nin sources, each times its filter, into `dst` */
+/* the fused launch of one plane group: in place on `dst` (filters[0]; the convolve's, or the filtered forward's x pass); from
+ * srcs[0] into `dst` (filters[0]; the convolve's, or the filtered inverse's x pass); or the gather of nin sources, each times
+ * its filter, into `dst` */
 typedef struct conv_launch {
   conv_flavour flavour;
   int nin;
@@ -3065,6 +3067,28 @@ static int conv_need_arrays(struct _offt_plan *po, const char *who, int n, const
   return 0;
 }
 
+/* The refusals the calls on n arrays share, in their order: n outside 1 ... limit (`limit_name` in the sentence), the filter
+ * kind, no arrays at all, the call's one other array (`one`, `one_role`, say_null: conv_need_device), the n arrays of `role`
+ * ("output": nout and outs in the sentences; "input": nin and ins) and their filters. */
+static int conv_check_n(struct _offt_plan *po, const char *who, int n, int limit, const char *limit_name, const char *role,
+                        int filter_kind, void *const *arrs, const void *const *filters, const void *one, const char *one_role,
+                        int say_null) {
+  const int cut = (int)strlen(role) - 3; /* "out" of "output", "in" of "input" */
+  if (n < 1 || n > limit) CONV_REFUSE(po, "%s: n%.*s = %d (1 ... %s = %d %ss)", who, cut, role, n, limit_name, limit, role);
+  if (conv_check_kind(po, who, filter_kind)) return -1;
+  if (!arrs || !filters) CONV_REFUSE(po, "%s: %.*ss and filters must be arrays of n%.*s pointers (got NULL)", who, cut, role, cut, role);
+  if (conv_need_device(po, who, one, one_role, -1, CONV_NO_STAGING, say_null)) return -1;
+  return conv_need_arrays(po, who, n, filters, arrs, role);
+}
+
+/* order[]: the n outputs with the one that is `src` (at most one: the entries differ) last -- until it is made, `src` holds
+ * the spectrum every other output is made from */
+static void conv_order(const void *src, int n, void *const *outs, int *order) {
+  int m = 0;
+  for (int k = 0; k < n; k++) if (outs[k] != src) order[m++] = k;
+  for (int k = 0; k < n; k++) if (outs[k] == src) order[m++] = k;
+}
+
 /* the last refusals: a backend without the call's multiply (`multiply` names it), a communicator that failed earlier */
 static int conv_ready(struct _offt_plan *po, const char *who, int has_multiply, const char *multiply) {
   hip_state *st = (hip_state *)po->hip_state;
@@ -3103,6 +3127,18 @@ static int conv_leave(struct _offt_plan *po, double t0, int rc) {
   return 0;
 }
 
+/* What every fused route launches, from the x pass `l` of a schedule: *fd, that pass's descriptor (the lines through its
+ * input side, scale 1, stores not kept), and *fl, the filter's addressing (that pass's output side). */
+static void conv_route_descs(const offt_pass_desc *l, int kind, offt_pass_desc *fd, offt_filter_desc *fl) {
+  *fd = *l;
+  fd->scale = 1.0;
+  fd->out_keep = 0;
+  memset(fl, 0, sizeof *fl);
+  fl->kind = kind;
+  fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
+  fl->b1_stride = l->out_b1_stride; fl->b2_stride = l->out_b2_stride;
+}
+
 /* The single-rank fused route: the forward's first two launches, ONE launch for the forward's last pass + the filter + the
  * inverse's first pass (they work on the same lines: the caller's array in z-y-x, the scratch volume V in the rotated
  * y-z-x layout), the inverse's last two launches.  *fd receives the fused launch's descriptor (the forward's last pass;
@@ -3122,15 +3158,9 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
   if (flavour == CONV_OOP && (!fw->zyx || !st->be->conv_pass_oop)) return 0;
   if (flavour == CONV_SUM && (!fw->zyx || !st->be->conv_pass_sum)) return 0;
   if (st->use_pipeline || !st->be->conv_pass) return 0;
-  *fd = *l;
-  fd->scale = 1.0;
-  fd->out_keep = 0;
+  conv_route_descs(l, kind, fd, fl);
   if (l->half) fd->half = 3; /* half box: the fused launch loads the lower half of every x line and stores only that */
-  memset(fl, 0, sizeof *fl);
-  fl->kind = kind;
   fl->mixed = st->opt.conv_mixed; /* OFFT_HIP_OPT_CONV_MIXED: a length that is no power of two may have a fused kernel too */
-  fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
-  fl->b1_stride = l->out_b1_stride; fl->b2_stride = l->out_b2_stride;
   /* the inverse's first pass must store where the forward's last one loads, with the same addressing.  Where the inverse
    * is the forward schedule mirrored (single_schedule) that holds by construction; the one schedule that keeps its launch
    * order, in-place x-y-z on a complex plan, starts its inverse with the z pass and has no fused route */
@@ -3152,7 +3182,23 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
   }
 }
 
-/* behind offt_hip_convolve_fused, offt_hip_convolve_multi_fused and offt_hip_convolve_sum_fused */
+/* The fused route of the two filtered calls (the two halves of a convolve as calls of their own, for a caller whose state is
+ * a spectrum): one rank, the z-y-x layout, no half box, both backend entries and a kernel pair for the x extent (powers of
+ * two from 64 to 1024), OFFT_HIP_OPT_SPEC_FUSED set.  *fd and *fl as above, from the forward's x pass.  0: the generic route. */
+static int spec_fused_route(struct _offt_plan *po, const single_sched *fw, int kind, offt_pass_desc *fd, offt_filter_desc *fl) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_pass_desc *l = &fw->d[2];
+  if (st->use_pipeline || !fw->zyx || st->half_box || !st->opt.spec_fused || !st->be->filt_pass_fwd || !st->be->filt_pass_inv) return 0;
+  conv_route_descs(l, kind, fd, fl);
+  /* in place on the caller's array: the x pass loads and stores the same lines */
+  if (fw->src[2] != fw->dst[2] || l->out_axis_stride != l->in_axis_stride || l->out_col_stride != l->in_col_stride ||
+      l->out_b1_stride != l->in_b1_stride || l->out_b2_stride != l->in_b2_stride)
+    return 0;
+  return offt_hipk_filt_has_fused(fd, fl);
+}
+
+/* behind offt_hip_convolve_fused, offt_hip_convolve_multi_fused, offt_hip_convolve_sum_fused and offt_hip_spectral_fused (asked
+ * as CONV_FILT_FWD: the two filtered calls have one route) */
 static int conv_fused_query(const struct _offt_plan *po, conv_flavour flavour) {
   if (!po || !po->hip_state) return 0;
   single_sched fw, iv;
@@ -3161,62 +3207,79 @@ static int conv_fused_query(const struct _offt_plan *po, conv_flavour flavour) {
   struct _offt_plan *p = (struct _offt_plan *)po;
   if (((hip_state *)po->hip_state)->use_pipeline) return 0;
   single_schedule(p, NULL, -1, &fw);
+  if (flavour == CONV_FILT_FWD) return spec_fused_route(p, &fw, OFFT_FILTER_REAL, &fd, &fl);
   single_schedule(p, NULL, +1, &iv);
   return conv_fused_route(p, &fw, &iv, OFFT_FILTER_REAL, flavour, &fd, &fl);
 }
 int offt_hip_convolve_fused(const struct _offt_plan *po) { return conv_fused_query(po, CONV_INPLACE); }
 int offt_hip_convolve_multi_fused(const struct _offt_plan *po) { return conv_fused_query(po, CONV_OOP); }
 int offt_hip_convolve_sum_fused(const struct _offt_plan *po) { return conv_fused_query(po, CONV_SUM); }
+int offt_hip_spectral_fused(const struct _offt_plan *po) { return conv_fused_query(po, CONV_FILT_FWD); }
 
-/* The middle of every fused route: the forward's y pass (fw->d[1]; left out with with_y = 0, for the later outputs of the
- * multi call), the fused launch `cl` with the descriptors of conv_fused_route, the inverse's y pass (iv->d[1]).
- * z-y-x: all three work on z-planes of the caller's arrays (nb1 = Nz in single_schedule, pruned or not: one z-plane per batch
+/* the y pass of `ss` on the g planes from z0 on (g = 0: as it is), its stores kept for the launch behind it where `keep` */
+static int conv_y_pass(const hip_state *st, const single_sched *ss, int z0, int g, int keep) {
+  offt_pass_desc d = ss->d[1];
+  if (g) {
+    d.nb1 = g;
+    if (keep) d.out_keep = 1;
+  }
+  return st->be->pass(&d, (const char *)ss->src[1] + (size_t)z0 * (size_t)d.in_b1_stride * st->esz,
+                      (char *)ss->dst[1] + (size_t)z0 * (size_t)d.out_b1_stride * st->esz, st->s_compute);
+}
+
+/* The middle of every fused route: the forward's y pass (fw->d[1]; launched with with_y = 1 only: not for the later outputs
+ * of the multi call; no fw at all on the filtered inverse), the fused launch `cl` with the descriptors of its route, the
+ * inverse's y pass (iv->d[1]; no iv on the filtered forward).
+ * z-y-x: all of them work on z-planes of the caller's arrays (nb1 = Nz in single_schedule, pruned or not: one z-plane per batch
  * entry), so they alternate over groups of planes that fit the Infinity Cache, as the y and x launches of a plain transform
- * do (execute_single) -- y(group) keeps its stores, the fused launch re-reads and keeps, the inverse's y pass re-reads.  Same
- * group size rule and option (OFFT_HIP_OPT_ZGROUP_MIB, 0 = plain launches).  A group's planes sit at the same offset in
- * every source and in the destination of the fused launch.  Every other layout, and z-y-x without groups, launches the
- * three descriptors as they are. */
+ * do (execute_single) -- every launch with another behind it in the group keeps its stores (the forward's y pass; the fused
+ * launch where there is an inverse y pass), the last one re-reads.  Same group size rule and option
+ * (OFFT_HIP_OPT_ZGROUP_MIB, 0 = plain launches), asked about `producer`: the forward's y pass, or on the filtered inverse the
+ * plain x pass its launch stands in for.  The convolve flavours ask for the z-y-x layout and all three launches over every
+ * plane; the filtered ones have the layout from their route and ask it of the launches they have.  A group's planes sit at the
+ * same offset in every source and in the destination of the fused launch.  Every other layout, and z-y-x without groups,
+ * launches the descriptors as they are. */
 static int conv_plane_groups(struct _offt_plan *po, const single_sched *fw, int with_y, const offt_pass_desc *fd,
-                             const offt_filter_desc *fl, const conv_launch *cl, const single_sched *iv) {
+                             const offt_filter_desc *fl, const conv_launch *cl, const single_sched *iv, const offt_pass_desc *producer) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_backend *be = st->be;
   void *s = st->s_compute;
-  const offt_pass_desc *py = &fw->d[1], *qy = &iv->d[1];
   const size_t esz = st->esz, fesz = fl->kind == OFFT_FILTER_COMPLEX ? esz : esz / 2; /* filter bytes per element */
   const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
+  const int filtered = cl->flavour == CONV_FILT_FWD || cl->flavour == CONV_FILT_INV;
   int ng = 0; /* planes per group; 0: plain launches */
-  if (fw->zyx && py->nb1 == cnt && fd->nb1 == cnt && qy->nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, py);
+  if ((filtered || fw->zyx) && (!fw || fw->d[1].nb1 == cnt) && fd->nb1 == cnt && (!iv || iv->d[1].nb1 == cnt))
+    ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, producer);
   const int step = ng >= 1 ? ng : cnt;
   for (int z0 = 0; z0 < cnt; z0 += step) {
-    offt_pass_desc a = *py, b = *fd, q = *qy;
-    if (ng >= 1) {
-      a.nb1 = b.nb1 = q.nb1 = cnt - z0 < ng ? cnt - z0 : ng;
-      a.out_keep = b.out_keep = 1;
+    const int g = ng < 1 ? 0 : cnt - z0 < ng ? cnt - z0 : ng; /* planes of this group; 0: the descriptors as they are */
+    offt_pass_desc b = *fd;
+    if (g) {
+      b.nb1 = g;
+      if (iv) b.out_keep = 1;
     }
     const size_t off = (size_t)z0 * (size_t)b.in_b1_stride * esz, foff = (size_t)z0 * (size_t)fl->b1_stride * fesz;
-    if (with_y && be->pass(&a, (const char *)fw->src[1] + (size_t)z0 * (size_t)a.in_b1_stride * esz,
-                           (char *)fw->dst[1] + (size_t)z0 * (size_t)a.out_b1_stride * esz, s))
-      return -1;
+    const void *filter = (const char *)cl->filters[0] + foff, *src = (const char *)cl->srcs[0] + off;
+    void *dst = (char *)cl->dst + off;
+    if (with_y && conv_y_pass(st, fw, z0, g, 1)) return -1;
     int rc = -1;
     switch (cl->flavour) {
-    case CONV_INPLACE: rc = be->conv_pass(&b, fl, (const char *)cl->filters[0] + foff, (char *)cl->dst + off, s); break;
-    case CONV_OOP:
-      rc = be->conv_pass_oop(&b, fl, (const char *)cl->filters[0] + foff, (const char *)cl->srcs[0] + off, (char *)cl->dst + off, s);
-      break;
+    case CONV_INPLACE: rc = be->conv_pass(&b, fl, filter, dst, s); break;
+    case CONV_OOP: rc = be->conv_pass_oop(&b, fl, filter, src, dst, s); break;
     case CONV_SUM: {
       const void *srcs[OFFT_HIP_CONV_MAX_IN], *fg[OFFT_HIP_CONV_MAX_IN];
       for (int k = 0; k < cl->nin; k++) {
         srcs[k] = (const char *)cl->srcs[k] + off;
         fg[k] = (const char *)cl->filters[k] + foff;
       }
-      rc = be->conv_pass_sum(&b, fl, cl->nin, fg, srcs, (char *)cl->dst + off, s);
+      rc = be->conv_pass_sum(&b, fl, cl->nin, fg, srcs, dst, s);
       break;
     }
+    case CONV_FILT_FWD: rc = be->filt_pass_fwd(&b, fl, filter, dst, s); break;
+    case CONV_FILT_INV: rc = be->filt_pass_inv(&b, fl, filter, src, dst, s); break;
     }
     if (rc) return -1;
-    if (be->pass(&q, (const char *)iv->src[1] + (size_t)z0 * (size_t)q.in_b1_stride * esz,
-                 (char *)iv->dst[1] + (size_t)z0 * (size_t)q.out_b1_stride * esz, s))
-      return -1;
+    if (iv && conv_y_pass(st, iv, z0, g, 0)) return -1;
   }
   return 0;
 }
@@ -3250,7 +3313,7 @@ static int execute_convolve_single(struct _offt_plan *po, void *data, int nout, 
     void *out = outs[order[i]];
     single_schedule(po, out, +1, &iv); /* z-y-x: x in place on out, y: out -> W, z: W -> out, the output scale on the z pass */
     const conv_launch cl = {out == data ? CONV_INPLACE : CONV_OOP, 1, &fw.src[2], iv.dst[0], &filters[order[i]]};
-    if (conv_plane_groups(po, &fw, i == 0, &fd, &fl, &cl, &iv)) return -1;
+    if (conv_plane_groups(po, &fw, i == 0, &fd, &fl, &cl, &iv, &fw.d[1])) return -1;
     if (be->pass(&iv.d[2], iv.src[2], iv.dst[2], s)) return -1;
   }
   return 0;
@@ -3280,7 +3343,7 @@ static int execute_convolve_sum_single(struct _offt_plan *po, int nin, void *con
     if (k < nin - 1 && be->pass(&fw.d[1], fw.src[1], fw.dst[1], s)) return -1;
   }
   const conv_launch cl = {CONV_SUM, nin, (const void *const *)ins, out, filters};
-  if (conv_plane_groups(po, &fw, 1, &fd, &fl, &cl, &iv)) return -1; /* (fw: of the last input) */
+  if (conv_plane_groups(po, &fw, 1, &fd, &fl, &cl, &iv, &fw.d[1])) return -1; /* (fw: of the last input) */
   return be->pass(&iv.d[2], iv.src[2], iv.dst[2], s) ? -1 : 0;
 }
 
@@ -3316,6 +3379,19 @@ static int conv_pointwise(struct _offt_plan *po, void *data, const void *filter,
                            c->ostride[2], st->s_compute) ? -1 : 0;
 }
 
+/* ... in place, or src -> dst (pointwise_oop; on a table from before it, a copy and the in-place multiply) */
+static int conv_multiply(struct _offt_plan *po, const void *src, void *dst, const void *filter, int kind) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const struct _offt_comm *c = po->comm;
+  if (src == dst) return conv_pointwise(po, dst, filter, kind);
+  if (be->pointwise_oop)
+    return be->pointwise_oop(src, dst, filter, st->prec, kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0], c->ostride[1],
+                             c->ostride[2], st->s_compute) ? -1 : 0;
+  if (be->memcpy_dd(dst, src, local_elems(c) * st->esz, st->s_compute)) return -1;
+  return conv_pointwise(po, dst, filter, kind);
+}
+
 int offt_hip_execute_convolve(struct _offt_plan *po, void *data, const void *filter, int filter_kind) {
   static const char who[] = "offt_hip_execute_convolve";
   hip_state *st = (hip_state *)po->hip_state;
@@ -3341,22 +3417,14 @@ int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout,
                                     int filter_kind) {
   static const char who[] = "offt_hip_execute_convolve_multi";
   hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
-  const struct _offt_comm *c = po->comm;
   conv_begin(po);
-  if (nout < 1 || nout > OFFT_HIP_CONV_MAX_OUT)
-    CONV_REFUSE(po, "%s: nout = %d (1 ... OFFT_HIP_CONV_MAX_OUT = %d outputs)", who, nout, OFFT_HIP_CONV_MAX_OUT);
-  if (conv_check_kind(po, who, filter_kind)) return -1;
-  if (!outs || !filters) CONV_REFUSE(po, "%s: outs and filters must be arrays of nout pointers (got NULL)", who);
-  if (conv_need_device(po, who, data, "the data", -1, CONV_NO_STAGING, 0) || conv_need_arrays(po, who, nout, filters, outs, "output") ||
-      conv_ready(po, who, be->pointwise != NULL, "pointwise multiply"))
+  if (conv_check_n(po, who, nout, OFFT_HIP_CONV_MAX_OUT, "OFFT_HIP_CONV_MAX_OUT", "output", filter_kind, outs, filters, data, "the data", 0) ||
+      conv_ready(po, who, st->be->pointwise != NULL, "pointwise multiply"))
     return -1;
   /* one output, in place: the single-output call itself, bit for bit */
   if (nout == 1 && outs[0] == data) return offt_hip_execute_convolve(po, data, filters[0], filter_kind);
-  /* the output that is `data` (at most one: the entries differ) is computed last: until then `data` holds the spectrum */
-  int order[OFFT_HIP_CONV_MAX_OUT], n = 0;
-  for (int k = 0; k < nout; k++) if (outs[k] != data) order[n++] = k;
-  for (int k = 0; k < nout; k++) if (outs[k] == data) order[n++] = k;
+  int order[OFFT_HIP_CONV_MAX_OUT]; /* the output that is `data` is computed last */
+  conv_order(data, nout, outs, order);
   const double t0 = conv_enter(po);
   int rc = half_box_clear(po, data);
   if (!rc) rc = st->use_pipeline ? 1 : execute_convolve_single(po, data, nout, order, outs, filters, filter_kind);
@@ -3364,17 +3432,8 @@ int offt_hip_execute_convolve_multi(struct _offt_plan *po, void *data, int nout,
     /* generic: one forward on data, then per output the multiply data -> out and the inverse on out */
     rc = conv_forward(po, data);
     for (int i = 0; i < nout && !rc; i++) {
-      void *out = outs[order[i]];
-      const void *filter = filters[order[i]];
-      if (out == data) rc = conv_pointwise(po, data, filter, filter_kind);
-      else if (be->pointwise_oop)
-        rc = be->pointwise_oop(data, out, filter, st->prec, filter_kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0],
-                               c->ostride[1], c->ostride[2], st->s_compute) ? -1 : 0;
-      else { /* a backend from before the out-of-place multiply: copy, then multiply in place */
-        rc = be->memcpy_dd(out, data, local_elems(c) * st->esz, st->s_compute) ? -1 : 0;
-        if (!rc) rc = conv_pointwise(po, out, filter, filter_kind);
-      }
-      if (!rc) rc = conv_inverse(po, out);
+      rc = conv_multiply(po, data, outs[order[i]], filters[order[i]], filter_kind);
+      if (!rc) rc = conv_inverse(po, outs[order[i]]);
     }
   }
   return conv_leave(po, t0, rc);
@@ -3387,11 +3446,7 @@ int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *i
   const offt_backend *be = st->be;
   const struct _offt_comm *c = po->comm;
   conv_begin(po);
-  if (nin < 1 || nin > OFFT_HIP_CONV_MAX_IN)
-    CONV_REFUSE(po, "%s: nin = %d (1 ... OFFT_HIP_CONV_MAX_IN = %d inputs)", who, nin, OFFT_HIP_CONV_MAX_IN);
-  if (conv_check_kind(po, who, filter_kind)) return -1;
-  if (!ins || !filters) CONV_REFUSE(po, "%s: ins and filters must be arrays of nin pointers (got NULL)", who);
-  if (conv_need_device(po, who, out, "the output", -1, CONV_NO_STAGING, 1) || conv_need_arrays(po, who, nin, filters, ins, "input") ||
+  if (conv_check_n(po, who, nin, OFFT_HIP_CONV_MAX_IN, "OFFT_HIP_CONV_MAX_IN", "input", filter_kind, ins, filters, out, "the output", 1) ||
       conv_ready(po, who, be->pointwise_sum != NULL, "pointwise multiply-and-sum"))
     return -1;
   /* one input, in place: the single-output call itself, bit for bit */
@@ -3412,100 +3467,16 @@ int offt_hip_execute_convolve_sum(struct _offt_plan *po, int nin, void *const *i
   return conv_leave(po, t0, rc);
 }
 
-/* ---- filtered forward and filtered inverse: the two halves of a convolve as calls of their own, for a caller whose state
- * is a spectrum (pseudo-spectral solvers).  Same entry, exit and refusals as the convolve calls above. ----
- * The fused route: one rank, the z-y-x layout, no half box, both backend entries and a kernel pair for the x extent (powers
- * of two from 64 to 1024), OFFT_HIP_OPT_SPEC_FUSED set.  *fd receives the x pass's descriptor (lines through its input side,
- * scale 1) and *fl the filter's addressing (its output side).  0: the generic route. */
-static int spec_fused_route(struct _offt_plan *po, const single_sched *fw, int kind, offt_pass_desc *fd, offt_filter_desc *fl) {
-  hip_state *st = (hip_state *)po->hip_state;
-  const offt_pass_desc *l = &fw->d[2];
-  if (st->use_pipeline || !fw->zyx || st->half_box || !st->opt.spec_fused || !st->be->filt_pass_fwd || !st->be->filt_pass_inv) return 0;
-  *fd = *l;
-  fd->scale = 1.0;
-  fd->out_keep = 0;
-  memset(fl, 0, sizeof *fl);
-  fl->kind = kind;
-  fl->axis_stride = l->out_axis_stride; fl->col_stride = l->out_col_stride;
-  fl->b1_stride = l->out_b1_stride; fl->b2_stride = l->out_b2_stride;
-  /* in place on the caller's array: the x pass loads and stores the same lines */
-  if (fw->src[2] != fw->dst[2] || l->out_axis_stride != l->in_axis_stride || l->out_col_stride != l->in_col_stride ||
-      l->out_b1_stride != l->in_b1_stride || l->out_b2_stride != l->in_b2_stride)
-    return 0;
-  return offt_hipk_filt_has_fused(fd, fl);
-}
-
-int offt_hip_spectral_fused(const struct _offt_plan *po) {
-  if (!po || !po->hip_state) return 0;
-  single_sched fw;
-  offt_pass_desc fd;
-  offt_filter_desc fl;
-  struct _offt_plan *p = (struct _offt_plan *)po;
-  if (((hip_state *)po->hip_state)->use_pipeline) return 0;
-  single_schedule(p, NULL, -1, &fw);
-  return spec_fused_route(p, &fw, OFFT_FILTER_REAL, &fd, &fl);
-}
-
-/* Plane groups of a fused filtered call, conv_plane_groups' rule (OFFT_HIP_OPT_ZGROUP_MIB, 0 = plain launches; a remainder
- * group): per group the producer, then the consumer, the producer's stores kept.
- *   forward (inv = 0): y pass of the forward (fw->d[1]: W -> data), then the filtered x launch in place on `data`;
- *   inverse (inv = 1): the filtered x launch spec -> out, then the y pass of the inverse (iv->d[1]: out -> W). */
-static int spec_plane_groups(struct _offt_plan *po, const single_sched *ss, int inv, const offt_pass_desc *fd, const offt_filter_desc *fl,
-                             const void *filter, const void *src, void *dst) {
-  hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
-  void *s = st->s_compute;
-  const offt_pass_desc *py = &ss->d[1];
-  const size_t esz = st->esz, fesz = fl->kind == OFFT_FILTER_COMPLEX ? esz : esz / 2; /* filter bytes per element */
-  const int cnt = po->is_r2c ? po->Nz / 2 + 1 : po->Nz; /* z-planes of the spectrum */
-  int ng = 0; /* planes per group; 0: plain launches */
-  /* (the producer the rule asks about: the forward's y pass, or the plain x pass the filtered inverse launch stands in for) */
-  if (py->nb1 == cnt && fd->nb1 == cnt) ng = plane_group(st, (double)po->Nx * po->Ny, cnt, po->Ny, po->Nx, inv ? &ss->d[0] : py);
-  const int step = ng >= 1 ? ng : cnt;
-  for (int z0 = 0; z0 < cnt; z0 += step) {
-    offt_pass_desc y = *py, x = *fd;
-    if (ng >= 1) {
-      y.nb1 = x.nb1 = cnt - z0 < ng ? cnt - z0 : ng;
-      if (inv) x.out_keep = 1;
-      else y.out_keep = 1;
-    }
-    const size_t off = (size_t)z0 * (size_t)x.in_b1_stride * esz, foff = (size_t)z0 * (size_t)fl->b1_stride * fesz;
-    const char *ysrc = (const char *)ss->src[1] + (size_t)z0 * (size_t)y.in_b1_stride * esz;
-    char *ydst = (char *)ss->dst[1] + (size_t)z0 * (size_t)y.out_b1_stride * esz;
-    if (!inv) {
-      if (be->pass(&y, ysrc, ydst, s)) return -1;
-      if (be->filt_pass_fwd(&x, fl, (const char *)filter + foff, (char *)dst + off, s)) return -1;
-    } else {
-      if (be->filt_pass_inv(&x, fl, (const char *)filter + foff, (const char *)src + off, (char *)dst + off, s)) return -1;
-      if (be->pass(&y, ysrc, ydst, s)) return -1;
-    }
-  }
-  return 0;
-}
-
-/* this rank's output block times H: in place, or src -> dst (pointwise_oop; on a table from before it, a copy and the in-place
- * multiply) */
-static int spec_multiply(struct _offt_plan *po, const void *src, void *dst, const void *filter, int kind) {
-  hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
-  const struct _offt_comm *c = po->comm;
-  if (src == dst) return conv_pointwise(po, dst, filter, kind);
-  if (be->pointwise_oop)
-    return be->pointwise_oop(src, dst, filter, st->prec, kind, c->osize[0], c->osize[1], c->osize[2], c->ostride[0], c->ostride[1],
-                             c->ostride[2], st->s_compute) ? -1 : 0;
-  if (be->memcpy_dd(dst, src, local_elems(c) * st->esz, st->s_compute)) return -1;
-  return conv_pointwise(po, dst, filter, kind);
-}
-
+/* ---- filtered forward and filtered inverse: same entry, exit, refusals and runner as the convolve calls above; the route is
+ * spec_fused_route's ---- */
 /* data (input layout) -> H . fftn(data) in the forward's output layout, in place */
 int offt_hip_execute_forward_filtered(struct _offt_plan *po, void *data, const void *filter, int filter_kind) {
   static const char who[] = "offt_hip_execute_forward_filtered";
   hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
   conv_begin(po);
   if (conv_check_kind(po, who, filter_kind) || conv_need_device(po, who, filter, "the filter", -1, "", 1) ||
       conv_need_device(po, who, data, "the data", -1, CONV_NO_STAGING, 1) ||
-      conv_ready(po, who, be->pointwise != NULL, "pointwise multiply"))
+      conv_ready(po, who, st->be->pointwise != NULL, "pointwise multiply"))
     return -1;
   const double t0 = conv_enter(po);
   int rc = half_box_clear(po, data);
@@ -3515,9 +3486,10 @@ int offt_hip_execute_forward_filtered(struct _offt_plan *po, void *data, const v
   if (!st->use_pipeline) single_schedule(po, data, -1, &fw);
   if (!rc && !st->use_pipeline && spec_fused_route(po, &fw, filter_kind, &fd, &fl)) {
     /* z pass, then per plane group the y pass (kept) and the x pass with the multiply and the output scale on its stores */
+    const conv_launch cl = {CONV_FILT_FWD, 1, (const void *const *)&data, data, &filter};
     fd.scale = fw.d[2].scale;
-    rc = be->pass(&fw.d[0], fw.src[0], fw.dst[0], st->s_compute) ? -1 : 0;
-    if (!rc) rc = spec_plane_groups(po, &fw, 0, &fd, &fl, filter, data, data);
+    rc = st->be->pass(&fw.d[0], fw.src[0], fw.dst[0], st->s_compute) ? -1 : 0;
+    if (!rc) rc = conv_plane_groups(po, &fw, 1, &fd, &fl, &cl, NULL, &fw.d[1]);
   } else if (!rc) {
     rc = conv_forward_scaled(po, data);
     if (!rc) rc = conv_pointwise(po, data, filter, filter_kind);
@@ -3531,19 +3503,12 @@ int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, i
                                       int filter_kind) {
   static const char who[] = "offt_hip_execute_inverse_filtered";
   hip_state *st = (hip_state *)po->hip_state;
-  const offt_backend *be = st->be;
   conv_begin(po);
-  if (nout < 1 || nout > OFFT_HIP_CONV_MAX_OUT)
-    CONV_REFUSE(po, "%s: nout = %d (1 ... OFFT_HIP_CONV_MAX_OUT = %d outputs)", who, nout, OFFT_HIP_CONV_MAX_OUT);
-  if (conv_check_kind(po, who, filter_kind)) return -1;
-  if (!outs || !filters) CONV_REFUSE(po, "%s: outs and filters must be arrays of nout pointers (got NULL)", who);
-  if (conv_need_device(po, who, spec, "the spectrum", -1, CONV_NO_STAGING, 1) || conv_need_arrays(po, who, nout, filters, outs, "output") ||
-      conv_ready(po, who, be->pointwise != NULL, "pointwise multiply"))
+  if (conv_check_n(po, who, nout, OFFT_HIP_CONV_MAX_OUT, "OFFT_HIP_CONV_MAX_OUT", "output", filter_kind, outs, filters, spec, "the spectrum", 1) ||
+      conv_ready(po, who, st->be->pointwise != NULL, "pointwise multiply"))
     return -1;
-  /* the output that is `spec` (at most one: the entries differ) comes last: until then `spec` holds the spectrum */
-  int order[OFFT_HIP_CONV_MAX_OUT], n = 0;
-  for (int k = 0; k < nout; k++) if (outs[k] != spec) order[n++] = k;
-  for (int k = 0; k < nout; k++) if (outs[k] == spec) order[n++] = k;
+  int order[OFFT_HIP_CONV_MAX_OUT]; /* the output that is `spec` comes last */
+  conv_order(spec, nout, outs, order);
   const double t0 = conv_enter(po);
   int rc = 0;
   single_sched fw, iv;
@@ -3553,15 +3518,15 @@ int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, i
   const int fused = !st->use_pipeline && spec_fused_route(po, &fw, filter_kind, &fd, &fl);
   for (int i = 0; i < nout && !rc; i++) {
     void *out = outs[order[i]];
-    const void *filter = filters[order[i]];
     if (fused) {
       /* per plane group the x pass with the multiply on its loads (spec -> out, kept) and the inverse's y pass (out -> W); then
        * the inverse's last pass (W -> out; real output over Nz/2+1 planes on an r2c plan), the output scale on its stores */
+      const conv_launch cl = {CONV_FILT_INV, 1, &spec, out, &filters[order[i]]};
       single_schedule(po, out, +1, &iv);
-      rc = spec_plane_groups(po, &iv, 1, &fd, &fl, filter, spec, out);
-      if (!rc) rc = be->pass(&iv.d[2], iv.src[2], iv.dst[2], st->s_compute) ? -1 : 0;
+      rc = conv_plane_groups(po, NULL, 0, &fd, &fl, &cl, &iv, &iv.d[0]);
+      if (!rc) rc = st->be->pass(&iv.d[2], iv.src[2], iv.dst[2], st->s_compute) ? -1 : 0;
     } else {
-      rc = spec_multiply(po, spec, out, filter, filter_kind);
+      rc = conv_multiply(po, spec, out, filters[order[i]], filter_kind);
       if (!rc) rc = conv_inverse(po, out);
     }
   }

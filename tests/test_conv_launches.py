@@ -1,12 +1,13 @@
-"""The launch sequences of the multi-output and the multi-input convolve, pinned: every backend call of
-offt_hip_execute_convolve_multi and offt_hip_execute_convolve_sum on one rank (descriptors field by field, filter descriptors,
-buffers, strides, out_keep, the scale, order, streams, event edges) and the three routes a plan reports, against
-tests/golden/conv_launches.json.
+"""The launch sequences of the multi-output and the multi-input convolve and of the two filtered transforms, pinned: every
+backend call of offt_hip_execute_convolve_multi, offt_hip_execute_convolve_sum, offt_hip_execute_forward_filtered and
+offt_hip_execute_inverse_filtered on one rank (descriptors field by field, filter descriptors, buffers, strides, out_keep, the
+scale, order, streams, event edges) and the routes a plan reports, against tests/golden/conv_launches.json.
 
 The sibling of tests/test_single_rank_launches.py, whose Recorder it extends to the whole of offt_backend: memcpy_dd,
-zero_outside, conv_pass_oop, pointwise_oop, conv_pass_sum and pointwise_sum are logged too, pointers, streams and events named
-as there ("data", "out1", "in0", "filter2" are the caller's arrays).  The tables are those of tests/cpu_backend_multi.c and
-tests/cpu_backend_sum.c, the older ones among them (no fused launch; no multiply with a destination).
+zero_outside, conv_pass_oop, pointwise_oop, conv_pass_sum, pointwise_sum, filt_pass_fwd and filt_pass_inv are logged too,
+pointers, streams and events named as there ("data", "spec", "out1", "in0", "filter2" are the caller's arrays).  The tables are
+those of tests/cpu_backend_multi.c, tests/cpu_backend_sum.c and tests/cpu_backend_spec.c, the older ones among them (no fused
+launch; no multiply with a destination).
 
   python tests/test_conv_launches.py --record [<commit>]    rewrites the fixture (with the library that OFFT_AMD_TEST_LIB
                                                             names, built from <commit>)
@@ -25,6 +26,7 @@ import numpy as np
 
 import _conv_multi_world as MW
 import _conv_sum_world as SW
+import _spec_world as SPW
 import cpu_world
 import test_single_rank_launches as SRL
 from offt_amd import api
@@ -36,7 +38,8 @@ DESC_FIELDS = [f[0] for f in Desc._fields_]
 FDESC_FIELDS = [f[0] for f in FDesc._fields_]
 
 # offt_backend (offt_amd/csrc/offt_backend.h), entry by entry, to its end
-TABLE_ENTRIES = SRL.TABLE_ENTRIES + ["zero_outside", "conv_pass_oop", "pointwise_oop", "conv_pass_sum", "pointwise_sum"]
+TABLE_ENTRIES = SRL.TABLE_ENTRIES + ["zero_outside", "conv_pass_oop", "pointwise_oop", "conv_pass_sum", "pointwise_sum",
+                                     "filt_pass_fwd", "filt_pass_inv"]
 
 
 class Table(C.Structure):
@@ -52,7 +55,9 @@ SIGNATURES = dict(SRL.SIGNATURES,
                   conv_pass_oop=C.CFUNCTYPE(I, C.POINTER(Desc), C.POINTER(FDesc), V, V, V, V),
                   pointwise_oop=C.CFUNCTYPE(I, V, V, V, I, I, I, I, I, LL, LL, LL, V),
                   conv_pass_sum=C.CFUNCTYPE(I, C.POINTER(Desc), C.POINTER(FDesc), I, PV, PV, V, V),
-                  pointwise_sum=C.CFUNCTYPE(I, I, PV, PV, V, I, I, I, I, I, LL, LL, LL, V))
+                  pointwise_sum=C.CFUNCTYPE(I, I, PV, PV, V, I, I, I, I, I, LL, LL, LL, V),
+                  filt_pass_fwd=C.CFUNCTYPE(I, C.POINTER(Desc), C.POINTER(FDesc), V, V, V),
+                  filt_pass_inv=C.CFUNCTYPE(I, C.POINTER(Desc), C.POINTER(FDesc), V, V, V, V))
 
 
 class Recorder(SRL.Recorder):
@@ -114,6 +119,19 @@ class Recorder(SRL.Recorder):
             return orig(nin, ins, filts, out, prec, kind, n0, n1, n2, s0, s1, s2, stream)
         return f
 
+    def _filt_pass_fwd(self, orig):
+        def f(d, fl, filt, data, stream):
+            self.log.append(["filt_pass_fwd", self.desc(d), self.fdesc(fl), self.ptr(filt), self.ptr(data), self.name("s", stream)])
+            return orig(d, fl, filt, data, stream)
+        return f
+
+    def _filt_pass_inv(self, orig):
+        def f(d, fl, filt, src, dst, stream):
+            self.log.append(["filt_pass_inv", self.desc(d), self.fdesc(fl), self.ptr(filt), self.ptr(src), self.ptr(dst),
+                             self.name("s", stream)])
+            return orig(d, fl, filt, src, dst, stream)
+        return f
+
 
 # ---- the cases -----------------------------------------------------------------------------------------------------------
 GRID = [64, 64, 40]                             # (x == y: the rotating y-z-x layout needs it)
@@ -122,13 +140,14 @@ MIXED_GRID, MIXED_GRID_96 = [48, 64, 40], [96, 64, 40]  # mixed-radix x lengths
 BOTH_MIXED = [(api.OPT_CONV_MIXED, 1), (api.OPT_CONV_MULTI_MIXED, 1)]
 ZG0 = {"OFFT_ZGROUP_MIB": "0"}                  # plain launches (unset, this grid is ONE group of all its planes, stores kept)
 ZG = {"OFFT_ZGROUP_MIB": "1"}                   # 1 MiB plane groups: 16 of the 40 z-planes of 64 x 64 in double, so three groups
+SPEC = [(api.OPT_SPEC_FUSED, 1)]                # the filtered calls' fused route is opt-in
 
 
 def all_cases():
-    """a case: run ("multi" / "sum"), id, layout, N, r2c, f32, cplx (complex filter), env, K (outputs / inputs), inplace
-    (index of the output that is `data` / of the input that is `out`, or None), opts (offt_hip_set_option pairs), half (1: half
-    box on, the padding cleared; 2: on, every launch skips the padding), table (which backend table), fused (the route the
-    call under test must take: the case is there for it)"""
+    """a case: run ("multi" / "sum" / "fwdfilt" / "invfilt"), id, layout, N, r2c, f32, cplx (complex filter), env, K (outputs /
+    inputs / filters), inplace (index of the output that is `data` or `spec` / of the input that is `out`, or None), opts
+    (offt_hip_set_option pairs), half (1: half box on, the padding cleared; 2: on, every launch skips the padding), table (which
+    backend table), fused (the route the call under test must take: the case is there for it)"""
     def case(run, cid, fused, **kw):
         return dict(dict(run=run, id=f"{run}-{cid}", fused=fused, layout="zyx", N=GRID, r2c=0, f32=0, cplx=0, env={}, K=2, inplace=None,
                          opts=[], half=0, table="full"), **kw)
@@ -152,7 +171,24 @@ def all_cases():
              case("sum", "zyx-half-unpruned", 1, half=1),
              case("sum", "zyx-table_nofused", 0, table="nofused"),
              case("sum", "yzx_rot", 0, layout="yzx_rot"), case("sum", "xyz_inplace", 0, layout="xyz_inplace")]
+    # the filtered forward (one filter) and the filtered inverse (K outputs of one spectrum): the fused route in z-y-x with both
+    # backend entries and OFFT_HIP_OPT_SPEC_FUSED set, the generic one everywhere else
+    for run, kw in (("fwdfilt", dict(K=1)), ("invfilt", dict(K=2))):
+        cases += [case(run, "zyx", 1, opts=SPEC, **kw), case(run, "zyx-zgroup1", 1, opts=SPEC, env=ZG, **kw),
+                  case(run, "zyx-zgroup0", 1, opts=SPEC, env=ZG0, **kw),
+                  case(run, "zyx-r2c-f32-cplx", 1, opts=SPEC, r2c=1, f32=1, cplx=1, **kw),
+                  case(run, "zyx-spec_fused-off", 0, **kw), case(run, "zyx-half-unpruned", 0, opts=SPEC, half=1, **kw),
+                  case(run, "zyx-table_nofilt", 0, opts=SPEC, table="nofilt", **kw),
+                  case(run, "yzx_rot", 0, opts=SPEC, layout="yzx_rot", **kw),
+                  case(run, "xyz_inplace", 0, opts=SPEC, layout="xyz_inplace", **kw)]
+    cases += [case("invfilt", "zyx-3out-spec-in-the-middle", 1, opts=SPEC, K=3, inplace=1),
+              case("invfilt", "zyx-1out-is-spec", 1, opts=SPEC, K=1, inplace=0),
+              case("invfilt", "zyx-table_old", 0, opts=SPEC, table="old")]
     return cases
+
+
+def is_filtered(case):
+    return case["run"] in ("fwdfilt", "invfilt")
 
 
 def run_case(rec, case):
@@ -184,8 +220,12 @@ def run_case(rec, case):
         kind = api.FILTER_COMPLEX if case["cplx"] else api.FILTER_REAL
         L.offt_hip_set_output_scale(po, 0.5)  # (not 1.0: which launch carries the scale is part of the record)
         routes = [int(bool(q(po))) for q in (api.offt_hip_convolve_fused, api.offt_hip_convolve_multi_fused, api.offt_hip_convolve_sum_fused)]
-        assert routes[1 if case["run"] == "multi" else 2] == case["fused"], (case["id"], routes)
-        rec.log.append(["convolve_fused", "convolve_multi_fused", "convolve_sum_fused"] + routes)
+        names = ["convolve_fused", "convolve_multi_fused", "convolve_sum_fused"]
+        if is_filtered(case):
+            names.append("spectral_fused")
+            routes.append(int(bool(api.offt_hip_spectral_fused(po))))
+        assert routes[{"multi": 1, "sum": 2}.get(case["run"], 3)] == case["fused"], (case["id"], routes)
+        rec.log.append(names + routes)
         assert bool(api.offt_hip_half_box_pruned(po)) == (case["half"] == 2), case["id"]
         rec.log.append(["half_box_pruned", int(case["half"] == 2)])
         if case["run"] == "multi":
@@ -193,6 +233,15 @@ def run_case(rec, case):
             outs = [data if k == inplace else np.zeros(ne, dtype=ct) for k in range(K)]
             rec.arrays.update({"data": data}, **{f"out{k}": o for k, o in enumerate(outs) if o is not data})
             api.offt_hip_execute_convolve_multi(po, data.ctypes.data, [o.ctypes.data for o in outs], [f.ctypes.data for f in filts], kind)
+        elif case["run"] == "fwdfilt":
+            data = np.zeros(ne, dtype=ct)
+            rec.arrays["data"] = data
+            api.offt_hip_execute_forward_filtered(po, data.ctypes.data, filts[0].ctypes.data, kind)
+        elif case["run"] == "invfilt":
+            spec = np.zeros(ne, dtype=ct)
+            outs = [spec if k == inplace else np.zeros(ne, dtype=ct) for k in range(K)]
+            rec.arrays.update({"spec": spec}, **{f"out{k}": o for k, o in enumerate(outs) if o is not spec})
+            api.offt_hip_execute_inverse_filtered(po, spec.ctypes.data, [o.ctypes.data for o in outs], [f.ctypes.data for f in filts], kind)
         else:
             ins = [np.zeros(ne, dtype=ct) for _ in range(K)]
             out = np.zeros(ne, dtype=ct) if inplace is None else ins[inplace]
@@ -205,13 +254,17 @@ def run_case(rec, case):
 
 def run_all():
     """{case id: log} for every case"""
-    subprocess.check_call(["make", "-s", "-C", ROOT, "tests/libcpubackend.so", "tests/libcpubackend_multi.so", "tests/libcpubackend_sum.so"])
+    subprocess.check_call(["make", "-s", "-C", ROOT, "tests/libcpubackend.so", "tests/libcpubackend_multi.so", "tests/libcpubackend_sum.so",
+                           "tests/libcpubackend_spec.so"])
     cpu_world.install(0, 1)  # (the library routing; the table is replaced below)
     L = api.lib()
-    M, S = MW.multi_cb_lib(), SW.sum_cb_lib()
+    M, S, F = MW.multi_cb_lib(), SW.sum_cb_lib(), SPW.spec_cb_lib()
     recs = {("multi", "full"): Recorder(M.cpu_backend_multi_table()), ("multi", "unfused"): Recorder(M.cpu_backend_multi_table_unfused()),
             ("multi", "old"): Recorder(M.cpu_backend_multi_table_old()), ("sum", "full"): Recorder(S.cpu_backend_sum_table()),
             ("sum", "nofused"): Recorder(S.cpu_backend_sum_table_nofused())}
+    for run in ("fwdfilt", "invfilt"):  # (a recorder per run kind, as above; the three tables are statics of their own)
+        recs.update({(run, "full"): Recorder(F.cpu_backend_spec_table()), (run, "nofilt"): Recorder(F.cpu_backend_spec_table_nofilt()),
+                     (run, "old"): Recorder(F.cpu_backend_spec_table_old())})
     out = {}
     try:
         for case in all_cases():
