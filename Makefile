@@ -93,6 +93,10 @@ tests/libcpubackend_sum.so: tests/cpu_backend_sum.c tests/cpu_backend_padreal.c 
 tests/libcpubackend_spec.so: tests/cpu_backend_spec.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
 	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_spec.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c -lm
 
+# ... and with the entry of the shell-binned spectra filled and its calls counted (tests/test_spectrum_shells.py)
+tests/libcpubackend_shells.so: tests/cpu_backend_shells.c tests/cpu_backend_spec.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
+	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_shells.c tests/cpu_backend_spec.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c -lm
+
 # ... and with every launch, event and stream operation logged with its stream, and the memory each launch touches (tests/test_streams.py)
 tests/libcpubackend_streams.so: tests/cpu_backend_streams.c tests/cpu_backend_spec.c tests/cpu_backend_sum.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
 	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_streams.c tests/cpu_backend_spec.c tests/cpu_backend_sum.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c -lm -lpthread

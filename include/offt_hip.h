@@ -147,6 +147,28 @@ int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, i
                                       int filter_kind);
 /* 1 if both calls take the fused route on this plan, else 0 */
 int offt_hip_spectral_fused(const struct _offt_plan *po);
+/* Shell-binned power and cross spectra of a stored spectrum: the isotropic P(|k|) of a density or velocity field, or the
+ * cross spectrum of two fields, from this rank's block in the forward's OUTPUT layout (the Nz/2+1 half spectrum of an r2c
+ * plan), without the spectrum leaving the device.  a and b (NULL: b = a) are device memory in the plan's precision; neither
+ * is written.
+ * On axis i, global index g has the signed wavenumber k_i = g if 2 g <= N_i, else g - N_i; K2 = (kmul[0] k_x)^2 +
+ * (kmul[1] k_y)^2 + (kmul[2] k_z)^2 in 64-bit integers (kmul NULL: {1,1,1}; a 2N x N x N grid of one spacing: {1,2,2}).
+ * The shell of a mode is the nearest integer to sqrt(K2), the s with (2s-1)^2 <= 4 K2 < (2s+1)^2, decided in integer
+ * arithmetic: membership is exact.  Modes of shells >= nbins are left out.
+ * sums[s] = sum over the shell of w Re(A conj(B)), counts[s] = sum of w (counts may be NULL): device arrays of nbins entries,
+ * overwritten.  w = 1; on an r2c plan w = 2 where 0 < k_z and 2 k_z != Nz, so that both arrays equal what the full spectrum
+ * of the real field gives.  Every element is converted to double before its product, and every term is formed and added in
+ * double, single-precision plans included; the order of the additions depends on the plan and nbins only, so that two calls
+ * with the same inputs give the same bits.
+ * LOCAL, not collective: on several ranks each rank gets the partial sums of its own block (zeros for an empty block), and
+ * adding them across ranks is the caller's.  Stream, async and offt_hip_last_device_seconds as for
+ * offt_hip_execute_forward_filtered; offt_hip_last_pass_seconds reports zeros.
+ * 0 on success; -1 with t[ALL] = 99999999 and offt_hip_last_error(), and nothing launched, for a NULL or host-memory a or
+ * sums, a host-memory b or counts, nbins < 1 or > OFFT_HIP_SHELLS_MAX_BINS, a kmul entry below 1, a backend without the
+ * entry. */
+#define OFFT_HIP_SHELLS_MAX_BINS 4096
+int offt_hip_spectrum_shells(struct _offt_plan *po, const void *a, const void *b, const int kmul[3], int nbins, double *sums,
+                             long long *counts);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
  *   full spectrum of the zero-padded field, in the usual output layout.

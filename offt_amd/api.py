@@ -117,6 +117,8 @@ def bind(L):
     L.offt_hip_execute_inverse_filtered.argtypes = [PP, C.c_void_p, i, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i]
     L.offt_hip_spectral_fused.restype = i
     L.offt_hip_spectral_fused.argtypes = [PP]
+    L.offt_hip_spectrum_shells.restype = i
+    L.offt_hip_spectrum_shells.argtypes = [PP, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), i, C.c_void_p, C.c_void_p]
     L.offt_hip_set_half_box.restype = i
     L.offt_hip_set_half_box.argtypes = [PP, i]
     L.offt_hip_half_box_pruned.restype = i
@@ -287,6 +289,20 @@ def offt_hip_execute_inverse_filtered(po, spec, outs, filts, filter_kind=FILTER_
 def offt_hip_spectral_fused(po):
     """True if both filtered calls run the route whose x pass carries the multiply"""
     return lib().offt_hip_spectral_fused(po) == 1
+
+
+SHELLS_MAX_BINS = 4096  # offt_hip.h OFFT_HIP_SHELLS_MAX_BINS
+
+
+def offt_hip_spectrum_shells(po, a, b, nbins, sums, counts=None, kmul=None):
+    """shell-binned power (b None) or cross spectrum of this rank's block of a stored spectrum (forward's output layout):
+    sums[s] = sum of w Re(a conj(b)) and counts[s] = sum of w over the modes whose |k| rounds to s, s < nbins; device pointers,
+    sums of nbins doubles, counts (optional) of nbins 64-bit integers, kmul three integers >= 1 or None.  Local, not
+    collective (include/offt_hip.h)"""
+    L = lib()
+    km = (C.c_int * 3)(*kmul) if kmul is not None else None
+    if L.offt_hip_spectrum_shells(po, a, b, km, nbins, sums, counts) != 0:
+        raise RuntimeError("offt_hip_spectrum_shells failed: " + L.offt_hip_last_error().decode())
 
 
 def offt_hip_set_half_box(po, on=True):

@@ -83,6 +83,13 @@ typedef struct offt_backend {
    * filt_pass_inv: offt_hipk_filt_pass_inv -- the inverse x pass with the filter on its loads, src -> dst (dst may be src). */
   int (*filt_pass_fwd)(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, void *data, void *stream);
   int (*filt_pass_inv)(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream);
+  /* ---- shell-binned spectra (offt_hip_spectrum_shells); appended at the end, so that every older table leaves it NULL and
+   * the call is refused there ----
+   * spectrum_shells: offt_hipk_spectrum_shells -- the sweep and the fixed-order sum of its partials (`partials`: device
+   * memory of offt_hipk_spectrum_shells_partials bytes, a backend without workgroups ignores it). */
+  int (*spectrum_shells)(const void *a, const void *b, int precision, int r2c, const int n[3], const long long stride[3], const int start[3],
+                         const int N[3], const int kmul[3], int nbins, double *sums, long long *counts, void *partials,
+                         long long partials_bytes, void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);

@@ -248,6 +248,25 @@ int offt_hipk_filt_has_fused(const offt_pass_desc *d, const offt_filter_desc *f)
 /* "fft_filt_fwd_panel_k" / "fft_filt_inv_panel_k", or "no fused kernel" */
 const char *offt_hipk_filt_fwd_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f);
 const char *offt_hipk_filt_inv_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f);
+/* ---- shell-binned power and cross spectra (offt_hip_spectrum_shells) ----
+ * A read-only sweep over the strided box n[] x stride[] (complex elements of `precision`; arrays indexed by axis x, y, z) of
+ * a spectrum whose local index 0 sits at global index start[] of a grid of N[] points (r2c: the box is part of the
+ * N[2]/2+1 half spectrum, N[2] the full length, and modes off the planes k_z = 0 and 2 k_z = N[2] weigh 2).  With the signed
+ * wavenumbers k_i and K2 = sum (kmul[i] k_i)^2, the shell of a mode is the s with (2s-1)^2 <= 4 K2 < (2s+1)^2, decided in
+ * integers; sums[s] = sum of w Re(a conj(b)) over the shell (b NULL or a: |a|^2), counts[s] = sum of w (counts may be NULL),
+ * both of nbins entries, overwritten; shells >= nbins are dropped.  start NULL: zeros; kmul NULL: ones.  Every term is
+ * formed and added in double.  Rows along the smallest stride, 16 B per lane, non-temporal; no floating-point atomic: runs of
+ * equal shell are summed across lanes, the run heads update per-wave LDS tables, waves and workgroups are added in index
+ * order (through `partials`, device memory of at least offt_hipk_spectrum_shells_partials bytes, which the call overwrites),
+ * so that equal arguments give equal bits.  An empty box stores zeros.  -1, nothing launched: bad arguments, kmul[i] * N[i]/2
+ * above 2^30, 2^30 rows or more, too few partials. */
+#define OFFT_HIPK_SHELLS_MAX_BINS 4096
+int offt_hipk_spectrum_shells(const void *a, const void *b, int precision, int r2c, const int n[3], const long long stride[3],
+                              const int start[3], const int N[3], const int kmul[3], int nbins, double *sums, long long *counts,
+                              void *partials, long long partials_bytes, void *stream);
+/* bytes of `partials` a call with these arguments needs at most (whatever the strides and the arrays' alignment); 0 for an
+ * empty box and for arguments the call refuses.  Host arithmetic only. */
+long long offt_hipk_spectrum_shells_partials(int precision, const int n[3], const int N[3], const int kmul[3], int nbins);
 /* zero a strided 3-D block n0 x n1 x n2 OUTSIDE the kept sub-box [0,k0) x [0,k1) x [0,k2) (0 <= k <= n); the kept part is
  * not touched.  Elements are complex values of `precision`, or, with OFFT_HIPK_ZERO_REAL or-ed into it, real scalars (the
  * rows of an r2c plan; strides and extents then count scalars).  Vector stores, 16 B per lane along a unit stride s2. */

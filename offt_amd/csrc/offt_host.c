@@ -429,6 +429,7 @@ typedef struct hip_state {
   unsigned long long *p2p_status; /* host-visible: a wait kernel gave up */
   ncclComm_t comm1, comm2; int have_comm1, have_comm2;
   void *stage; size_t stage_bytes;
+  void *shells_part; long long shells_bytes; /* offt_hip_spectrum_shells: the workgroups' partial sums, grown on demand */
   int variant[3];
   double out_scale;
   int yx_fused;        /* the last single-rank execute alternated launches i and i+1 over groups of planes: i + 1 (0: none) */
@@ -716,11 +717,18 @@ static int hb_zero_outside(void *buf, int precision, int n0, int n1, int n2, int
   if (rc) SET_ERR("clearing the padding failed: %s", offt_hipk_last_error());
   return rc;
 }
+static int hb_spectrum_shells(const void *a, const void *b, int precision, int r2c, const int n[3], const long long stride[3], const int start[3],
+                              const int N[3], const int kmul[3], int nbins, double *sums, long long *counts, void *partials,
+                              long long partials_bytes, void *stream) {
+  const int rc = offt_hipk_spectrum_shells(a, b, precision, r2c, n, stride, start, N, kmul, nbins, sums, counts, partials, partials_bytes, stream);
+  if (rc) SET_ERR("shell-binned spectrum failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
     hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside,
-    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv};
+    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv, hb_spectrum_shells};
 #ifdef OFFT_TEST_SEAMS
 /* the HIP backend without its fused multi-input launch, for offt_hip_test_set_backend: a plan made under it takes the generic
  * route of offt_hip_execute_convolve_sum on the device (tools/conv_probe.py times that route with it) */
@@ -1135,6 +1143,7 @@ static void state_free(hip_state *st) {
   be->dfree(st->agree_d); free(st->agree_h);
   mesh_teardown(st);
   be->dfree(st->stage);
+  be->dfree(st->shells_part);
   be->event_destroy(st->ev0); be->event_destroy(st->ev1);
   for (int i = 0; i < 4; i++) be->event_destroy(st->evp[i]);
   if (st->own_stream) be->stream_destroy(st->s_compute);
@@ -3530,6 +3539,41 @@ int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, i
       if (!rc) rc = conv_inverse(po, out);
     }
   }
+  return conv_leave(po, t0, rc);
+}
+
+/* ---- shell-binned power and cross spectra of a stored spectrum: the convolve calls' entry, exit and refusals around one
+ * backend entry.  Local: this rank's block (osize box, ostride addressing, ostart in the global grid) only. ---- */
+int offt_hip_spectrum_shells(struct _offt_plan *po, const void *a, const void *b, const int kmul[3], int nbins, double *sums,
+                             long long *counts) {
+  static const char who[] = "offt_hip_spectrum_shells";
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const struct _offt_comm *c = po->comm;
+  conv_begin(po);
+  if (conv_need_device(po, who, a, "the spectrum", -1, "", 1) || (b && conv_need_device(po, who, b, "the second spectrum", -1, "", 0)) ||
+      conv_need_device(po, who, sums, "sums", -1, "", 1) || (counts && conv_need_device(po, who, counts, "counts", -1, "", 0)))
+    return -1;
+  if (nbins < 1 || nbins > OFFT_HIP_SHELLS_MAX_BINS)
+    CONV_REFUSE(po, "%s: nbins = %d (1 ... OFFT_HIP_SHELLS_MAX_BINS = %d bins)", who, nbins, OFFT_HIP_SHELLS_MAX_BINS);
+  for (int i = 0; kmul && i < 3; i++)
+    if (kmul[i] < 1) CONV_REFUSE(po, "%s: kmul[%d] = %d (integer multipliers >= 1)", who, i, kmul[i]);
+  if (conv_ready(po, who, be->spectrum_shells != NULL, "shell-binned spectrum")) return -1;
+  const int n[3] = {c->osize[0], c->osize[1], c->osize[2]}, N[3] = {po->Nx, po->Ny, po->Nz};
+  const long long stride[3] = {c->ostride[0], c->ostride[1], c->ostride[2]};
+  /* the partials: plan-owned, grown behind whatever still reads the smaller allocation */
+  const long long need = offt_hipk_spectrum_shells_partials(st->prec, n, N, kmul, nbins);
+  if (need > st->shells_bytes) {
+    if (st->shells_part && be->stream_sync(st->s_compute)) CONV_REFUSE(po, "%s: the stream failed before the partials could grow", who);
+    be->dfree(st->shells_part);
+    st->shells_bytes = 0;
+    st->shells_part = be->dmalloc((size_t)need);
+    if (!st->shells_part) CONV_REFUSE(po, "%s: cannot allocate %lld bytes of partial sums", who, need);
+    st->shells_bytes = need;
+  }
+  const double t0 = conv_enter(po);
+  const int rc = be->spectrum_shells(a, b, st->prec, po->is_r2c, n, stride, c->ostart, N, kmul, nbins, sums, counts, st->shells_part,
+                                     st->shells_bytes, st->s_compute) ? -1 : 0;
   return conv_leave(po, t0, rc);
 }
 

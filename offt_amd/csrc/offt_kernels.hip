@@ -425,6 +425,184 @@ pointwise_sum_k(SumArgs sa, typename vec2<T>::type *out, int n1, int n2, long lo
   }
 }
 
+// ---------------------------------------------------------------------------
+// shell-binned power / cross spectrum of a strided box (offt_hipk_spectrum_shells): a read-only sweep that ends in a keyed
+// reduction, every floating-point addition in an order fixed by the geometry alone.
+// ---------------------------------------------------------------------------
+// the box after the stride sort (axis 2 = smallest stride), each axis with what its wavenumber needs
+struct ShellArgs {
+  int n[3];          // extents
+  long long st[3];   // strides in elements
+  int g0[3];         // global index of local index 0
+  int N[3];          // global length of the axis (the FULL Nz on the halved axis of an r2c plan)
+  int km[3];         // integer multiplier of the axis' wavenumber
+  int zaxis;         // the halved axis of an r2c plan (weights 2 / 1), -1: complex plan
+  int Nz;            // ... and its full length N[zaxis]
+  int nb;            // bins kept: min(nbins, largest shell of the grid + 1)
+  int n2l;           // lane slots per row: n[2] / EPL
+  int step[3];       // the slots between two chunks of one wave, as (axis-0 rows, axis-1 rows, slots of a row)
+  int with_counts;
+};
+
+// nearest integer to sqrt(k2): the s with (2s-1)^2 <= 4 k2 < (2s+1)^2.  k2 is clamped first (every shell the table can hold
+// is far below the clamp, and the shell is monotone in k2), so that the decision runs in 32-bit integers.  The hardware
+// square root is the first guess only: at c <= 2^27 it is off by less than 0.01 (float(c) and v_sqrt_f32 are each good to
+// 2^-23 relative, sqrt(c) < 11586), so the guess is at most one off and one step either way settles it.
+__device__ __forceinline__ int shell_of(unsigned long long k2) {
+  const unsigned c = k2 < (1ull << 27) ? (unsigned)k2 : (1u << 27);
+  const unsigned four = 4u * c;
+  unsigned s = (unsigned)(__builtin_amdgcn_sqrtf((float)c) + 0.5f);
+  s += (2u * s + 1u) * (2u * s + 1u) <= four ? 1u : 0u;
+  s -= s > 0u && (2u * s - 1u) * (2u * s - 1u) > four ? 1u : 0u;
+  return (int)s;
+}
+
+// lane i reads lane i + D of its row of 16 lanes (zero past the row's end): DPP row_shl, no LDS traffic
+template <int D>
+__device__ __forceinline__ double row_above(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x100 + D, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x100 + D, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
+// One wave, one element per lane (consecutive lanes = consecutive elements of the sweep): add `term` into tab[key], lanes
+// with key < 0 into nothing.  Lanes of equal key that follow one another form a run.  Inside each row of 16 lanes a run is
+// summed towards its first lane by a doubling scan of DPP moves; the piece of a run that starts a row of 16 is then handed to
+// the run's head in the rows below, rows 3, 2, 1 in that order.  The run heads update the table with a plain
+// read-modify-write.  Two heads of one wave can hold the same key only in different monotone segments `seg` of the sweep
+// (|k| along a row rises up to the fold and falls after it), so the heads go segment by segment, in lane order, and the
+// slots of one round are distinct.  Every addition has its place fixed by the keys alone.
+__device__ __forceinline__ void shells_add(double *tab, int lane, int key, int seg, double term) {
+  const int prev = __builtin_amdgcn_update_dpp(key, key, 0x138, 0xf, 0xf, false);   // wave_shr:1: the key of lane - 1
+  const bool head = lane == 0 || prev != key;
+  const unsigned long long heads = __ballot(head);
+  // the last lane of this lane's piece: before the next head, and inside the row of 16
+  const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+  int last = above ? lane + __ffsll((long long)above) - 1 : 63;
+  last = last < (lane | 15) ? last : (lane | 15);
+  double v = key >= 0 ? term : 0.0;
+  { const double o = row_above<1>(v); if (lane + 1 <= last) v += o; }
+  { const double o = row_above<2>(v); if (lane + 2 <= last) v += o; }
+  { const double o = row_above<4>(v); if (lane + 4 <= last) v += o; }
+  { const double o = row_above<8>(v); if (lane + 8 <= last) v += o; }
+#pragma unroll
+  for (int r = 3; r >= 1; r--) {
+    if ((heads >> (16 * r)) & 1ull) continue;   // (uniform) a run starts there: nothing to hand down
+    const int h = 63 - __clzll((long long)(heads & ((1ull << (16 * r)) - 1ull)));   // the head of the run that goes on into row r
+    const double o = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16 * r), __builtin_amdgcn_readlane(__double2loint(v), 16 * r));
+    if (lane == h) v += o;
+  }
+  const bool hk = head && key >= 0;
+  unsigned long long pend = __ballot(hk);
+  while (pend) {
+    const int sg = __builtin_amdgcn_readlane(seg, __ffsll((long long)pend) - 1);
+    const bool mine = hk && seg == sg;
+    if (mine) tab[key] += v;
+    pend &= ~__ballot(mine);
+  }
+}
+
+// the sweep: every wave walks chunks of 64 lane slots (EPL elements each, 16 B per lane, non-temporal) of the rows in
+// storage order, the next chunk's load in flight while this one is binned.  LDS: one table of nb doubles per wave, one table
+// of nb integer counts per workgroup.  At the end the waves' tables are added in wave order and stored, with the counts, as
+// this workgroup's line of the partials.
+template <typename T, bool CROSS, int EPL>
+__global__ void __launch_bounds__(256)
+shells_sweep_k(ShellArgs sa, const typename vec2<T>::type *a, const typename vec2<T>::type *b, double *psum, unsigned *pcnt) {
+  using V2 = typename vec2<T>::type;
+  typedef T vt __attribute__((ext_vector_type(2 * EPL)));
+  extern __shared__ double shells_lds[];
+  const int nb = sa.nb, waves = blockDim.x >> 6, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double *tab = shells_lds + (size_t)wave * nb;
+  unsigned *cnt = reinterpret_cast<unsigned *>(shells_lds + (size_t)waves * nb);
+  for (int i = threadIdx.x; i < waves * nb; i += blockDim.x) shells_lds[i] = 0.0;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) cnt[i] = 0u;
+  __syncthreads();
+
+  const long long slot = ((long long)blockIdx.x * waves + wave) * 64 + lane;
+  const long long row = slot / sa.n2l;
+  int i2 = (int)(slot % sa.n2l), i1 = (int)(row % sa.n[1]);
+  long long i0 = row / sa.n[1];
+  auto load = [&](const V2 *p, bool live, long long o) {
+    vt x = {};
+    if (live) x = __builtin_nontemporal_load(reinterpret_cast<const vt *>(p + o));
+    return x;
+  };
+  bool live = i0 < sa.n[0];
+  long long o = i0 * sa.st[0] + i1 * sa.st[1] + (long long)i2 * EPL * sa.st[2];
+  vt xa = load(a, live, o), xb = {};
+  if constexpr (CROSS) xb = load(b, live, o);
+  while (__builtin_amdgcn_readfirstlane((int)(i0 < sa.n[0]))) {   // lane 0 holds the wave's first slot
+    // this lane's slot of the wave's next chunk, and its load
+    int j2 = i2 + sa.step[2], j1 = i1 + sa.step[1];
+    long long j0 = i0 + sa.step[0];
+    if (j2 >= sa.n2l) { j2 -= sa.n2l; ++j1; }
+    if (j1 >= sa.n[1]) { j1 -= sa.n[1]; ++j0; }
+    const bool nlive = j0 < sa.n[0];
+    const long long no = j0 * sa.st[0] + j1 * sa.st[1] + (long long)j2 * EPL * sa.st[2];
+    const vt na = load(a, nlive, no);
+    vt nbv = {};
+    if constexpr (CROSS) nbv = load(b, nlive, no);
+
+    // wavenumbers of the row, then per element the shell, the weight and the term
+    const int ga = (int)i0 + sa.g0[0], gb = i1 + sa.g0[1];
+    // (|multiplier . wavenumber| <= 2^30 by the launcher's check: squares of 32-bit magnitudes)
+    const unsigned qa = (unsigned)abs(sa.km[0] * (2 * ga <= sa.N[0] ? ga : ga - sa.N[0]));
+    const unsigned qb = (unsigned)abs(sa.km[1] * (2 * gb <= sa.N[1] ? gb : gb - sa.N[1]));
+    const unsigned long long k01 = (unsigned long long)qa * qa + (unsigned long long)qb * qb;
+    const int rowid = (int)i0 * sa.n[1] + i1;
+    const int row0 = __builtin_amdgcn_readfirstlane(rowid);
+#pragma unroll
+    for (int e = 0; e < EPL; e++) {
+      const int gc = i2 * EPL + e + sa.g0[2];
+      const unsigned qc = (unsigned)abs(sa.km[2] * (2 * gc <= sa.N[2] ? gc : gc - sa.N[2]));
+      const int s = shell_of(k01 + (unsigned long long)qc * qc);
+      const int key = live && s < nb ? s : -1;
+      const int gz = sa.zaxis == 0 ? ga : sa.zaxis == 1 ? gb : gc;
+      const int w = sa.zaxis >= 0 && gz > 0 && 2 * gz != sa.Nz ? 2 : 1;
+      const double ar = (double)xa[2 * e], ai = (double)xa[2 * e + 1];
+      double term;
+      if constexpr (CROSS) term = ar * (double)xb[2 * e] + ai * (double)xb[2 * e + 1];
+      else term = ar * ar + ai * ai;
+      if (sa.with_counts && key >= 0) atomicAdd(&cnt[key], (unsigned)w);
+      shells_add(tab, lane, key, 2 * (rowid - row0) + (2 * gc > sa.N[2] ? 1 : 0), (double)w * term);
+    }
+    i0 = j0; i1 = j1; i2 = j2; live = nlive; xa = na;
+    if constexpr (CROSS) xb = nbv;
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < nb; s += blockDim.x) {
+    double acc = 0.0;
+    for (int w = 0; w < waves; w++) acc += shells_lds[(size_t)w * nb + s];
+    psum[(size_t)blockIdx.x * nb + s] = acc;
+    pcnt[(size_t)blockIdx.x * nb + s] = cnt[s];
+  }
+}
+
+// the partials of nwg workgroups added in workgroup order: a workgroup owns 8 bins, each of its 32 thread groups adds a
+// contiguous range of the workgroups, and the 32 sub-sums are added in group order.  Bins nb ... nbins-1 hold no mode.
+#define SHELLS_COMBINE_GROUPS 32
+__global__ void __launch_bounds__(256)
+shells_combine_k(const double *psum, const unsigned *pcnt, int nwg, int nb, int nbins, double *sums, long long *counts) {
+  __shared__ double ssum[SHELLS_COMBINE_GROUPS][8];
+  __shared__ long long scnt[SHELLS_COMBINE_GROUPS][8];
+  const int bin = threadIdx.x & 7, grp = threadIdx.x >> 3, s = blockIdx.x * 8 + bin;
+  const int per = (nwg + SHELLS_COMBINE_GROUPS - 1) / SHELLS_COMBINE_GROUPS;
+  const int g0 = grp * per, g1 = g0 + per < nwg ? g0 + per : nwg;
+  double acc = 0.0;
+  long long c = 0;
+  if (s < nb)
+    for (int g = g0; g < g1; g++) { acc += psum[(size_t)g * nb + s]; c += pcnt[(size_t)g * nb + s]; }
+  ssum[grp][bin] = acc; scnt[grp][bin] = c;
+  __syncthreads();
+  if (grp == 0 && s < nbins) {
+    acc = 0.0; c = 0;
+    for (int g = 0; g < SHELLS_COMBINE_GROUPS; g++) { acc += ssum[g][bin]; c += scnt[g][bin]; }
+    sums[s] = acc;
+    if (counts) counts[s] = c;
+  }
+}
+
 // zero a strided 3-D block outside the kept sub-box [0,k0) x [0,k1) x [0,k2) (offt_hipk_zero_outside): rows along i2, one
 // workgroup row per (i0, i1).  W = scalars of type S per 16-B store; VEC: the rows are unit-stride and 16-B aligned, a lane
 // clears 16 B at W-scalar boundaries (the first store of a row that starts inside the kept part is split into scalars)
@@ -2106,7 +2284,127 @@ int pointwise_sum_launch(const char *who, int nin, const void *const *ins, const
   HIPK_CHECK(hipGetLastError());
   return 0;
 }
+
+// ---- offt_hipk_spectrum_shells: the geometry of a call, worked out on the host ----
+struct ShellGeom {
+  ShellArgs sa;      // all but n2l and step, which depend on the elements per lane (shells_grid)
+  int waves;         // waves per workgroup: as many of 4, 2, 1 as have their tables in 64 KiB of LDS
+  size_t lds;        // ... and those tables' bytes
+  long long rows;
+};
+
+// the host's copy of shell_of (the same clamp, the same integer decision)
+int shell_of_host(unsigned long long k2) {
+  const unsigned c = k2 < (1ull << 27) ? (unsigned)k2 : (1u << 27);
+  const unsigned four = 4u * c;
+  unsigned s = (unsigned)(std::sqrt((double)c) + 0.5);
+  while ((2u * s + 1u) * (2u * s + 1u) <= four) ++s;
+  while (s > 0u && (2u * s - 1u) * (2u * s - 1u) > four) --s;
+  return (int)s;
+}
+
+// false with g_err set: arguments the sweep cannot take.  start may be NULL (zeros), kmul may be NULL (ones).
+bool shells_geom(const char *who, int precision, int r2c, const int n[3], const long long st[3], const int start[3], const int N[3],
+                 const int kmul[3], int nbins, ShellGeom &g) {
+  if (precision != OFFT_PREC_F64 && precision != OFFT_PREC_F32) { snprintf(g_err, sizeof g_err, "%s: bad precision %d", who, precision); return false; }
+  if (nbins < 1 || nbins > OFFT_HIPK_SHELLS_MAX_BINS) {
+    snprintf(g_err, sizeof g_err, "%s: nbins = %d (1 ... %d)", who, nbins, OFFT_HIPK_SHELLS_MAX_BINS);
+    return false;
+  }
+  if (!n || !N) { snprintf(g_err, sizeof g_err, "%s: needs the box and the global extents (got NULL)", who); return false; }
+  memset(&g, 0, sizeof g);
+  int order[3] = {0, 1, 2};   // by falling stride, PointRows' sort
+  if (st)
+    for (int a = 0; a < 2; a++)
+      for (int b = 0; b < 2 - a; b++)
+        if (st[order[b]] < st[order[b + 1]]) std::swap(order[b], order[b + 1]);
+  ShellArgs &sa = g.sa;
+  sa.zaxis = -1;
+  unsigned long long k2max = 0;
+  for (int i = 0; i < 3; i++) {
+    const int ax = order[i], km = kmul ? kmul[ax] : 1, s0 = start ? start[ax] : 0;
+    const bool halved = r2c && ax == 2;
+    if (km < 1) { snprintf(g_err, sizeof g_err, "%s: kmul[%d] = %d (multipliers are >= 1)", who, ax, km); return false; }
+    if (N[ax] < 1 || n[ax] < 0 || s0 < 0 || (long long)s0 + n[ax] > (halved ? N[ax] / 2 + 1 : N[ax])) {
+      snprintf(g_err, sizeof g_err, "%s: axis %d: block %d + %d outside the spectrum of %d points", who, ax, s0, n[ax], N[ax]);
+      return false;
+    }
+    const long long q = (long long)km * (N[ax] / 2);
+    if (q > (1ll << 30)) { snprintf(g_err, sizeof g_err, "%s: kmul[%d] * N/2 = %lld is above 2^30", who, ax, q); return false; }
+    k2max += (unsigned long long)(q * q);
+    sa.n[i] = n[ax]; sa.st[i] = st ? st[ax] : 0; sa.g0[i] = s0; sa.N[i] = N[ax]; sa.km[i] = km;
+    if (halved) { sa.zaxis = i; sa.Nz = N[ax]; }
+  }
+  g.rows = (long long)sa.n[0] * sa.n[1];
+  if (g.rows >= (1ll << 30)) { snprintf(g_err, sizeof g_err, "%s: %lld rows (below 2^30)", who, g.rows); return false; }
+  const int top = shell_of_host(k2max) + 1;
+  sa.nb = nbins < top ? nbins : top;
+  g.waves = (size_t)sa.nb * 36 <= 65536 ? 4 : (size_t)sa.nb * 20 <= 65536 ? 2 : 1;
+  g.lds = (size_t)sa.nb * (8 * (size_t)g.waves + 4);
+  return true;
+}
+
+// workgroups of the sweep with `epl` elements per lane (0 for an empty box); fills sa.n2l and sa.step.  Enough workgroups
+// to fill the device, no more partials than 32 MiB (256 workgroups whatever they take).
+int shells_grid(ShellGeom &g, int epl) {
+  ShellArgs &sa = g.sa;
+  if (g.rows < 1 || sa.n[2] < 1) return 0;
+  sa.n2l = sa.n[2] / epl;
+  const long long chunks = (g.rows * sa.n2l + 63) / 64, want = (chunks + g.waves - 1) / g.waves;
+  long long cap = (32ll << 20) / ((long long)sa.nb * 12);
+  if (cap < 256) cap = 256;
+  if (cap > 8192 / g.waves) cap = 8192 / g.waves;
+  const int nwg = (int)(want < cap ? want : cap);
+  const long long stride = (long long)nwg * g.waves * 64, r = stride / sa.n2l;
+  sa.step[2] = (int)(stride % sa.n2l); sa.step[1] = (int)(r % sa.n[1]); sa.step[0] = (int)(r / sa.n[1]);
+  return nwg;
+}
 }  // namespace
+
+long long offt_hipk_spectrum_shells_partials(int precision, const int n[3], const int N[3], const int kmul[3], int nbins) {
+  ShellGeom g;
+  if (!shells_geom("offt_hipk_spectrum_shells_partials", precision, 0, n, nullptr, nullptr, N, kmul, nbins, g)) return 0;
+  return (long long)shells_grid(g, 1) * g.sa.nb * 12;   // one element per lane: the larger grid of the two
+}
+
+int offt_hipk_spectrum_shells(const void *a, const void *b, int precision, int r2c, const int n[3], const long long stride[3], const int start[3],
+                              const int N[3], const int kmul[3], int nbins, double *sums, long long *counts, void *partials,
+                              long long partials_bytes, void *stream) {
+  const char *who = "offt_hipk_spectrum_shells";
+  ShellGeom g;
+  if (!stride) { snprintf(g_err, sizeof g_err, "%s: needs the strides (got NULL)", who); return -1; }
+  if (!shells_geom(who, precision, r2c, n, stride, start, N, kmul, nbins, g)) return -1;
+  if (!sums) { snprintf(g_err, sizeof g_err, "%s: sums is NULL", who); return -1; }
+  ShellArgs &sa = g.sa;
+  const bool empty = g.rows < 1 || sa.n[2] < 1;
+  if (!empty && !a) { snprintf(g_err, sizeof g_err, "%s: the spectrum is NULL", who); return -1; }
+  const PointRows pr(sa.n[0], sa.n[1], sa.n[2], sa.st[0], sa.st[1], sa.st[2]);
+  const bool pair = !empty && pr.pair_rows(precision) && !((uintptr_t)a & 15) && !((uintptr_t)b & 15);
+  const int nwg = shells_grid(g, pair ? 2 : 1);
+  const long long need = (long long)nwg * sa.nb * 12;
+  if (need > partials_bytes || (need && !partials)) {
+    snprintf(g_err, sizeof g_err, "%s: %lld bytes of partials, %lld needed (offt_hipk_spectrum_shells_partials)", who, partials ? partials_bytes : 0ll, need);
+    return -1;
+  }
+  sa.with_counts = counts != nullptr;
+  double *psum = (double *)partials;
+  unsigned *pcnt = (unsigned *)(psum + (size_t)nwg * sa.nb);
+  hipStream_t sm = (hipStream_t)stream;
+  (void)hipGetLastError();
+  if (nwg) {
+#define SWEEP(T, CROSS, EPL) \
+  hipLaunchKernelGGL((shells_sweep_k<T, CROSS, EPL>), dim3((unsigned)nwg), dim3(64 * g.waves), g.lds, sm, sa, (const typename vec2<T>::type *)a, (const typename vec2<T>::type *)b, psum, pcnt)
+    const bool cross = b != nullptr && b != a;
+    if (pair) { if (cross) SWEEP(float, true, 2); else SWEEP(float, false, 2); }
+    else if (cross) FOR_PREC(precision, SWEEP(T, true, 1));
+    else FOR_PREC(precision, SWEEP(T, false, 1));
+#undef SWEEP
+    HIPK_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(shells_combine_k, dim3((unsigned)((nbins + 7) / 8)), dim3(256), 0, sm, psum, pcnt, nwg, sa.nb, nbins, sums, counts);
+  HIPK_CHECK(hipGetLastError());
+  return 0;
+}
 
 int offt_hipk_conv_has_fused(const offt_pass_desc *fwd, const offt_filter_desc *f) { return pick_conv(fwd, f, false) != nullptr; }
 const char *offt_hipk_conv_kernel_name(const offt_pass_desc *fwd, const offt_filter_desc *f) { return conv_kernel_name(pick_conv(fwd, f, false)); }

@@ -43,7 +43,12 @@ the caller's route built from calls that predate the two (offt_3d_execute + offt
 offt_3d_execute_dir(+1)).  The three ALTERNATE after a warm-up, MIXED_REPS times each, and a line reports min and median of
 all three, the ratios against both, each baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5
 (104 / 136).
-usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+A spec with the prefix shells: measures offt_hip_spectrum_shells (the power spectrum, every shell, with counts) on a plan's
+output block filled with random numbers, next to the in-place REAL offt_hipk_pointwise sweep over the same block (40 B per
+point in double precision against the call's 16 B).  The two ALTERNATE after a warm-up, MIXED_REPS times each, device time by
+events on one stream; the line reports min and median of both, their ratio (the condition: below 1; the byte model: 0.4) and
+the call's rate over the bytes it reads.
+usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:|shells:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
        (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768;
         the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512;
         the multi:mixed: set of profiles/conv_multi_mixed.txt: multi:mixed:768 multi:mixed:f32:768 multi:mixed:1000
@@ -52,7 +57,9 @@ usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:][half:][f
         x lengths sum:64 sum:128 sum:256 sum:f32:256 sum:f32:512;
         the sum:mixed: set of profiles/conv_sum_mixed.txt: sum:mixed:768 sum:mixed:f32:768 sum:mixed:1000 sum:mixed:f32:1000
         sum:mixed:half:768;
-        the spec: set of profiles/spec_filtered.txt: spec:512 spec:f32:512 spec:1024 spec:f32:1024 spec:r2c:512 spec:r2c:f32:512)"""
+        the spec: set of profiles/spec_filtered.txt: spec:512 spec:f32:512 spec:1024 spec:f32:1024 spec:r2c:512 spec:r2c:f32:512;
+        the shells: set of profiles/spectrum_shells.txt: shells:512 shells:f32:512 shells:r2c:512 shells:r2c:f32:512 shells:1024
+        shells:f32:1024 shells:r2c:1024 shells:r2c:f32:1024)"""
 import ctypes as C
 import os
 import sys
@@ -255,6 +262,60 @@ def probe_spec(rest, zg):
     torch.cuda.empty_cache()
 
 
+def probe_shells(rest):
+    """shells:[r2c:][f64|f32:]N -- offt_hip_spectrum_shells next to the in-place real pointwise sweep over the same block"""
+    r2c = rest.startswith("r2c:")
+    kind, _, n_s = rest[(4 if r2c else 0):].rpartition(":")
+    n = int(n_s)
+    prec = api.F32 if kind == "f32" else api.F64
+    V, I, LL = C.c_void_p, C.c_int, C.c_longlong
+    L.offt_hipk_pointwise.argtypes = [V, V, I, I, I, I, I, LL, LL, LL, V]
+    po = api.offt_3d_init(n, n, n, precision=prec, is_r2c=int(r2c))
+    stream = torch.cuda.Stream()
+    L.offt_hip_set_stream(po, stream.cuda_stream)
+    td = torch.float32 if prec == api.F32 else torch.float64
+    ne = api.local_elems(po)
+    c = api.comm_dict(po)
+    osz, ost = c["osize"], c["ostride"]
+    a = torch.randn(ne * 2, dtype=td, device="cuda")
+    H = torch.ones(ne, dtype=td, device="cuda")
+    nb = int(np.rint(np.sqrt(3.0) * (n // 2))) + 1
+    sums = torch.zeros(nb, dtype=torch.float64, device="cuda")
+    cnt = torch.zeros(nb, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def run(fn):
+        ev[0].record(stream)
+        fn()
+        ev[1].record(stream)
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) * 1e-3
+
+    def point():
+        assert L.offt_hipk_pointwise(a.data_ptr(), H.data_ptr(), prec, api.FILTER_REAL, osz[0], osz[1], osz[2], ost[0], ost[1], ost[2],
+                                     stream.cuda_stream) == 0
+
+    rs = (("shells", lambda: api.offt_hip_spectrum_shells(po, a.data_ptr(), None, nb, sums.data_ptr(), cnt.data_ptr())), ("pointwise", point))
+    t = {k: [] for k, _ in rs}
+    for rep_i in range(2 + MIXED_REPS):
+        for name, fn in rs:
+            dt = run(fn)
+            if rep_i >= 2:
+                t[name].append(dt)
+    assert int(cnt.sum()) == n ** 3
+    mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+    esz = 4 if prec == api.F32 else 8
+    read = 2.0 * esz * osz[0] * osz[1] * osz[2]
+    print(f"shells: {'r2c ' if r2c else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3: call min {mn['shells'] * 1e3:.3f} ms median {md['shells'] * 1e3:.3f} ms "
+          f"({read / mn['shells'] / 1e9:.0f} GB/s read)  pointwise (in place, real) min {mn['pointwise'] * 1e3:.3f} ms median {md['pointwise'] * 1e3:.3f} ms  "
+          f"call/pointwise min {mn['shells'] / mn['pointwise']:.3f} median {md['shells'] / md['pointwise']:.3f}  "
+          f"pointwise spread {md['pointwise'] / mn['pointwise'] - 1:.3f}  byte model {16 / 40:.3f}  bins {nb}  n {MIXED_REPS}", flush=True)
+    api.offt_3d_fin(po)
+    del a, H
+    torch.cuda.empty_cache()
+
+
 def probe_sum_mixed(rest, zg):
     """sum:mixed:[half:][f64|f32|r2c:]N -- OFFT_HIP_OPT_CONV_SUM_MIXED at 1 and at 0 and the caller's route, on one plan"""
     K = 3
@@ -338,6 +399,9 @@ def main():
     for spec in specs:
         if spec.startswith("spec:"):
             probe_spec(spec[5:], zg)
+            continue
+        if spec.startswith("shells:"):
+            probe_shells(spec[7:])
             continue
         if spec.startswith("sum:mixed:"):
             probe_sum_mixed(spec[10:], zg)
