@@ -16,7 +16,7 @@ $(BUILD):
 	mkdir -p $(BUILD)
 
 # the kernel instantiations are grouped into several translation units so that `make -j` compiles them in parallel
-HIPSRC    := offt_reg_pow2_f32_big offt_kernels offt_reg_pow2_f64 offt_reg_pow2_f64_1024 offt_reg_pow2_f64_anysplit offt_reg_pow2_f32 offt_reg_pow2_f32_anysplit offt_reg_pow2_f32_pair offt_reg_pow2_tw4 offt_reg_mixed_f64_a offt_reg_mixed_f64_b \
+HIPSRC    := offt_reg_pow2_f32_big offt_kernels offt_reg_pow2_f64 offt_reg_pow2_f64_1024 offt_reg_pair_yx_f64 offt_reg_pow2_f64_anysplit offt_reg_pow2_f32 offt_reg_pow2_f32_anysplit offt_reg_pow2_f32_pair offt_reg_pow2_tw4 offt_reg_mixed_f64_a offt_reg_mixed_f64_b \
              offt_reg_mixed_f64_c offt_reg_mixed_f64_d offt_reg_mixed_f64_e offt_reg_mixed_f32_a offt_reg_mixed_f32_b offt_reg_bluestein offt_reg_bluestein_f32 \
              offt_reg_conv_f64 offt_reg_conv_f32 offt_reg_conv_oop_f64 offt_reg_conv_oop_f32 offt_reg_conv_mixed_f64 offt_reg_conv_mixed_f32 offt_reg_conv_oop_mixed_f64 offt_reg_conv_oop_mixed_f32 offt_reg_conv_sum_f64 offt_reg_conv_sum_f32 offt_reg_conv_sum_mixed_f64 offt_reg_conv_sum_mixed_f32 offt_reg_spec_f64 offt_reg_spec_f32 offt_reg_half_f64 offt_reg_half_f32 offt_reg_half_real_f64 offt_reg_half_real_f32 \
              offt_reg_half_mixed_f64 offt_reg_half_mixed_f32 offt_reg_half_real_mixed_f64 offt_reg_half_real_mixed_f32
@@ -100,6 +100,10 @@ tests/libcpubackend_shells.so: tests/cpu_backend_shells.c tests/cpu_backend_spec
 # ... and with every launch, event and stream operation logged with its stream, and the memory each launch touches (tests/test_streams.py)
 tests/libcpubackend_streams.so: tests/cpu_backend_streams.c tests/cpu_backend_spec.c tests/cpu_backend_sum.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
 	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_streams.c tests/cpu_backend_spec.c tests/cpu_backend_sum.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c -lm -lpthread
+
+# ... and the plain interpreter with offt_backend::pass_pair and a log of the passes (tests/test_zgroup_pipeline.py)
+tests/libcpubackend_pipeline.so: tests/cpu_backend_pipeline.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
+	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_pipeline.c tests/cpu_backend.c oracle/oracle_fft.c -lm
 
 # run-fft-compatible C harness.  MPI=1 builds the multi-rank variant
 # against an MPI found at MPI_PREFIX (e.g. /opt/conda; linked by file name, not -L: a conda lib directory also holds an

@@ -251,6 +251,14 @@ int offt_hip_wait(struct _offt_plan *po);
                                           (offt_hip_spectral_fused: one rank, z-y-x, a power-of-two x extent from 64 to 1024, no half
                                           box), 0 (default) = transform and multiply as separate launches.  Read by every filtered
                                           call; the results agree to rounding (OFFT_SPEC_FUSED) */
+#define OFFT_HIP_OPT_ZGROUP_PIPELINE 19 /* single rank, forward z-y-x in double precision: 1 (default) = the x launch of one plane group and
+                                          the y launch of the next are ONE launch (y(0) | {x(0), y(1)} | ... | x(G-1)) where the x and y
+                                          extents are equal and 64, 128, 256, 512 or 1024 points; 0 = the launches alternate.  Equal
+                                          bits either way; never with OFFT_HIP_OPT_ZGROUP_STREAMS = 2 (OFFT_ZGROUP_PIPELINE) */
+#define OFFT_HIP_OPT_ZGROUP_PLANES 20  /* single rank, the forward z-y-x transform only (no convolve or filtered call reads it): planes
+                                          per group of its y / x launches where they run in groups at all -- it turns nothing on, and
+                                          OFFT_HIP_OPT_ZGROUP_MIB = 0 stays off; > 0 takes the place of the MiB count, 0 (default) =
+                                          that count decides.  For groups finer than a MiB (OFFT_ZGROUP_PLANES) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds
@@ -282,6 +290,9 @@ double offt_hip_last_device_seconds(const struct _offt_plan *po);
  * bits (1 = z, 2 = y, 4 = x). */
 void offt_hip_last_pass_seconds(const struct _offt_plan *po, double t[3]);
 int offt_hip_last_passes_paired(const struct _offt_plan *po);
+/* how many launches of the last single-rank execute carried two passes in one grid (OFFT_HIP_OPT_ZGROUP_PIPELINE): 0 = the
+ * plan did not take that route */
+int offt_hip_last_pipelined_launches(const struct _offt_plan *po);
 /* last error text ("" if none); errors also go to stderr, like the reference's
  * printf-only error handling (offt-compute.c:702-704)                           */
 const char *offt_hip_last_error(void);

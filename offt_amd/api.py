@@ -22,6 +22,9 @@ PARAM_NAMES = ["P1", "T1", "W1", "Px1", "Py1", "Fz", "FP1", "Ux1", "Uz1", "FU1",
 FFTW_ESTIMATE = 1 << 6
 F64, F32 = 0, 1
 FILTER_REAL, FILTER_COMPLEX = 0, 1  # offt_hip.h OFFT_HIP_FILTER_REAL / OFFT_HIP_FILTER_COMPLEX
+OPT_ZGROUP_PLANES = 20  # offt_hip.h OFFT_HIP_OPT_ZGROUP_PLANES: planes per plane group (> 0: instead of OPT_ZGROUP_MIB)
+OPT_ZGROUP_PIPELINE = 19  # offt_hip.h OFFT_HIP_OPT_ZGROUP_PIPELINE: x(group g-1) and y(group g) of the forward z-y-x plane groups as one launch
+OPT_ZGROUP_MIB = 0  # offt_hip.h OFFT_HIP_OPT_ZGROUP_MIB: MiB per plane group (0 off, -1 the library's rule)
 OPT_SPEC_FUSED = 18  # (17 is unassigned) offt_hip.h OFFT_HIP_OPT_SPEC_FUSED: the filtered forward / inverse may run the route whose x pass carries the multiply
 OPT_CONV_SUM_MIXED = 16  # offt_hip.h OFFT_HIP_OPT_CONV_SUM_MIXED: with OPT_CONV_MIXED, the multi-input convolve of such a plan may run the fused gather route (15 is unassigned)
 OPT_CONV_MULTI_MIXED = 14  # offt_hip.h OFFT_HIP_OPT_CONV_MULTI_MIXED: with OPT_CONV_MIXED, the multi-output convolve of such a plan may run the fused multi route
@@ -145,6 +148,8 @@ def bind(L):
     L.offt_hip_last_pass_seconds.argtypes = [PP, C.POINTER(C.c_double)]
     L.offt_hip_last_passes_paired.restype = i
     L.offt_hip_last_passes_paired.argtypes = [PP]
+    L.offt_hip_last_pipelined_launches.restype = i
+    L.offt_hip_last_pipelined_launches.argtypes = [PP]
     L.offt_hip_last_error.restype = C.c_char_p
     L.offt_hip_malloc.restype = C.c_void_p
     L.offt_hip_malloc.argtypes = [C.c_longlong]

@@ -90,6 +90,11 @@ typedef struct offt_backend {
   int (*spectrum_shells)(const void *a, const void *b, int precision, int r2c, const int n[3], const long long stride[3], const int start[3],
                          const int N[3], const int kmul[3], int nbins, double *sums, long long *counts, void *partials,
                          long long partials_bytes, void *stream);
+  /* ---- pipelined plane groups (execute_single, OFFT_HIP_OPT_ZGROUP_PIPELINE); appended, so that every older table leaves it
+   * NULL and its plans alternate their launches as before ----
+   * pass_pair: offt_hipk_fft_pass_pair -- two independent passes as one launch: `dy` from iny to outy and `dx` from inx to
+   * outx.  A backend without workgroups runs the two one after the other. */
+  int (*pass_pair)(const offt_pass_desc *dy, const void *iny, void *outy, const offt_pass_desc *dx, const void *inx, void *outx, void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);

@@ -103,6 +103,19 @@ _Static_assert(sizeof(offt_pass_desc) == 192 && __builtin_offsetof(offt_pass_des
 int offt_hipk_prepare(int n, int precision);
 /* Launch one pass on `stream` (a hipStream_t).  No allocation, no sync.        */
 int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void *stream);
+/* Two passes as ONE launch on `stream` (fft_pair_yx_k): the workgroups of `dx` (contiguous in and out: the x pass of one
+ * group of z-planes) next to those of `dy` (contiguous in, strided out, stored with the default cache policy whatever
+ * dy->out_keep says: the y pass of the FOLLOWING group), interleaved in dispatch order.  The two must be independent -- neither
+ * reads or writes what the other writes -- because nothing orders them inside the launch.  Each descriptor keeps its own
+ * scale.  Forward double-precision complex lines without a split, half lines or four-step twiddles, both passes of the same
+ * length: 64, 128, 256, 512 or 1024 points (one shape for both roles, so that neither loses occupancy to the other).  The two bodies are those of the kernels offt_hipk_fft_pass would launch for dy (with out_keep) and dx:
+ * equal bits.  -1, nothing launched: no such kernel (a forced variant, another flavour, another length), a NULL pointer. */
+int offt_hipk_fft_pass_pair(const offt_pass_desc *dy, const void *iny, void *outy, const offt_pass_desc *dx, const void *inx, void *outx,
+                            void *stream);
+/* 1 if offt_hipk_fft_pass_pair has a kernel for (dy, dx); a registry lookup, needs no device */
+int offt_hipk_has_pass_pair(const offt_pass_desc *dy, const offt_pass_desc *dx);
+/* "fft_pair_yx_k", or "no paired kernel" */
+const char *offt_hipk_pair_kernel_name(const offt_pass_desc *dy, const offt_pass_desc *dx);
 /* 1 if the pass, with out_keep set, runs on a kernel whose stores stay cached (otherwise out_keep is ignored)          */
 int offt_hipk_keeps_output(const offt_pass_desc *d);
 /* 1 if a register/LDS Stockham panel kernel exists for (n, precision): powers of two up to 4096

@@ -374,6 +374,9 @@ static struct _offt_comm *comm_build(const struct _offt_plan *po) {
 /* ------------------------------------------------------------------------- */
 /* device state                                                               */
 /* ------------------------------------------------------------------------- */
+/* pipelined plane groups (execute_single, OFFT_HIP_OPT_ZGROUP_PIPELINE): whether a plan starts with them
+ * (profiles/zgroup_pipeline.txt) */
+#define ZGROUP_PIPELINE_DEFAULT 1
 typedef struct hip_state {
   int prec;
   size_t esz;           /* bytes per complex element */
@@ -433,12 +436,16 @@ typedef struct hip_state {
   int variant[3];
   double out_scale;
   int yx_fused;        /* the last single-rank execute alternated launches i and i+1 over groups of planes: i + 1 (0: none) */
+  int yx_pipelined;    /* ... and this many of its launches carried x(group g-1) and y(group g) in one grid (0: plain alternation) */
   void *s_aux, *ev_aux[4]; /* ... with the x launches on this second stream, ordered behind their y launch by these events */
   /* plan-level options (offt_hip_set_option).  The environment variables of the same meaning are read ONCE, in
    * offt_3d_init, as defaults: nothing below depends on the process environment after the plan exists */
   struct {
     int zgroup_mib;      /* single rank: group size of the alternating launches in MiB; 0 = off; -1 = the library's rule */
     int zgroup_streams;  /* ... 2 = consumer launches on a second stream */
+    int zgroup_planes;   /* ... the forward y / x pair of execute_single only: planes per group where it runs in groups at all (> 0) */
+    int zgroup_pipeline; /* ... 1 = x(group g-1) and y(group g) in one grid where the pair has such a kernel (execute_single) */
+    int zgroup_pipeline_set; /* ... and somebody said so (option or environment), see execute_single */
     int slab_chunk_mib;  /* slab schedule: largest z-chunk of the y-transformed volume (Infinity-Cache reuse K2 -> K3) */
     int comm_streams;    /* pencil schedule: 2 = row and column exchanges on separate streams */
     long long min_msg;   /* tiles are merged upwards until a per-peer message has this many bytes */
@@ -507,6 +514,18 @@ static int hb_pass(const offt_pass_desc *d, const void *in, void *out, void *str
 #endif
   int rc = offt_hipk_fft_pass(d, in, out, stream);
   if (rc) SET_ERR("pass n=%d failed: %s", d->n, offt_hipk_last_error());
+  return rc;
+}
+/* offt_hipk_fft_pass_pair: the x pass of one group of planes and the y pass of the next as one launch (execute_single) */
+static int hb_pass_pair(const offt_pass_desc *dy, const void *iny, void *outy, const offt_pass_desc *dx, const void *inx, void *outx, void *stream) {
+  static int log_passes = -1; /* OFFT_LOG_PASSES, as in hb_pass */
+  if (log_passes < 0) log_passes = getenv("OFFT_LOG_PASSES") && atoi(getenv("OFFT_LOG_PASSES"));
+  if (log_passes)
+    fprintf(stderr, "offt-pass-pair %s y: n %d ncols %d nb1 %d x: n %d ncols %d nb1 %d prec %d elems %lld\n", offt_hipk_pair_kernel_name(dy, dx), dy->n,
+            dy->ncols, dy->nb1, dx->n, dx->ncols, dx->nb1, dy->precision,
+            (long long)dy->n * dy->ncols * dy->nb1 * dy->nb2 + (long long)dx->n * dx->ncols * dx->nb1 * dx->nb2);
+  const int rc = offt_hipk_fft_pass_pair(dy, iny, outy, dx, inx, outx, stream);
+  if (rc) SET_ERR("paired pass n=%d, n=%d failed: %s", dy->n, dx->n, offt_hipk_last_error());
   return rc;
 }
 static int hb_prepare(int n, int prec) { return offt_hipk_prepare(n, prec); }
@@ -728,7 +747,7 @@ static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
     hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside,
-    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv, hb_spectrum_shells};
+    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv, hb_spectrum_shells, hb_pass_pair};
 #ifdef OFFT_TEST_SEAMS
 /* the HIP backend without its fused multi-input launch, for offt_hip_test_set_backend: a plan made under it takes the generic
  * route of offt_hip_execute_convolve_sum on the device (tools/conv_probe.py times that route with it) */
@@ -1198,6 +1217,9 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->k1_streams = getenv("OFFT_K1_STREAMS") ? atoi(getenv("OFFT_K1_STREAMS")) : 1;
   st->opt.zgroup_mib = getenv("OFFT_ZGROUP_MIB") ? atoi(getenv("OFFT_ZGROUP_MIB")) : -1;
   st->opt.zgroup_streams = getenv("OFFT_ZGROUP_STREAMS") ? atoi(getenv("OFFT_ZGROUP_STREAMS")) : 1;
+  st->opt.zgroup_planes = getenv("OFFT_ZGROUP_PLANES") ? atoi(getenv("OFFT_ZGROUP_PLANES")) : 0;
+  st->opt.zgroup_pipeline = getenv("OFFT_ZGROUP_PIPELINE") ? atoi(getenv("OFFT_ZGROUP_PIPELINE")) != 0 : ZGROUP_PIPELINE_DEFAULT;
+  st->opt.zgroup_pipeline_set = getenv("OFFT_ZGROUP_PIPELINE") != NULL;
   st->opt.slab_chunk_mib = getenv("OFFT_SLAB_CHUNK_MIB") ? atoi(getenv("OFFT_SLAB_CHUNK_MIB")) : 256;
   st->opt.comm_streams = getenv("OFFT_COMM_STREAMS") ? atoi(getenv("OFFT_COMM_STREAMS")) : 1;
   st->opt.min_msg = getenv("OFFT_MIN_MSG") ? atoll(getenv("OFFT_MIN_MSG")) : 4LL << 20;
@@ -1693,6 +1715,8 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
     case OFFT_HIP_OPT_SPEC_FUSED: st->opt.spec_fused = value != 0; break; /* read by every filtered forward / inverse (spec_fused_route) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
+    case OFFT_HIP_OPT_ZGROUP_PIPELINE: st->opt.zgroup_pipeline = value != 0; st->opt.zgroup_pipeline_set = 1; break;
+    case OFFT_HIP_OPT_ZGROUP_PLANES: st->opt.zgroup_planes = (int)value; break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
     case OFFT_HIP_OPT_K1_STREAMS: st->k1_streams = (int)value; break;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: st->opt.exec_timeout_s = (double)value; break;
@@ -1724,6 +1748,8 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
   switch (option) {
     case OFFT_HIP_OPT_ZGROUP_MIB: return st->opt.zgroup_mib;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: return st->opt.zgroup_streams;
+    case OFFT_HIP_OPT_ZGROUP_PIPELINE: return st->opt.zgroup_pipeline;
+    case OFFT_HIP_OPT_ZGROUP_PLANES: return st->opt.zgroup_planes;
     case OFFT_HIP_OPT_F32_PAIRS: return st->opt.f32_pairs;
     case OFFT_HIP_OPT_HALF_R2C: return st->opt.half_r2c;
     case OFFT_HIP_OPT_HALF_MIXED: return st->opt.half_mixed;
@@ -1761,6 +1787,8 @@ int offt_hip_last_passes_paired(const struct _offt_plan *po) {
   if (!st->yx_fused) return 0;
   return (1 << st->pass_slot[st->yx_fused - 1]) | (1 << st->pass_slot[st->yx_fused]);
 }
+/* how many launches of the last single-rank execute carried two passes (0: none, the pair alternated or ran as plain launches) */
+int offt_hip_last_pipelined_launches(const struct _offt_plan *po) { return ((const hip_state *)po->hip_state)->yx_pipelined; }
 void offt_hip_last_pass_seconds(const struct _offt_plan *po, double t[3]) {
   const hip_state *st = (const hip_state *)po->hip_state;
   t[0] = st->pass_s[0]; t[1] = st->pass_s[1]; t[2] = st->pass_s[2];
@@ -2029,8 +2057,29 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
   st->yx_fused = 0;
   const int ia = ss.pair, ib = ia + 1, cnt = ss.planes; /* producer and consumer launch; planes the two share */
   int ng = 0;
+  /* The forward z-y-x pair again: x(group g-1) and y(group g) touch different planes, so ONE launch can carry both
+   * (be->pass_pair, fft_pair_yx_k) and the pair becomes  y(0) | {x(0), y(1)} | ... | {x(G-2), y(G-1)} | x(G-1):  G + 1 launches
+   * instead of 2 G, half the boundaries at which the chip drains and refills.  The groups keep their size: smaller ones came
+   * out slower here too (profiles/zgroup_pipeline.txt).  Every dependence (x(g) on y(g)) still crosses a launch boundary of
+   * the one stream.
+   * OFFT_HIP_OPT_ZGROUP_PIPELINE; taken where the launcher has a paired kernel for the two descriptors, never with the
+   * second stream.  A table installed through offt_hip_test_set_backend may have been written before pass_pair existed and
+   * be SHORTER than offt_backend (tests/test_single_rank_launches.py installs a copy of the first 23 entries): the entry of
+   * such a table is read only for a plan whose option somebody set. */
+  int pipelined = 0;
+  if (st->opt.zgroup_pipeline && (be->pass == hb_pass || st->opt.zgroup_pipeline_set) && ia == 1 && ss.zyx && dir <= 0 && st->esz == 16 && !st->half_pruned && st->opt.zgroup_streams < 2 && be->pass_pair &&
+      ss.d[ia].nb1 == cnt &&
+      ss.d[ib].nb1 == cnt && cnt >= 1) {
+    offt_pass_desc da = ss.d[ia];
+    da.out_keep = 1;
+    pipelined = be->pass != hb_pass || offt_hipk_has_pass_pair(&da, &ss.d[ib]);
+  }
+  st->yx_pipelined = 0;
   if (ia >= 0 && ss.d[ia].nb1 == cnt && ss.d[ib].nb1 == cnt && !ss.d[ia].real_input)
     ng = plane_group(st, ss.plane_elems, cnt, ss.d[ia].n, ss.d[ib].n, &ss.d[ia]);
+  /* OFFT_HIP_OPT_ZGROUP_PLANES: the size of this pair's groups in planes, where the rule above has groups at all (it turns
+   * nothing on: OFFT_HIP_OPT_ZGROUP_MIB = 0 stays off), for groups finer than a MiB count can say; no other call reads it */
+  if (ng >= 1 && st->opt.zgroup_planes > 0 && ia == 1 && ss.zyx && dir <= 0) ng = st->opt.zgroup_planes > cnt ? cnt : st->opt.zgroup_planes;
   if (ng >= 1) {
     /* OFFT_ZGROUP_STREAMS=2: consumer launches on a second stream (then 128 MiB groups do as well as 256 MiB on one stream).
      * The consumer of a group runs on a second stream behind its producer, so that the next group's producer fills the
@@ -2052,10 +2101,27 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
       offt_pass_desc da = ss.d[ia], db = ss.d[ib];
       da.nb1 = g; db.nb1 = g;
       da.out_keep = 1;
+      if (pipelined && z0 > 0) {
+        /* the middle launches: y of this group next to x of the one before (which has ng planes: only the last can be short) */
+        const int zp = z0 - ng;
+        db.nb1 = ng;
+        if (be->pass_pair(&da, (const char *)ss.src[ia] + (size_t)z0 * (size_t)da.in_b1_stride * st->esz,
+                          (char *)ss.dst[ia] + (size_t)z0 * (size_t)da.out_b1_stride * st->esz, &db,
+                          (const char *)ss.src[ib] + (size_t)zp * (size_t)db.in_b1_stride * st->esz,
+                          (char *)ss.dst[ib] + (size_t)zp * (size_t)db.out_b1_stride * st->esz, s))
+          return -1;
+        st->yx_pipelined++;
+        db.nb1 = g;
+      }
       const char *sa = (const char *)ss.src[ia] + (size_t)z0 * (size_t)da.in_b1_stride * st->esz;
       char *oa = (char *)ss.dst[ia] + (size_t)z0 * (size_t)da.out_b1_stride * st->esz;
       const char *sb = (const char *)ss.src[ib] + (size_t)z0 * (size_t)db.in_b1_stride * st->esz;
       char *ob = (char *)ss.dst[ib] + (size_t)z0 * (size_t)db.out_b1_stride * st->esz;
+      if (pipelined) { /* prologue y(0); epilogue x(G-1) */
+        if (z0 == 0 && be->pass(&da, sa, oa, s)) return -1;
+        if (z0 + g >= cnt && be->pass(&db, sb, ob, s)) return -1;
+        continue;
+      }
       if (be->pass(&da, sa, oa, s)) return -1;
       if (aux) {
         be->event_record(st->ev_aux[k & 3], s);

@@ -700,6 +700,7 @@ struct Env {
   const bool bluestein_long_pow2 = num("OFFT_BLUESTEIN_LONG_POW2", 0) != 0;  // ... on M = 2^k only, not the shortest (64 | 32) x L
   const bool r2c_bluestein = num("OFFT_R2C_BLUESTEIN", 1) != 0;          // real lines of a Bluestein length through scratch (0: any-length kernel)
   const int mix_threads = num("OFFT_MIX_THREADS", 0);                    // workgroup size of the any-length kernel (64 .. 1024), 0 = by LDS footprint
+  const int pair_run = num("OFFT_PAIR_RUN", 0);                           // fft_pair_yx_k: blocks per run of one role (a power of two >= 8), 0 = one period of the XCD order
 };
 const Env &env() { static const Env e; return e; }
 
@@ -715,6 +716,7 @@ void build_registry() {
   reg_pow2_f64();
   reg_pow2_f64_1024();
   reg_pow2_f64_anysplit();
+  reg_pair_yx_f64();
   reg_pow2_f32();
   reg_pow2_f32_big();
   reg_pow2_f32_anysplit();
@@ -2036,6 +2038,74 @@ int offt_hipk_fft_pass(const offt_pass_desc *d, const void *in, void *out, void 
     case Via::AnyLength: return launch_any_length(d, in, out, tb, (hipStream_t)stream);
   }
   return -1;
+}
+
+// ---- two passes in one grid (offt_hipk.h) ----
+namespace {
+// the fft_pair_yx_k entry for (dy, dx), or nullptr; *vy, *vx: the entries the two descriptors resolve to on their own (dy with
+// out_keep), whose bodies the pair entry must carry
+Variant *pick_pair(const offt_pass_desc *dy, const void *iny, const void *outy, const offt_pass_desc *dx, const void *inx, const void *outx,
+                   Variant **vy, Variant **vx) {
+  if (!dy || !dx) return nullptr;
+  auto plain = [](const offt_pass_desc *d) {
+    return d->precision == OFFT_PREC_F64 && d->direction < 0 && d->n >= 1 && d->ncols >= 1 && d->nb1 >= 1 && d->nb2 >= 1 && !d->half && !d->real_input &&
+           !d->tw4 && !d->in_split && !d->in_split_nfloor && !d->out_split && !d->out_split_nfloor && d->in_contig;
+  };
+  if (!plain(dy) || !plain(dx) || dy->out_contig || !dx->out_contig || dx->out_keep) return nullptr;
+  offt_pass_desc ky = *dy;
+  ky.out_keep = 1;
+  const Route ry = resolve(&ky, iny, outy), rx = resolve(dx, inx, outx);
+  if (ry.via != Via::Panel || rx.via != Via::Panel) return nullptr;
+  auto body = [](const Variant *v, bool keep) { return v->key.role == Role::Plain && v->key.keep == keep && !v->mixed && !v->modfn; };
+  if (!body(ry.v, true) || !body(rx.v, false)) return nullptr;
+  Variant *p = find_variant(VariantKey{dy->n, OFFT_PREC_F64, true, false, Role::PairYX, true, 0}, dx->n);
+  if (!p || p->id != dx->n) return nullptr;
+  // (equal lengths only, so one shape: the elements per thread of both bodies are the entry's too)
+  if (dy->n != dx->n || p->e != ry.v->e || p->e != rx.v->e || p->pair_y_id != ry.v->id || p->pair_x_id != rx.v->id || p->cols != ry.v->cols ||
+      p->pair_x_cols != rx.v->cols || p->threads != ry.v->threads || p->threads != rx.v->threads || p->lds < ry.v->lds || p->lds < rx.v->lds)
+    return nullptr;
+  *vy = ry.v; *vx = rx.v;
+  return p;
+}
+}  // namespace
+
+int offt_hipk_has_pass_pair(const offt_pass_desc *dy, const offt_pass_desc *dx) {
+  Variant *vy, *vx;
+  return pick_pair(dy, nullptr, nullptr, dx, nullptr, nullptr, &vy, &vx) != nullptr;
+}
+
+const char *offt_hipk_pair_kernel_name(const offt_pass_desc *dy, const offt_pass_desc *dx) {
+  Variant *vy, *vx;
+  const Variant *p = pick_pair(dy, nullptr, nullptr, dx, nullptr, nullptr, &vy, &vx);
+  return p ? p->kernel : "no paired kernel";
+}
+
+int offt_hipk_fft_pass_pair(const offt_pass_desc *dy, const void *iny, void *outy, const offt_pass_desc *dx, const void *inx, void *outx,
+                            void *stream) {
+  Variant *vy, *vx;
+  Variant *p = pick_pair(dy, iny, outy, dx, inx, outx, &vy, &vx);
+  if (!p || !iny || !outy || !inx || !outx) {
+    snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass_pair: no paired kernel for these descriptors (n=%d and n=%d)", dy ? dy->n : 0, dx ? dx->n : 0);
+    return -1;
+  }
+  Tables ty, tx;
+  if (get_tables(dy->n, dy->precision, ty, false) || get_tables(dx->n, dx->precision, tx, false)) return -1;
+  PassArgs ay = pass_args(dy, p->cols), ax = pass_args(dx, p->pair_x_cols);
+  const long long nyb = (long long)ay.ncp * dy->nb1 * dy->nb2, nxb = (long long)ax.ncp * dx->nb1 * dx->nb2;
+  if (nyb + nxb > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass_pair: grid too large"); return -1; }
+  // each role keeps the XCD-aware order of a launch of its own; a run of one role is a whole period of that order (8 XCDs
+  // times G panels) unless OFFT_PAIR_RUN says otherwise
+  xcd_order(nyb, &ay.xcd_lim, &ay.xcd_gshift);
+  xcd_order(nxb, &ax.xcd_lim, &ax.xcd_gshift);
+  unsigned run_shift = 3u + (env().xcd_remap > 0 ? ax.xcd_gshift : 0u);
+  if (env().pair_run >= 8 && is_pow2(env().pair_run)) run_shift = (unsigned)log2i(env().pair_run);
+  const long long least = nxb < nyb ? nxb : nyb;
+  unsigned nx = (unsigned)nxb, both = (unsigned)((least >> run_shift) << run_shift);
+  unsigned total_lim = 0, total_gshift = 0;  // (launch() works out the order of the whole grid: no role uses it)
+  void *args[] = {(void *)&ay, (void *)&iny, (void *)&outy, (void *)&ty.full, (void *)&ax, (void *)&inx, (void *)&outx, (void *)&tx.full,
+                  (void *)&nx, (void *)&both, (void *)&run_shift};
+  return launch("offt_hipk_fft_pass_pair", p->fn, nullptr, &p->attr_set, p->lds, p->lds, p->threads, nyb + nxb, &total_lim, &total_gshift, args,
+                (hipStream_t)stream);
 }
 
 }  // extern "C"

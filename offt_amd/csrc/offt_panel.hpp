@@ -283,10 +283,11 @@ __device__ __forceinline__ int padidx(int i) {
 //        compile time on either side -- no predicate, no address arithmetic for the skipped half.  The two real ends
 //        of a half-box chain (fft_half_r2c_panel_k, fft_half_c2r_panel_k): R2C with bit 1 -- the reals n >= N/2 of a row
 //        are zero and not loaded; C2R with bit 2 -- the reals n >= N/2 of a row are not stored
+//   blk  the workgroup's index in the pass's grid: blockIdx.x, except in a launch that carries two passes (fft_pair_yx_k)
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool INC, bool OUTC, bool SPLIT, bool R2C, bool KEEP, bool TW4,
           bool C2R, int HALF = 0>
 __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::type *in, typename vec2<T>::type *out,
-                                           const typename vec2<T>::type *twq) {
+                                           const typename vec2<T>::type *twq, const unsigned blk = blockIdx.x) {
   using V2 = typename vec2<T>::type;
   using S = typename lanes<T>::scalar;
   constexpr int NL = lanes<T>::n;   // memory columns per lane (2: column pairs)
@@ -326,7 +327,7 @@ __device__ __forceinline__ void panel_body(PassArgs a, const typename vec2<T>::t
   }
 
   // panel -> (column panel, b1, b2)
-  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const unsigned bid = panel_of_block(blk, a.xcd_lim, a.xcd_gshift);
   const int cp = bid % (unsigned)a.ncp;
   const unsigned rest = bid / (unsigned)a.ncp;
   const int b1 = rest % (unsigned)a.nb1;
@@ -2413,6 +2414,8 @@ enum class Role {
             // and their panelx twins
   FiltFwd,  // forward x pass with the filter on its stores, in place (offt_hipk_filt_pass_fwd): fft_filt_fwd_panel_k
   FiltInv,  // inverse x pass with the filter on its loads, src -> dst (offt_hipk_filt_pass_inv): fft_filt_inv_panel_k
+  PairYX,   // two passes in one grid (offt_hipk_fft_pass_pair): fft_pair_yx_k, the x pass of one group of planes next to the y pass
+            // of the next.  key.n is the y length, the entry's id the x length.
 };
 // column-pair instances (T = f32x2) are kept under their own precision so that the one-column variants and their ids stay
 // what they were
@@ -2454,6 +2457,9 @@ struct Variant {
   bool full_table;
   const char *kernel;  // the __global__ template it is an instance of ("<pairs>" appended for T = f32x2)
   std::string name;
+  // Role::PairYX only: the two plain entries whose bodies the kernel carries -- the KEEP contig-in / strided-out one of key.n
+  // (its shape is cols, threads, e above) and the contig / contig one of the x length -- by registry id, and the x body's columns
+  int pair_y_id = -1, pair_x_id = -1, pair_x_cols = 0;
 };
 // id of the fft_panelx_k instance a power-of-two length keeps for per-peer splits fft_panel_k cannot address
 // (uneven, or not a power of two: grids split over 3, 6, ... ranks)
@@ -2742,6 +2748,7 @@ void reg_variantx_conv_sum() {
 void reg_pow2_f64();
 void reg_pow2_f64_1024();
 void reg_pow2_f64_anysplit();
+void reg_pair_yx_f64();
 void reg_pow2_f32();
 void reg_pow2_f32_big();
 void reg_pow2_f32_anysplit();
