@@ -137,7 +137,8 @@ int offt_hip_convolve_sum_fused(const struct _offt_plan *po);
  * 1 <= nout <= OFFT_HIP_CONV_MAX_OUT.
  * With scale 1, inverse_filtered(forward_filtered(x, H1), [H2]) equals offt_hip_execute_convolve(x, H1 . H2) to rounding.
  * On one rank, in the z-y-x layout, with a power-of-two x extent from 64 to 1024 and no half box, the x pass carries the
- * multiply where OFFT_HIP_OPT_SPEC_FUSED is set (off by default); every other plan transforms and multiplies in separate launches.  Stream, async,
+ * multiply where OFFT_HIP_OPT_SPEC_FUSED is set (off by default), and with OFFT_HIP_OPT_SPEC_MIXED set as well also with a mixed-radix x
+ * extent that has a filtered kernel pair; every other plan transforms and multiplies in separate launches.  Stream, async,
  * offt_hip_last_device_seconds and OFFT_HIP_OPT_ZGROUP_MIB are honoured as in offt_hip_execute_convolve_multi.
  * Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and offt_hip_last_error(), and nothing launched,
  * for a NULL or host-memory argument, a bad nout, two equal outs entries, an unknown filter_kind, a backend without the
@@ -259,6 +260,13 @@ int offt_hip_wait(struct _offt_plan *po);
                                           per group of its y / x launches where they run in groups at all -- it turns nothing on, and
                                           OFFT_HIP_OPT_ZGROUP_MIB = 0 stays off; > 0 takes the place of the MiB count, 0 (default) =
                                           that count decides.  For groups finer than a MiB (OFFT_ZGROUP_PLANES) */
+#define OFFT_HIP_OPT_SPEC_MIXED 21     /* filtered forward / inverse on a plan whose x extent is no power of two: 1 = together with
+                                          OFFT_HIP_OPT_SPEC_FUSED (both set) the x pass carries the multiply where that extent has a
+                                          mixed-radix filtered kernel pair (96, 192, 320, 384, 640, 768, 1000 points in double, 384, 640,
+                                          768, 1000 in single precision; complex and r2c plans, one rank, the z-y-x layout, no half
+                                          box), 0 (default) = such a plan transforms and multiplies in separate launches.  Alone it
+                                          changes nothing.  Read by every filtered call; the results agree to rounding
+                                          (OFFT_SPEC_MIXED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -175,7 +175,10 @@ typedef struct offt_filter_desc {
    * the in-place launch does not look at it.  Bit 3 (value 4) = such a length may run the multi-input gather kernel
    * (fft_conv_sum_panelx_k, fft_conv_sum_half_panelx_k, the same lengths; offt_hipk_conv_pass_sum; plan option
    * OFFT_HIP_OPT_CONV_SUM_MIXED): it too counts only together with bit 1 ((mixed & 5) == 5), and no other launch looks at
-   * it.  A power-of-two length resolves to the same kernel whatever the field says. */
+   * it.  Bit 4 (value 8) = a line length without a power-of-two filtered kernel may run on the mixed-radix filtered kernels
+   * (fft_filt_fwd_panelx_k, fft_filt_inv_panelx_k, the same lengths; plan option OFFT_HIP_OPT_SPEC_MIXED): it stands alone
+   * (it needs none of bits 1-3), only offt_hipk_filt_pass_fwd and offt_hipk_filt_pass_inv read it, and bits 1-3 mean
+   * nothing to those two.  A power-of-two length resolves to the same kernel whatever the field says. */
   int mixed;
   long long axis_stride, col_stride, b1_stride, b2_stride;
 } offt_filter_desc;
@@ -249,7 +252,9 @@ int offt_hipk_pointwise_sum(int nin, const void *const *ins, const void *const *
  * halves of offt_hipk_conv_pass as launches of their own, for a caller whose state is a spectrum ----
  * `d` is the x pass of a forward transform: contiguous complex lines (in_contig, in_axis_stride 1, no split, no half lines),
  * addressed through its in_* side on both launches; `f` addresses the filter like that pass's output, axis stride 1.
- * Power-of-two lines of 64 ... 1024 points, each with a cache-keeping twin (d->out_keep).
+ * Power-of-two lines of 64 ... 1024 points, each with a cache-keeping twin (d->out_keep); with bit 4 of f->mixed also the
+ * mixed-radix lengths listed at offt_filter_desc::mixed, whose instances have no cache-keeping twin (d->out_keep is ignored
+ * there); without that bit such a length finds no kernel, whatever bits 1-3 say.
  * offt_hipk_filt_pass_fwd: data = H . FFT(data) . d->scale along the lines, forward (exp(-i...)), in place.
  * offt_hipk_filt_pass_inv: dst = d->scale . IFFT(H . src) along the lines, unnormalised inverse (exp(+i...)) whatever
  * d->direction says, stored at the offsets it loaded from; `src` is not written unless dst == src, which is allowed.
@@ -258,7 +263,8 @@ int offt_hipk_filt_pass_fwd(const offt_pass_desc *d, const offt_filter_desc *f, 
 int offt_hipk_filt_pass_inv(const offt_pass_desc *d, const offt_filter_desc *f, const void *filter, const void *src, void *dst, void *stream);
 /* 1 if BOTH launches have a kernel for (d, f); the registry lookup needs no device */
 int offt_hipk_filt_has_fused(const offt_pass_desc *d, const offt_filter_desc *f);
-/* "fft_filt_fwd_panel_k" / "fft_filt_inv_panel_k", or "no fused kernel" */
+/* "fft_filt_fwd_panel_k" / "fft_filt_inv_panel_k", with bit 4 of f->mixed at a mixed-radix length "fft_filt_fwd_panelx_k" /
+ * "fft_filt_inv_panelx_k", or "no fused kernel" */
 const char *offt_hipk_filt_fwd_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f);
 const char *offt_hipk_filt_inv_kernel_name(const offt_pass_desc *d, const offt_filter_desc *f);
 /* ---- shell-binned power and cross spectra (offt_hip_spectrum_shells) ----

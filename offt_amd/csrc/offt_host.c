@@ -463,6 +463,8 @@ typedef struct hip_state {
                             kernels too (bit 3 of offt_filter_desc::mixed), 0 = such a length takes the generic route */
     int spec_fused;      /* filtered forward / inverse: 1 = the fused route (the x pass carries the multiply) where the plan has one
                           * (spec_fused_route), 0 = transform and multiply as separate launches (OFFT_HIP_OPT_SPEC_FUSED) */
+    int spec_mixed;      /* filtered forward / inverse: 1 = together with spec_fused the fused route may run on the mixed-radix
+                          * kernels (bit 4 of offt_filter_desc::mixed), 0 = such an x extent takes the generic route */
     int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -1231,6 +1233,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.conv_multi_mixed = getenv("OFFT_CONV_MULTI_MIXED") && atoi(getenv("OFFT_CONV_MULTI_MIXED")) != 0;
   st->opt.conv_sum_mixed = getenv("OFFT_CONV_SUM_MIXED") && atoi(getenv("OFFT_CONV_SUM_MIXED")) != 0;
   st->opt.spec_fused = getenv("OFFT_SPEC_FUSED") ? atoi(getenv("OFFT_SPEC_FUSED")) != 0 : OFFT_SPEC_FUSED_DEFAULT;
+  st->opt.spec_mixed = getenv("OFFT_SPEC_MIXED") && atoi(getenv("OFFT_SPEC_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
   st->opt.block_pad = getenv("OFFT_BLOCK_PAD") && atoi(getenv("OFFT_BLOCK_PAD")) != 0;
@@ -1713,6 +1716,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
     case OFFT_HIP_OPT_CONV_MULTI_MIXED: st->opt.conv_multi_mixed = value != 0; break; /* read by every multi-output convolve (conv_fused_route, CONV_OOP) */
     case OFFT_HIP_OPT_CONV_SUM_MIXED: st->opt.conv_sum_mixed = value != 0; break; /* read by every multi-input convolve (conv_fused_route, CONV_SUM) */
     case OFFT_HIP_OPT_SPEC_FUSED: st->opt.spec_fused = value != 0; break; /* read by every filtered forward / inverse (spec_fused_route) */
+    case OFFT_HIP_OPT_SPEC_MIXED: st->opt.spec_mixed = value != 0; break; /* likewise */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_PIPELINE: st->opt.zgroup_pipeline = value != 0; st->opt.zgroup_pipeline_set = 1; break;
@@ -1758,6 +1762,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_CONV_MULTI_MIXED: return st->opt.conv_multi_mixed;
     case OFFT_HIP_OPT_CONV_SUM_MIXED: return st->opt.conv_sum_mixed;
     case OFFT_HIP_OPT_SPEC_FUSED: return st->opt.spec_fused;
+    case OFFT_HIP_OPT_SPEC_MIXED: return st->opt.spec_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
     case OFFT_HIP_OPT_P2P_TIMEOUT_S: return (long long)st->opt.p2p_timeout_s;
@@ -3259,7 +3264,8 @@ static int conv_fused_route(struct _offt_plan *po, const single_sched *fw, const
 
 /* The fused route of the two filtered calls (the two halves of a convolve as calls of their own, for a caller whose state is
  * a spectrum): one rank, the z-y-x layout, no half box, both backend entries and a kernel pair for the x extent (powers of
- * two from 64 to 1024), OFFT_HIP_OPT_SPEC_FUSED set.  *fd and *fl as above, from the forward's x pass.  0: the generic route. */
+ * two from 64 to 1024; with OFFT_HIP_OPT_SPEC_MIXED, bit 4 of offt_filter_desc::mixed, also the mixed-radix lengths that have
+ * one), OFFT_HIP_OPT_SPEC_FUSED set.  *fd and *fl as above, from the forward's x pass.  0: the generic route. */
 static int spec_fused_route(struct _offt_plan *po, const single_sched *fw, int kind, offt_pass_desc *fd, offt_filter_desc *fl) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_pass_desc *l = &fw->d[2];
@@ -3269,6 +3275,7 @@ static int spec_fused_route(struct _offt_plan *po, const single_sched *fw, int k
   if (fw->src[2] != fw->dst[2] || l->out_axis_stride != l->in_axis_stride || l->out_col_stride != l->in_col_stride ||
       l->out_b1_stride != l->in_b1_stride || l->out_b2_stride != l->in_b2_stride)
     return 0;
+  if (st->opt.spec_mixed) fl->mixed |= 8; /* (spec_fused holds here: the option counts only together with it) */
   return offt_hipk_filt_has_fused(fd, fl);
 }
 

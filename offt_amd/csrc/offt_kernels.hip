@@ -743,6 +743,8 @@ void build_registry() {
   reg_conv_sum_f32();
   reg_spec_f64();
   reg_spec_f32();
+  reg_spec_mixed_f64();
+  reg_spec_mixed_f32();
   reg_half_f64();
   reg_half_f32();
   reg_half_real_f64();
@@ -2197,7 +2199,7 @@ Variant *pick_conv(const offt_pass_desc *d, const offt_filter_desc *f, bool keep
   if (d->half && d->half != 3) return nullptr;  // half lines: loads and stores together, or not at all
   if (d->half && keep && !oop) return nullptr;  // (no cache-keeping twin of the in-place half-line kernels)
   Variant *v = find_variant(VariantKey{d->n, d->precision, true, true, oop ? Role::ConvOop : Role::Conv, keep, d->half});
-  if (v && v->mixed && (oop ? (f->mixed & 3) != 3 : !f->mixed)) return nullptr;
+  if (v && v->mixed && (oop ? (f->mixed & 3) != 3 : !(f->mixed & 7))) return nullptr;  // (bit 4 is the filtered launches' alone)
   return v;
 }
 const char *conv_kernel_name(const Variant *v) { return v ? v->kernel : "no fused kernel"; }
@@ -2285,10 +2287,14 @@ int pointwise_launch(const char *who, const void *in, void *out, bool oop, const
   return 0;
 }
 
-// the filtered-forward (inv = false) or filtered-inverse instance for (d, f), or nullptr: full lines, power-of-two lengths only
+// the filtered-forward (inv = false) or filtered-inverse instance for (d, f), or nullptr: full lines.  The power-of-two
+// lengths whatever f->mixed says; the mixed-radix instances (fft_filt_fwd_panelx_k, fft_filt_inv_panelx_k, no keeping twin)
+// only with bit 4 of f->mixed, which stands alone: bits 1-3 mean nothing here
 Variant *pick_filt(const offt_pass_desc *d, const offt_filter_desc *f, bool keep, bool inv) {
   if (!whole_lines(d, f) || d->half) return nullptr;
-  return find_variant(VariantKey{d->n, d->precision, true, true, inv ? Role::FiltInv : Role::FiltFwd, keep, 0});
+  Variant *v = find_variant(VariantKey{d->n, d->precision, true, true, inv ? Role::FiltInv : Role::FiltFwd, keep, 0});
+  if (v && v->mixed && !(f->mixed & 8)) return nullptr;
+  return v;
 }
 
 // offt_hipk_filt_pass_fwd (inv = false: (a, f, data, filter, twq)) and offt_hipk_filt_pass_inv ((a, f, src, dst, filter, twq))

@@ -2132,6 +2132,223 @@ fft_conv_oop_half_panelx_k(PassArgs a, ConvArgs f, const typename vec2<T>::type 
   convx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, src, dst, filter, twt);
 }
 
+// Filtered forward and filtered inverse of whole lines of a mixed-radix length (offt_hipk_filt_pass_fwd and
+// offt_hipk_filt_pass_inv with bit 4 of offt_filter_desc::mixed): convx_body cut in two, the way filt_body is conv_body cut in
+// two.  Contiguous complex lines, no split, no half lines, addressing through the load side, convx_body's thread mapping and
+// predicates: a butterfly that is off neither loads the filter nor stores.
+//   INV = false (fft_filt_fwd_panelx_k): load, forward stages, H[n] times the register that holds output index n in the last
+//     stage's order, scale, store where the line came from.  In place.
+//   INV = true (fft_filt_inv_panelx_k): load from `src`, H[n] loaded with the element's own index and multiplied in the load
+//     distribution, conjugate, the stages, conjugate, scale, store to `dst` at the same offsets.  `src` is not written unless
+//     dst == src (a workgroup owns whole lines and has loaded all of them before its first exchange, i.e. before any store).
+// No round trip through the exchange image: there is only one half.  Filter values are read once: non-temporal.
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT, bool INV>
+__device__ __forceinline__ void filtx_body(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst,
+                                           const void *filter, const typename vec2<T>::type *twt) {
+  using V2 = typename vec2<T>::type;
+  using Cfg = PanelXCfg<N, TPL, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int NT = Cfg::NT, NSTAGE = Cfg::NSTAGE, LSTRIDE = Cfg::LSTRIDE, EMAX = Cfg::EMAX;
+  constexpr int PADDIV = Cfg::PADDIV;
+  static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
+  static_assert(smooth235(R0) && smooth235(R1) && smooth235(R2), "radices must be products of primes <= 13, or primes <= 31");
+  static_assert(R0 <= 32 && R1 <= 32 && R2 <= 32, "register radix <= 32");
+  static_assert(NSTAGE > 1, "the twiddle table is staged for the exchanges");
+  static_assert(Cfg::QUARTER, "quarter-wave twiddle table: N is a multiple of 4");
+  constexpr int RL = NSTAGE == 3 ? R2 : R1;  // radix of the last stage
+  constexpr int NBF0 = N / R0, NB0 = cdiv(NBF0, TPL);  // butterflies per line / per thread, first stage
+  constexpr int NBFL = N / RL, NBL = cdiv(NBFL, TPL);  // ... last stage
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T *exs = reinterpret_cast<T *>(smem);
+  V2 *exv = reinterpret_cast<V2 *>(smem);
+  V2 *tw = reinterpret_cast<V2 *>(smem + Cfg::TW_OFF);
+
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Cfg::QT; i += NT) tw[i] = twt[i];  // (visible after the first exchange's barrier)
+  auto pad = [](int i) {
+    if constexpr (Cfg::SWZ) return i ^ ((i / R0) & 15);
+    else if constexpr (PADDIV > 0) return i + i / PADDIV;
+    else return i;
+  };
+
+  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const int cp = bid % (unsigned)a.ncp;
+  const unsigned rest = bid / (unsigned)a.ncp;
+  const int b1 = rest % (unsigned)a.nb1;
+  const int b2 = rest / (unsigned)a.nb1;
+  const int c0 = cp * COLS;
+  const int j = tid % TPL, c = tid / TPL;
+  const bool valid = (c0 + c) < a.ncols;
+  const long long lo = (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + c) * a.in_col;
+  const V2 *line = src + lo;
+  V2 *sline = dst + lo;
+  const long long fb = (long long)b1 * f.b1 + (long long)b2 * f.b2 + (long long)(c0 + c) * f.col;
+  // butterfly u of a stage with NBF butterflies per line is live for this thread (compile-time true but for the last one)
+  auto live0 = [&](int u) { return (u + 1) * TPL <= NBF0 || j + u * TPL < NBF0; };
+  auto liveL = [&](int u) { return (u + 1) * TPL <= NBFL || j + u * TPL < NBFL; };
+  auto at = [&](int i) { return c * LSTRIDE + pad(i); };
+
+  // x times H at line index n (a lane that is off multiplies by zero and stores nothing)
+  auto times_h = [&](cx<T> x, int n, bool on, auto complex_filter) {
+    const long long off = fb + (long long)n * f.axis;
+    if constexpr (decltype(complex_filter)::value) {
+      V2 h;
+      h.x = 0; h.y = 0;
+      if (on) h = gload(reinterpret_cast<const V2 *>(filter) + off);
+      return cx<T>{x.x * h.x - x.y * h.y, x.x * h.y + x.y * h.x};
+    } else {
+      T h = 0;
+      if (on) h = __builtin_nontemporal_load(reinterpret_cast<const T *>(filter) + off);
+      return cx<T>{x.x * h, x.y * h};
+    }
+  };
+
+  cx<T> v[EMAX];
+
+  static_for<0, NB0 * R0>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+    const int n = j + u * TPL + t * NBF0;
+    V2 val;
+    val.x = 0; val.y = 0;
+    if (valid && live0(u)) val = gload(line + (long long)n * a.in_axis);
+    v[decltype(ii)::value] = cx<T>{val.x, val.y};
+  });
+  if constexpr (INV) {
+    // H in the load distribution, then conjugated (the inverse as conj(F(conj(.))))
+    auto filt = [&](auto complex_filter) {
+      static_for<0, NB0 * R0>([&](auto ii) {
+        constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+        const int n = j + u * TPL + t * NBF0;
+        const cx<T> x = times_h(v[decltype(ii)::value], n, valid && live0(u), complex_filter);
+        v[decltype(ii)::value] = cx<T>{x.x, -x.y};
+      });
+    };
+    if (f.cplx) filt(std::true_type{});
+    else filt(std::false_type{});
+  }
+
+  // the forward stages of panelx_body (contiguous / contiguous), ending in the last stage's register order:
+  // v[u RL + perm_mixed(RL, t)] holds line index j + u TPL + t N/RL
+  static_for<0, NSTAGE>([&](auto sidx) {
+    constexpr int s = decltype(sidx)::value;
+    constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
+    constexpr int Ns = (s == 0) ? 1 : ((s == 1) ? R0 : R0 * R1);
+    constexpr int NBF = N / R;
+    constexpr int NB = cdiv(NBF, TPL);
+    if constexpr (s > 0) {
+      constexpr int M = N / (Ns * R);
+      static_for<0, NB>([&](auto uu) {
+        constexpr int u = decltype(uu)::value;
+        const int q = j + u * TPL;
+        const int km = (q % Ns) * M;
+        static_for<1, R>([&](auto tt) {
+          constexpr int t = decltype(tt)::value;
+          const int e = km * t;            // <= (Ns-1)(R-1)M < N, also for a predicated-off butterfly
+          const int qd = e / (N / 4);
+          const V2 w = tw[e - qd * (N / 4)];
+          T cr = (qd & 1) ? w.y : w.x;     // times (-i)^qd
+          T ci = (qd & 1) ? -w.x : w.y;
+          if (qd & 2) { cr = -cr; ci = -ci; }
+          const cx<T> x = v[u * R + t];
+          v[u * R + t] = cx<T>{x.x * cr - x.y * ci, x.x * ci + x.y * cr};
+        });
+      });
+    }
+    static_for<0, NB>([&](auto uu) { dft_mixed<T, R, false>(&v[decltype(uu)::value * R]); });
+    if constexpr (s < NSTAGE - 1) {
+      constexpr int Rn = (s == 0) ? R1 : R2;
+      constexpr int NBFn = N / Rn, NBn = cdiv(NBFn, TPL);
+      auto wr_idx = [&](int u, int t) {
+        const int q = j + u * TPL;
+        const int k = q % Ns;
+        return at((q - k) * R + k + t * Ns);
+      };
+      auto wr_live = [&](int u) { return (u + 1) * TPL <= NBF || j + u * TPL < NBF; };
+      auto rd_idx = [&](int u, int t) { return at(j + u * TPL + t * NBFn); };
+      auto rd_live = [&](int u) { return (u + 1) * TPL <= NBFn || j + u * TPL < NBFn; };
+      if constexpr (s > 0) __syncthreads();  // previous exchange's reads done
+      if constexpr (SPLIT) {
+        static_for<0, NB * R>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+          constexpr int from = u * R + perm_mixed(R, t);
+          if (wr_live(u)) exs[wr_idx(u, t)] = v[from].x;
+        });
+        __syncthreads();
+        T re[NBn * Rn];
+        static_for<0, NBn * Rn>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+          re[decltype(ii)::value] = rd_live(u) ? exs[rd_idx(u, t)] : (T)0;
+        });
+        __syncthreads();
+        static_for<0, NB * R>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+          constexpr int from = u * R + perm_mixed(R, t);
+          if (wr_live(u)) exs[wr_idx(u, t)] = v[from].y;
+        });
+        __syncthreads();
+        static_for<0, NBn * Rn>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+          v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], rd_live(u) ? exs[rd_idx(u, t)] : (T)0};
+        });
+      } else {
+        static_for<0, NB * R>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+          constexpr int from = u * R + perm_mixed(R, t);
+          const cx<T> x = v[from];
+          V2 w; w.x = x.x; w.y = x.y;
+          if (wr_live(u)) exv[wr_idx(u, t)] = w;
+        });
+        __syncthreads();
+        static_for<0, NBn * Rn>([&](auto ii) {
+          constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+          V2 w; w.x = 0; w.y = 0;
+          if (rd_live(u)) w = exv[rd_idx(u, t)];
+          v[decltype(ii)::value] = cx<T>{w.x, w.y};
+        });
+      }
+    }
+  });
+
+  // the last stage's order: forward times H[n] at the output index; inverse conjugated back; scale; store
+  const T sc = (T)a.scale;
+  auto store_all = [&](auto complex_filter) {
+    static_for<0, NBL * RL>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int from = u * RL + perm_mixed(RL, t);
+      const int n = j + u * TPL + t * NBFL;
+      const bool on = valid && liveL(u);
+      cx<T> x = v[from];
+      V2 w;
+      if constexpr (INV) {
+        w.x = x.x * sc;
+        w.y = -x.y * sc;
+      } else {
+        x = times_h(x, n, on, complex_filter);
+        w.x = x.x * sc;
+        w.y = x.y * sc;
+      }
+      if (on) gstore(sline + (long long)n * a.in_axis, w);
+    });
+  };
+  if (!INV && f.cplx) store_all(std::true_type{});
+  else store_all(std::false_type{});
+}
+
+// (bounded like fft_conv_panelx_k: one transform plus the filter values needs no more registers than the fused convolve --
+// the VGPR table is in DESIGN.md 4.5)
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_filt_fwd_panelx_k(PassArgs a, ConvArgs f, typename vec2<T>::type *data, const void *filter, const typename vec2<T>::type *twt) {
+  filtx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, false>(a, f, data, data, filter, twt);
+}
+
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__(TPL * COLS, (convx_wps<T, N, TPL, R0, R1, R2, COLS, SPLIT>()))
+fft_filt_inv_panelx_k(PassArgs a, ConvArgs f, const typename vec2<T>::type *src, typename vec2<T>::type *dst, const void *filter,
+                      const typename vec2<T>::type *twt) {
+  filtx_body<T, N, TPL, R0, R1, R2, COLS, SPLIT, true>(a, f, src, dst, filter, twt);
+}
+
 // Multi-input spectral convolution of whole lines of a mixed-radix length (offt_hipk_conv_pass_sum with bits 1 and 3 of
 // offt_filter_desc::mixed): to convx_body what conv_sum_body is to conv_body -- its first half in a loop over the inputs.
 // Per workgroup, for k = 0 ... nin-1: load the panel from src[k] (convx_body's loads), forward stages, times H_k in the last
@@ -2412,8 +2629,8 @@ enum class Role {
   ConvOop,  // ... with a separate store base (offt_hipk_conv_pass_oop): fft_conv_oop_panel_k, fft_conv_oop_half_panel_k, ...
   ConvSum,  // several sources summed into one destination (offt_hipk_conv_pass_sum): fft_conv_sum_panel_k, fft_conv_sum_half_panel_k
             // and their panelx twins
-  FiltFwd,  // forward x pass with the filter on its stores, in place (offt_hipk_filt_pass_fwd): fft_filt_fwd_panel_k
-  FiltInv,  // inverse x pass with the filter on its loads, src -> dst (offt_hipk_filt_pass_inv): fft_filt_inv_panel_k
+  FiltFwd,  // forward x pass with the filter on its stores, in place (offt_hipk_filt_pass_fwd): fft_filt_fwd_panel_k, fft_filt_fwd_panelx_k
+  FiltInv,  // inverse x pass with the filter on its loads, src -> dst (offt_hipk_filt_pass_inv): fft_filt_inv_panel_k, fft_filt_inv_panelx_k
   PairYX,   // two passes in one grid (offt_hipk_fft_pass_pair): fft_pair_yx_k, the x pass of one group of planes next to the y pass
             // of the next.  key.n is the y length, the entry's id the x length.
 };
@@ -2744,6 +2961,17 @@ void reg_variantx_conv_sum() {
               "fft_conv_sum_half_panelx_k", " multi-input convolution on half lines");
 }
 
+// filtered forward and filtered inverse at a mixed-radix length (fft_filt_fwd_panelx_k, fft_filt_inv_panelx_k;
+// offt_reg_spec_mixed_*.hip; picked only with bit 4 of offt_filter_desc::mixed): full lines, no cache-keeping twin
+template <typename T, int N, int TPL, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variantx_spec() {
+  const VariantShape s = panelx_shape<T, N, TPL, R0, R1, R2, COLS, SPLIT>();
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::FiltFwd, false, 0}, s, (const void *)fft_filt_fwd_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_filt_fwd_panelx_k", " filtered forward");
+  add_variant(VariantKey{N, prec_of<T>(), true, true, Role::FiltInv, false, 0}, s, (const void *)fft_filt_inv_panelx_k<T, N, TPL, R0, R1, R2, COLS, SPLIT>,
+              "fft_filt_inv_panelx_k", " filtered inverse");
+}
+
 // instantiation groups (offt_reg_*.hip)
 void reg_pow2_f64();
 void reg_pow2_f64_1024();
@@ -2775,6 +3003,8 @@ void reg_conv_sum_mixed_f64();
 void reg_conv_sum_mixed_f32();
 void reg_spec_f64();
 void reg_spec_f32();
+void reg_spec_mixed_f64();
+void reg_spec_mixed_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();

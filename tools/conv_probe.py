@@ -42,7 +42,8 @@ second plan made under the HIP backend with filt_pass_fwd / filt_pass_inv withhe
 the caller's route built from calls that predate the two (offt_3d_execute + offt_hipk_pointwise; offt_hipk_pointwise_oop +
 offt_3d_execute_dir(+1)).  The three ALTERNATE after a warm-up, MIXED_REPS times each, and a line reports min and median of
 all three, the ratios against both, each baseline's own spread (median / min - 1) and the byte model of DESIGN.md 4.5
-(104 / 136).
+(104 / 136).  The fused side has OFFT_HIP_OPT_SPEC_FUSED and OFFT_HIP_OPT_SPEC_MIXED set, so an x length that is no power of
+two (768, 1000) measures the mixed-radix filtered kernels.
 A spec with the prefix shells: measures offt_hip_spectrum_shells (the power spectrum, every shell, with counts) on a plan's
 output block filled with random numbers, next to the in-place REAL offt_hipk_pointwise sweep over the same block (40 B per
 point in double precision against the call's 16 B).  The two ALTERNATE after a warm-up, MIXED_REPS times each, device time by
@@ -58,6 +59,7 @@ usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:|shells:][
         the sum:mixed: set of profiles/conv_sum_mixed.txt: sum:mixed:768 sum:mixed:f32:768 sum:mixed:1000 sum:mixed:f32:1000
         sum:mixed:half:768;
         the spec: set of profiles/spec_filtered.txt: spec:512 spec:f32:512 spec:1024 spec:f32:1024 spec:r2c:512 spec:r2c:f32:512;
+        the spec: set of profiles/spec_filtered_mixed.txt: spec:768 spec:f32:768 spec:1000 spec:f32:1000 spec:r2c:768;
         the shells: set of profiles/spectrum_shells.txt: shells:512 shells:f32:512 shells:r2c:512 shells:r2c:f32:512 shells:1024
         shells:f32:1024 shells:r2c:1024 shells:r2c:f32:1024)"""
 import ctypes as C
@@ -190,6 +192,7 @@ def probe_spec(rest, zg):
             T.offt_hip_set_option(po, OPT_ZGROUP_MIB, zg)
     po = plans["fused"]
     T.offt_hip_set_option(po, api.OPT_SPEC_FUSED, 1)
+    T.offt_hip_set_option(po, api.OPT_SPEC_MIXED, 1)  # (an x length that is no power of two; a power of two does not read it)
     stream = torch.cuda.Stream()  # one stream for both plans, the caller's multiply and the timing events
     for p in plans.values():
         T.offt_hip_set_stream(p, stream.cuda_stream)
