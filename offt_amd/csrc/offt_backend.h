@@ -126,6 +126,11 @@ void offt_hip_test_set_p2p(offt_test_peer_open_fn fn, offt_test_hook_fn hook);
 /* p1 of the plan whose exchange is in progress on this thread: with it a transport maps (which, group member) to a
  * world rank -- which 1 = row group (rank_x * p2 + member), 2 = column group (member * p2 + rank_y), 0 = world   */
 int offt_hip_test_current_p1(void);
+/* 1 if `po` does not use the direct-store exchange, or if all of that exchange's state -- peer mappings, flag groups, slot
+ * counters, per-block tables -- was made for the buffers the plan holds now; 0 (reason in offt_hip_last_error()) if any of
+ * it describes buffers that were rebuilt since */
+struct _offt_plan;
+int offt_hip_test_p2p_consistent(const struct _offt_plan *po);
 
 #ifdef __cplusplus
 }

@@ -140,7 +140,7 @@ static world_state G_proc = {0, 1, 0, 0, NULL, 0};
 
 static int is_device_ptr(const void *p);
 static int world_max(struct _offt_plan *po, double *v);
-static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _offt_params *custom);
+static int static_sweep(struct _offt_plan *po, void *user_buf, const struct _offt_params *custom);
 struct hip_state;
 static void slab_teardown(struct hip_state *st);
 static void inv_cache_drop(struct hip_state *st);
@@ -429,6 +429,8 @@ typedef struct hip_state {
   void *recv1_base;      /* pencil schedule: the recv1 ring as ONE allocation (one mapping per peer) */
   long long *tab_p1, **tab_pr, *tab_p2; /* per-block base tables into the peers' volumes: slab K1, pencil K1 per ring slot, pencil K2 */
   unsigned long long epoch, *use1, tiles2, bar1, bar2; /* flag values: transforms done, uses of each ring slot, tiles sent in exchange 2, barriers */
+  int use1_n;            /* entries of use1 and of tab_pr: the ring p2p_open saw (st->ring moves on when the ring is rebuilt) */
+  unsigned long long buf_gen, p2p_gen; /* buf_gen counts slab_setup / ring_setup; p2p_gen: its value when p2p_open mapped the buffers */
   unsigned long long *p2p_status; /* host-visible: a wait kernel gave up */
   ncclComm_t comm1, comm2; int have_comm1, have_comm2;
   void *stage; size_t stage_bytes;
@@ -618,30 +620,46 @@ void offt_hip_test_set_p2p(offt_test_peer_open_fn fn, offt_test_hook_fn hook) { 
 /* map the group members' allocations (offt_backend::peer_open): hipIpc handles, gathered with the group's own exchange
  * primitive (64 bytes to and from every member), opened with peer access enabled on first use.  What the reference gets
  * from MPI for free -- the library moves the packed blocks -- becomes an address the packing kernel can store to. */
+static int wait_compute_ex(hip_state *st, int watch);
 static int hb_peer_open(void *ctx, int which, int n, int self, void *local, size_t bytes, void **peers) {
   hip_state *st = (hip_state *)ctx;
   if (g_test_peer_open) return g_test_peer_open(which, n, self, local, bytes, peers);
   (void)bytes;
   const size_t HB = sizeof(hipIpcMemHandle_t);
-  hipIpcMemHandle_t mine;
+  hipIpcMemHandle_t mine, none;
   char *d = NULL, *h = (char *)malloc(2 * HB * (size_t)n);
-  int rc = -1;
+  /* The exchange of the handles is collective, so like mesh_setup this keeps the local result in rc and goes through the
+   * exchange whatever it is: a rank that has nothing to offer (local == NULL: an earlier step of p2p_open failed here) or
+   * cannot export it sends a ZEROED handle and maps nothing; its peers see the zeroed handle and fail as well.  Only a rank
+   * that cannot even stage the handles stays away -- its peers' wait below is bounded. */
+  int rc = 0;
+  memset(&none, 0, HB);
+  mine = none;
+  for (int a = 0; a < n; a++) peers[a] = NULL;
   if (!h) return -1;
-  if (hipIpcGetMemHandle(&mine, local) != hipSuccess) { (void)hipGetLastError(); goto out; }
-  if (hipMalloc((void **)&d, 2 * HB * (size_t)n) != hipSuccess) { (void)hipGetLastError(); d = NULL; goto out; }
+  if (!local) rc = -1;
+  else if (hipIpcGetMemHandle(&mine, local) != hipSuccess) {
+    SET_ERR("hipIpcGetMemHandle for group %d failed: %s", which, hipGetErrorString(hipGetLastError()));
+    mine = none; rc = -1;
+  }
+  if (hipMalloc((void **)&d, 2 * HB * (size_t)n) != hipSuccess) { (void)hipGetLastError(); d = NULL; rc = -1; goto out; }
   for (int a = 0; a < n; a++) memcpy(h + (size_t)a * HB, &mine, HB);
   memset(h + HB * (size_t)n, 0, HB * (size_t)n);
-  if (hipMemcpy(d, h, 2 * HB * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) goto out;
+  if (hipMemcpy(d, h, 2 * HB * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) { rc = -1; goto out; }
   {
     const void *sp[n]; void *rp[n]; size_t sb[n], rb[n]; int pr[n];
     for (int a = 0; a < n; a++) { pr[a] = a; sp[a] = d + (size_t)a * HB; rp[a] = d + (size_t)(n + a) * HB; sb[a] = rb[a] = HB; }
-    if (hb_a2a(st, which, n, pr, sp, sb, rp, rb, st->s_compute)) goto out;
-    if (hipStreamSynchronize((hipStream_t)st->s_compute) != hipSuccess) goto out;
+    if (hb_a2a(st, which, n, pr, sp, sb, rp, rb, st->s_compute)) { rc = -1; goto out; }
+    /* bounded and error-polling, like world_max: a member that never joins must not hold the others for ever */
+    if (wait_compute_ex(st, !g_test_transport && G.have_comm)) { rc = -1; goto out; }
   }
-  if (hipMemcpy(h, d, 2 * HB * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) goto out;
-  rc = 0;
-  for (int a = 0; a < n; a++) peers[a] = NULL;
-  for (int a = 0; a < n; a++) {
+  if (hipMemcpy(h, d, 2 * HB * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { rc = -1; goto out; }
+  for (int a = 0; a < n && !rc; a++)
+    if (a != self && !memcmp(h + (size_t)(n + a) * HB, &none, HB)) {
+      SET_ERR("group %d member %d has nothing to map", which, a);
+      rc = -1;
+    }
+  for (int a = 0; a < n && !rc; a++) {
     if (a == self) { peers[a] = local; continue; }
     hipIpcMemHandle_t hm;
     memcpy(&hm, h + (size_t)(n + a) * HB, HB);
@@ -854,8 +872,11 @@ static int p2p_group_open(hip_state *st, p2p_group *g, int which, int n, int sel
   const size_t bytes = sizeof(unsigned long long) * (size_t)nslots * (size_t)n;
   g->flags = (unsigned long long *)be->flag_alloc(bytes, 0);
   g->pflags = (unsigned long long **)calloc((size_t)n, sizeof(void *));
-  if (!g->flags || !g->pflags) return -1;
-  return be->peer_open(st, which, n, self, g->flags, bytes, (void **)g->pflags);
+  /* (collective: a rank whose allocation failed still takes part in the mapping and offers nothing, see p2p_open) */
+  void *none[n];
+  const int have = g->flags && g->pflags;
+  const int rc = be->peer_open(st, which, n, self, have ? g->flags : NULL, bytes, have ? (void **)g->pflags : none);
+  return have ? rc : -1;
 }
 /* flag words: slot-major, one word per sender */
 static int p2p_signal(hip_state *st, const p2p_group *g, int slot, unsigned long long value, void *stream) {
@@ -895,8 +916,9 @@ static void p2p_teardown(hip_state *st) {
   if (st->g2.flags || st->g2.pflags) p2p_group_close(st, &st->g2);
   be->dfree(st->tab_p1); st->tab_p1 = NULL;
   be->dfree(st->tab_p2); st->tab_p2 = NULL;
-  if (st->tab_pr) { for (int r = 0; r < st->ring; r++) be->dfree(st->tab_pr[r]); free(st->tab_pr); st->tab_pr = NULL; }
-  free(st->use1); st->use1 = NULL;
+  /* (use1_n, not st->ring: the ring may have been rebuilt with another size since these were made) */
+  if (st->tab_pr) { for (int r = 0; r < st->use1_n; r++) be->dfree(st->tab_pr[r]); free(st->tab_pr); st->tab_pr = NULL; }
+  free(st->use1); st->use1 = NULL; st->use1_n = 0;
   be->flag_free(st->p2p_status, 1); st->p2p_status = NULL;
   st->p2p = 0;
 }
@@ -944,6 +966,7 @@ static int ring_setup(struct _offt_plan *po, hip_state *st) {
   const offt_backend *be = st->be;
   const struct _offt_comm *c = po->comm;
   const size_t min_msg = (size_t)st->opt.min_msg;
+  st->buf_gen++;
   /* phase 1: x-tiles of T1 planes, W1 + 1 ring slots.  Unless the caller fixed T1 the tile is merged upwards until a
    * per-peer message of exchange 1 is at least 4 MiB (the reference's M1/16 was sized for CPU caches and MPI eager limits) */
   st->T = po->params->v[_T1_];
@@ -1048,6 +1071,7 @@ static void mesh_teardown(hip_state *st) {
 }
 
 static int p2p_open(struct _offt_plan *po, hip_state *st);
+static int p2p_attach(struct _offt_plan *po, hip_state *st, int rc_local);
 static int mesh_setup(struct _offt_plan *po, hip_state *st) {
   const struct _offt_comm *c = po->comm;
   const int p1 = c->p1, p2 = c->p2;
@@ -1087,25 +1111,53 @@ static int mesh_setup(struct _offt_plan *po, hip_state *st) {
     }
     st->uses_rccl = st->x1 || st->x2;
   }
-  if (st->p2p) {
-    /* map the peers' volumes (collective).  Every rank first learns whether every rank has its buffers; afterwards
-     * whether every rank could map every peer -- if not, ALL ranks fall back to the staged exchange together. */
-    double bad = rc_local ? 1.0 : 0.0;
-    if (world_max(po, &bad) || bad > 0.0) return -1;
-    bad = p2p_open(po, st) ? 1.0 : 0.0;
-    if (world_max(po, &bad)) return -1;
-    if (bad > 0.0) {
-      if (!po->rank) fprintf(stderr, "offt(hip): direct-store exchange not available here (%s); using the staged RCCL exchange\n", g_err);
-      const int want = st->want_p2p;
-      mesh_teardown(st);
-      st->want_p2p = 0;
-      const int rc = mesh_setup(po, st);
-      st->want_p2p = want;
-      return rc;
-    }
-    st->uses_rccl = 0; /* the communicators were only needed to hand the mappings round */
-  }
+  if (st->p2p) return p2p_attach(po, st, rc_local);
   return rc_local;
+}
+
+/* The collective half of the direct-store exchange, behind every (re)build of the buffers it maps (mesh_setup, retile):
+ * map the peers' volumes.  Every rank first learns whether every rank has its buffers (`rc_local`: this rank's result of
+ * building them); afterwards whether every rank could map every peer -- if not, ALL ranks fall back to the staged exchange
+ * together (p2p_open itself never leaves its collective steps early, whatever happens on one rank). */
+static int p2p_attach(struct _offt_plan *po, hip_state *st, int rc_local) {
+  double bad = rc_local ? 1.0 : 0.0;
+  if (world_max(po, &bad) || bad > 0.0) return -1;
+  bad = p2p_open(po, st) ? 1.0 : 0.0;
+  if (world_max(po, &bad)) return -1;
+  if (bad > 0.0) {
+    if (!po->rank) fprintf(stderr, "offt(hip): direct-store exchange not available here (%s); using the staged RCCL exchange\n", g_err);
+    const int want = st->want_p2p;
+    mesh_teardown(st);
+    st->want_p2p = 0;
+    const int rc = mesh_setup(po, st);
+    st->want_p2p = want;
+    return rc;
+  }
+  st->uses_rccl = 0; /* the communicators were only needed to hand the mappings round */
+  return rc_local;
+}
+
+/* Rebuild the exchange volumes of the mesh in use for another tiling (po->params: T1 / W1 / T2) -- what the static sweep does
+ * between two points.  With the direct-store exchange the peers hold mappings of exactly these volumes, and the tables, flag
+ * groups and slot counters are sized for them: all of it is closed BEFORE anything is freed and made again afterwards, with
+ * the agreement of mesh_setup (a rank that cannot map sends the whole world back to the staged exchange, for the rest of the
+ * sweep: a plan that has fallen back is rebuilt as a staged one from then on).  Collective in that case: the sweep is, every
+ * rank visits the same points in the same order, so the world_max / peer_open calls in here line up across the ranks. */
+static int retile(struct _offt_plan *po, hip_state *st) {
+  const int p2p = st->p2p;
+  p2p_teardown(st);
+  st->p2p = p2p; /* (p2p_teardown clears it; the setups below shape their buffers for the exchange in use) */
+  /* every rank has closed its mappings before any rank frees what they map.  (The result is not needed: a world that cannot
+   * agree here cannot agree in p2p_attach's first step either, and that one is returned.) */
+  if (p2p) { double none = 0.0; (void)world_max(po, &none); }
+  int rc;
+  if (st->slab_zyx) { slab_teardown(st); rc = slab_setup(po, st); }
+  else { ring_teardown(st); rc = ring_setup(po, st); }
+  /* Non-zero from p2p_attach's first step (a rank could not rebuild its buffers) leaves st->p2p = 1 with NOTHING mapped:
+   * the buffers have the direct-store shape (no send side), so the flag stays, and no execute may run on this state.  The
+   * sweep keeps to that: sweep_time_point runs no point whose rc is non-zero, the next retile starts from p2p_teardown, and
+   * a failed LAST rebuild fails the plan (static_sweep's return value). */
+  return p2p ? p2p_attach(po, st, rc) : rc;
 }
 
 /* map what the packing passes store into and build their per-block tables (see the p2p block above) */
@@ -1113,48 +1165,117 @@ static int p2p_open(struct _offt_plan *po, hip_state *st) {
   const offt_backend *be = st->be;
   const struct _offt_comm *c = po->comm;
   const int p1 = c->p1, p2 = c->p2, rx = po->rank / p2, ry = po->rank % p2;
+  /* Up to four collective peer_open calls: the flags of group 1, R1 / the recv1 ring, the flags of group 2, recv2.  Like
+   * mesh_setup this keeps the local result in rc and makes EVERY one of them on every rank whatever it is -- a rank that left
+   * at its first failure would pair its next collective (the caller's world_max) with its peers' next peer_open.  A rank
+   * whose local step failed offers nothing (local = NULL: a zeroed handle) and maps nothing; the tables, which are local,
+   * are made only where everything before them worked.  The accumulated result is returned afterwards. */
+  int rc = 0;
   st->p2p_status = (unsigned long long *)be->flag_alloc(sizeof(unsigned long long), 1);
-  if (!st->p2p_status) return -1;
+  if (!st->p2p_status) rc = -1;
   st->epoch = st->tiles2 = st->bar1 = st->bar2 = 0;
+  st->p2p_gen = st->buf_gen;
   if (st->x1) {
     /* group 1 = the row group (p2 members; the whole world on a 1 x p mesh).  Slots: READY and FREE per ring slot (the slab
      * schedule has one "slot", its receive volume), then one barrier slot for the mirrored inverse */
     const int ring = st->slab_zyx ? 1 : st->ring;
-    if (p2p_group_open(st, &st->g1, 1, p2, ry, 2 * ring + 1)) return -1;
+    if (p2p_group_open(st, &st->g1, 1, p2, ry, 2 * ring + 1)) rc = -1;
     st->use1 = (unsigned long long *)calloc((size_t)ring, sizeof(unsigned long long));
+    st->use1_n = ring;
     st->peer_r1 = (void **)calloc((size_t)p2, sizeof(void *));
-    if (!st->use1 || !st->peer_r1) return -1;
-    if (st->slab_zyx) {
-      const size_t bytes = (st->slab_yc ? st->sBc * st->sH : st->sblkS * st->sNt) * p2 * st->esz;
-      if (be->peer_open(st, 1, p2, ry, st->R1, bytes, st->peer_r1)) return -1;
+    const size_t slot = ((st->blk1 * p2 * st->esz + 255) / 256) * 256;
+    void *mine = st->slab_zyx ? st->R1 : st->recv1_base, *none[p2];
+    const size_t bytes = st->slab_zyx ? (st->slab_yc ? st->sBc * st->sH : st->sblkS * st->sNt) * p2 * st->esz : slot * (size_t)ring;
+    const int have = st->use1 && st->peer_r1 && mine;
+    if (be->peer_open(st, 1, p2, ry, have ? mine : NULL, bytes, have ? st->peer_r1 : none) || !have) rc = -1;
+    if (!rc && st->slab_zyx) {
       st->tab_p1 = st->slab_yc ? tab_peers(st, p2, st->sH, (long long)st->sBc, ry, st->peer_r1, st->R1)
                                : tab_peers(st, p2, 1, (long long)st->sblkS, ry, st->peer_r1, st->R1);
-      if (!st->tab_p1) return -1;
-    } else {
-      const size_t slot = ((st->blk1 * p2 * st->esz + 255) / 256) * 256;
-      if (be->peer_open(st, 1, p2, ry, st->recv1_base, slot * (size_t)st->ring, st->peer_r1)) return -1;
-      st->tab_pr = (long long **)calloc((size_t)st->ring, sizeof(long long *));
-      if (!st->tab_pr) return -1;
-      for (int r = 0; r < st->ring; r++) {
+      if (!st->tab_p1) rc = -1;
+    } else if (!rc) {
+      st->tab_pr = (long long **)calloc((size_t)ring, sizeof(long long *));
+      if (!st->tab_pr) rc = -1;
+      for (int r = 0; r < ring && !rc; r++) {
         void *pr[p2];
         for (int a = 0; a < p2; a++) pr[a] = (char *)st->peer_r1[a] + (size_t)r * slot;
         st->tab_pr[r] = tab_peers(st, p2, 1, (long long)st->blk1, ry, pr, st->recv1[r]);
-        if (!st->tab_pr[r]) return -1;
+        if (!st->tab_pr[r]) rc = -1;
       }
     }
   }
   if (st->x2) {
     /* group 2 = the column group (p1 members).  Slots: READY (tiles sent so far), FREE (transforms consumed), barrier */
-    if (p2p_group_open(st, &st->g2, 2, p1, rx, 3)) return -1;
+    if (p2p_group_open(st, &st->g2, 2, p1, rx, 3)) rc = -1;
     st->peer_x2 = (void **)calloc((size_t)p1, sizeof(void *));
-    if (!st->peer_x2) return -1;
-    if (be->peer_open(st, 2, p1, rx, st->recv2, st->blk2 * p1 * st->esz, st->peer_x2)) return -1;
-    const long long stride = (long long)st->blk2;
-    st->tab_p2 = tab_peers(st, p1, 1, stride, rx, st->peer_x2, st->recv2);
-    if (!st->tab_p2) return -1;
+    void *none[p1];
+    const int have = st->peer_x2 && st->recv2;
+    if (be->peer_open(st, 2, p1, rx, have ? st->recv2 : NULL, st->blk2 * p1 * st->esz, have ? st->peer_x2 : none) || !have) rc = -1;
+    if (!rc) {
+      st->tab_p2 = tab_peers(st, p1, 1, (long long)st->blk2, rx, st->peer_x2, st->recv2);
+      if (!st->tab_p2) rc = -1;
+    }
   }
-  return 0;
+  return rc;
 }
+
+#ifdef OFFT_TEST_SEAMS
+/* Test seam: 1 if the plan does not use the direct-store exchange, or if every piece of that exchange's state describes the
+ * buffers the plan holds NOW -- the mappings were made after the last (re)build of the buffers, the self entries of the
+ * peer lists are the plan's own receive volumes, flags and slot counters are sized for the ring in use, and the self block of
+ * every per-block table is where tab_peers would put it today.  0 otherwise, with the reason in offt_hip_last_error(). */
+static int tab_entry(const long long *tab, int i, long long *v) {
+  if (g_backend) { *v = tab[i]; return 0; }
+  return hipMemcpy(v, tab + i, sizeof *v, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+#define P2P_STALE(...) do { SET_ERR("direct-store state is stale: " __VA_ARGS__); return 0; } while (0)
+int offt_hip_test_p2p_consistent(const struct _offt_plan *po) {
+  const hip_state *st = (const hip_state *)po->hip_state;
+  const struct _offt_comm *c = po->comm;
+  if (!st->p2p) return 1;
+  const int p1 = c->p1, p2 = c->p2, rx = po->rank / p2, ry = po->rank % p2;
+  if (st->p2p_gen != st->buf_gen) P2P_STALE("buffers rebuilt %llu time(s) since the peers were mapped", st->buf_gen - st->p2p_gen);
+  if (!st->p2p_status) P2P_STALE("no status word");
+  if (st->x1) {
+    const int ring = st->slab_zyx ? 1 : st->ring;
+    const void *mine = st->slab_zyx ? st->R1 : st->recv1_base;
+    if (!st->peer_r1 || !st->g1.flags || !st->g1.pflags || !st->use1) P2P_STALE("exchange 1 is not mapped");
+    if (st->g1.n != p2 || st->g1.self != ry) P2P_STALE("group 1 is %d members, self %d (mesh: %d, %d)", st->g1.n, st->g1.self, p2, ry);
+    if (st->peer_r1[ry] != mine) P2P_STALE("peer_r1[self] %p, receive volume %p", st->peer_r1[ry], mine);
+    if (st->g1.pflags[ry] != st->g1.flags) P2P_STALE("pflags[self] of group 1");
+    if (st->g1.nslots != 2 * ring + 1) P2P_STALE("g1.nslots %d, ring %d", st->g1.nslots, ring);
+    if (st->use1_n != ring) P2P_STALE("use1 has %d entries, ring %d", st->use1_n, ring);
+    long long got = 0;
+    if (st->slab_zyx) {
+      const int nper = st->slab_yc ? st->sH : 1;
+      const long long stride = st->slab_yc ? (long long)st->sBc : (long long)st->sblkS;
+      if (!st->tab_p1) P2P_STALE("no tab_p1");
+      for (int b = ry * nper; b < (ry + 1) * nper; b++) {
+        if (tab_entry(st->tab_p1, b, &got)) P2P_STALE("tab_p1 unreadable");
+        if (got != ((long long)ry * nper + b % nper) * stride) P2P_STALE("tab_p1[%d] %lld, stride %lld", b, got, stride);
+      }
+    } else {
+      const size_t slot = ((st->blk1 * p2 * st->esz + 255) / 256) * 256;
+      if (!st->tab_pr) P2P_STALE("no tab_pr");
+      for (int r = 0; r < ring; r++) {
+        if (st->recv1[r] != (char *)st->recv1_base + (size_t)r * slot) P2P_STALE("ring slot %d is not at %d * slot bytes", r, r);
+        if (!st->tab_pr[r] || tab_entry(st->tab_pr[r], ry, &got)) P2P_STALE("tab_pr[%d] unreadable", r);
+        if (got != (long long)ry * (long long)st->blk1) P2P_STALE("tab_pr[%d][self] %lld, blk1 %zu", r, got, st->blk1);
+      }
+    }
+  }
+  if (st->x2) {
+    long long got = 0;
+    if (!st->peer_x2 || !st->g2.flags || !st->g2.pflags || !st->tab_p2) P2P_STALE("exchange 2 is not mapped");
+    if (st->g2.n != p1 || st->g2.self != rx || st->g2.nslots != 3) P2P_STALE("group 2 is %d members, self %d, %d slots", st->g2.n, st->g2.self, st->g2.nslots);
+    if (st->peer_x2[rx] != st->recv2) P2P_STALE("peer_x2[self] %p, recv2 %p", st->peer_x2[rx], st->recv2);
+    if (st->g2.pflags[rx] != st->g2.flags) P2P_STALE("pflags[self] of group 2");
+    if (tab_entry(st->tab_p2, rx, &got)) P2P_STALE("tab_p2 unreadable");
+    if (got != (long long)rx * (long long)st->blk2) P2P_STALE("tab_p2[self] %lld, blk2 %zu", got, st->blk2);
+  }
+  return 1;
+}
+#undef P2P_STALE
+#endif
 
 static void state_free(hip_state *st) {
   if (!st) return;
@@ -1349,7 +1470,10 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
     printf("offt(hip): W2=%d: only W2 == 0 (blocking) vs W2 != 0 (FFTx overlapped with exchange 2) matters here; the window depth has no effect\n",
            custom_params->v[_W2_]);
   }
-  if (max_loop > 0) static_sweep(po, out, custom_params);
+  if (max_loop > 0 && static_sweep(po, out, custom_params)) {
+    SET_ERR("offt_3d_init: the sweep could not rebuild the buffers of the point it chose");
+    goto fail;
+  }
   po->t_init[INIT_ALL] = wall_seconds() - t0;
   if (!po->rank) { /* offt-compute.c:3469-3471 */
     const struct _offt_comm *c = po->comm;
@@ -1483,8 +1607,9 @@ static void sweep_report(struct _offt_plan *po, double perf) {
   print_params(po->params->v);
 }
 
-static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _offt_params *custom) {
+static int static_sweep(struct _offt_plan *po, void *user_buf, const struct _offt_params *custom) {
   hip_state *st = (hip_state *)po->hip_state;
+  int sweep_rc = 0;
   int *v = po->params->v;
   const double t0 = wall_seconds();
   const char *envdb = getenv("OFFT_SWEEP_DB");
@@ -1496,12 +1621,12 @@ static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _of
   void *buf = NULL;
   int own = 0;
   if (!st->use_pipeline) {
-    if (g_backend) return; /* kernel variants exist on the GPU only */
+    if (g_backend) return 0; /* kernel variants exist on the GPU only */
     buf = user_buf;
     if (!buf || !is_device_ptr(buf)) { /* tune on scratch: never stage a host array per point */
       buf = st->be->dmalloc(local_elems(po->comm) * st->esz);
       own = 1;
-      if (!buf) return;
+      if (!buf) return 0;
       (void)hipMemset(buf, 0, local_elems(po->comm) * st->esz);
     }
     memcpy(best_v, v, sizeof best_v);
@@ -1597,8 +1722,7 @@ static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _of
     st->t1_custom = st->t2_custom = 1;
     v[_T1_] = candT[best_i]; v[_T2_] = candTz[best_i];
     if (best_p1 != v[_P1_]) rc_mesh = mesh_rebuild(po, best_p1);
-    else if (st->slab_zyx) { slab_teardown(st); rc_mesh = slab_setup(po, st); }
-    else { ring_teardown(st); rc_mesh = ring_setup(po, st); }
+    else rc_mesh = retile(po, st);
     /* ---- stage B: tiling at that mesh.  slab: x-tile thickness T1 (message granularity of the exchange) x z-chunk
      * thickness T2 (granularity of the overlapped FFTy/FFTx work); pencil: T1 x W1, then T2 -- around the winner ---- */
     const int M1 = po->comm->M1, M3 = po->comm->M3;
@@ -1615,8 +1739,7 @@ static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _of
         if (st->slab_zyx) {
           if ((zi > 0 && Zc[zi] == Zc[0]) || (zi > 1 && Zc[zi] == Zc[1])) continue;
           v[_T1_] = Tc[ti]; v[_T2_] = Zc[zi];
-          slab_teardown(st);
-          const int rc = slab_setup(po, st) | rc_buf | rc_mesh;
+          const int rc = retile(po, st) | rc_buf | rc_mesh;
           const double perf = sweep_time_point(po, buf, rc);
           points++;
           sweep_report(po, perf);
@@ -1624,8 +1747,7 @@ static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _of
         } else {
           if ((zi > 0 && Wc[zi] == Wc[0]) || (zi > 1 && Wc[zi] == Wc[1])) continue;
           v[_T1_] = Tc[ti]; v[_W1_] = Wc[zi];
-          ring_teardown(st);
-          const int rc = ring_setup(po, st) | rc_buf | rc_mesh;
+          const int rc = retile(po, st) | rc_buf | rc_mesh;
           const double perf = sweep_time_point(po, buf, rc);
           points++;
           sweep_report(po, perf);
@@ -1638,8 +1760,7 @@ static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _of
         if (Zc[zi] == Zc[0] || (zi > 1 && Zc[zi] == Zc[1])) continue;
         memcpy(v, best_v, sizeof best_v);
         v[_T2_] = Zc[zi];
-        ring_teardown(st);
-        const int rc = ring_setup(po, st) | rc_buf | rc_mesh;
+        const int rc = retile(po, st) | rc_buf | rc_mesh;
         const double perf = sweep_time_point(po, buf, rc);
         points++;
         sweep_report(po, perf);
@@ -1647,12 +1768,14 @@ static void static_sweep(struct _offt_plan *po, void *user_buf, const struct _of
       }
     }
     memcpy(v, best_v, sizeof best_v);
-    if (st->slab_zyx) { slab_teardown(st); (void)slab_setup(po, st); }
-    else { ring_teardown(st); (void)ring_setup(po, st); }
+    /* the plan keeps what this last rebuild makes: if it fails on any rank, the plan fails on all of them */
+    double bad = retile(po, st) ? 1.0 : 0.0;
+    if (world_max(po, &bad) || bad > 0.0) sweep_rc = -1;
   }
   po->params->is_converged = 1;
   if (own) st->be->dfree(buf);
   po->t_init[INIT_AH] = wall_seconds() - t0;
+  return sweep_rc;
 }
 
 struct _offt_plan *offt_3d_init(int Nx, int Ny, int Nz, double *in, double *out, int is_r2c, int fftw_flag,
@@ -2438,6 +2561,7 @@ static int slab_setup(struct _offt_plan *po, hip_state *st) {
   const struct _offt_comm *c = po->comm;
   const size_t min_msg = (size_t)st->opt.min_msg;
   int T = po->params->v[_T1_], Tz = po->params->v[_T2_];
+  st->buf_gen++;
   if (T < 1) T = 1;
   if (Tz < 1) Tz = 1;
   if (!st->t1_custom) { int t4 = (c->M1 + 3) / 4; if (T < t4) T = t4; } /* 4 tiles: measured best kernel efficiency */
@@ -3063,6 +3187,9 @@ void offt_3d_execute_dir(struct _offt_plan *po, void *in, void *out, int directi
   if (timed) be->event_record(st->ev1, st->s_compute);
   if (rc) { /* the reference's failure marker, offt-compute.c:3881 */
     if (st->uses_rccl) comm_fail(st); /* peers may already sit in an exchange this rank will never join */
+    /* direct-store exchange: epoch / use1 / tiles2 have advanced for signals that were never sent, so this plan's counters are
+     * out of step with its peers' -- every later call fails at once, as after a flag wait that timed out (wait_compute) */
+    if (st->p2p) G.comm_failed = 1;
     t[ALL] = 99999999.0;
     return;
   }
@@ -3196,6 +3323,7 @@ static int conv_leave(struct _offt_plan *po, double t0, int rc) {
   if (!st->async) st->be->event_record(st->ev1, st->s_compute);
   if (rc) {
     if (st->uses_rccl) comm_fail(st);
+    if (st->p2p) G.comm_failed = 1; /* (flag counters out of step with the peers', see offt_3d_execute_dir) */
     t[ALL] = 99999999.0;
     return -1;
   }

@@ -33,6 +33,25 @@ def main():
             dry = api.offt_3d_init(*case["N"], custom_params=api.make_params(**case["params"]))
             a0 = CB.cpu_backend_alloc_count() - n0
             api.offt_3d_fin(dry)
+            if fa.get("final"):
+                # ... or while the sweep rebuilds the buffers of the point it CHOSE, the last thing init does: count what a plan
+                # WITH the sweep allocates (a fixed mesh and OFFT_SELF_BYPASS=0, so that the count does not depend on which
+                # point wins and the last allocation is a receive volume), then let the last one fail.  The plan must fail on
+                # EVERY rank: nobody may keep a plan whose peers have none.
+                n1 = CB.cpu_backend_alloc_count()
+                api.offt_3d_fin(api.offt_3d_init(*case["N"], custom_params=api.make_params(**case["params"]), max_loop=case["max_loop"]))
+                if rank == fa["rank"]:
+                    CB.cpu_backend_fail_alloc_at(CB.cpu_backend_alloc_count() - n1)
+                try:
+                    cpu_world.run_rank(*case["N"], kind=1, max_loop=case["max_loop"], **case["params"])
+                    failed = ""
+                except RuntimeError as e:
+                    failed = str(e)
+                for k in case.get("env", {}):
+                    os.environ.pop(k, None)
+                json.dump({"init_failed": failed}, open(os.path.join(outdir, f"case{ci}_rank{rank}.json"), "w"))
+                dist.barrier()
+                continue
             if rank == fa["rank"]:
                 CB.cpu_backend_fail_alloc_at(a0 + 2 + fa.get("extra", 0))
         res = cpu_world.run_rank(*case["N"], kind=1, is_equalxy=case.get("eq", 0), is_r2c=case.get("r2c", 0),

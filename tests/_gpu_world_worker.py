@@ -69,10 +69,25 @@ def main():
             # direct-store exchange between PROCESSES: the product's own hipIpc path (handles gathered through the
             # transport above, opened with hipIpcOpenMemHandle) -- the kernels of one process store into another's buffers
             os.environ["OFFT_EXCHANGE"] = "p2p"
-        po = api.offt_3d_init(*shape, custom_params=api.make_params(**case["params"]), is_equalxy=case.get("eq", 0), is_r2c=r2c)
+        if case.get("max_loop"):  # the sweep's point database: not into the working directory
+            os.environ.setdefault("OFFT_SWEEP_DB", os.path.join(outdir, "sweep-db"))
+        po = api.offt_3d_init(*shape, custom_params=api.make_params(**case["params"]), is_equalxy=case.get("eq", 0), is_r2c=r2c,
+                              max_loop=case.get("max_loop", 0))
         os.environ.pop("OFFT_EXCHANGE", None)
         L.offt_hip_get_exchange.argtypes = [C.c_void_p]
+        L.offt_hip_test_p2p_consistent.argtypes = [C.c_void_p]
         exchange = L.offt_hip_get_exchange(po)
+        consistent = []
+
+        def note():
+            # after init and after every execute: does the direct-store state describe the plan's buffers (offt_backend.h)?
+            consistent.append(int(L.offt_hip_test_p2p_consistent(po)))
+            if consistent[-1] != 1:
+                # nothing more runs on mappings of buffers that are gone, and the process leaves AT ONCE: its closed
+                # connections end the other ranks' next exchange, they do not sit out the process group's time-out
+                print("rank %d: %s" % (rank, L.offt_hip_last_error().decode()), flush=True)
+                os._exit(1)
+        note()
         c = api.comm_dict(po)
         v = list(po.contents.params.contents.v)
         dev = torch.zeros(api.local_elems(po) * 2, dtype=torch.float64, device="cuda")
@@ -80,22 +95,25 @@ def main():
         if L.offt_hip_fill_input(po, dev.data_ptr(), 1):
             raise SystemExit("fill failed")
         api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+        note()
         buf = dev.cpu().numpy().view(np.complex128)
         np.save(os.path.join(outdir, f"case{ci}_rank{rank}.npy"), buf)
         for _ in range(case.get("repeat", 0)):  # the same plan again: buffer reuse between transforms
             if L.offt_hip_fill_input(po, dev.data_ptr(), 1):
                 raise SystemExit("fill failed")
             api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+            note()
             if not np.array_equal(dev.cpu().numpy().view(np.complex128), buf):
                 raise SystemExit("repeat: result differs from the first transform")
         if case.get("inv"):
             torch.cuda.synchronize()
             api.offt_3d_execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
+            note()
             import cpu_world
             np.save(os.path.join(outdir, f"case{ci}_rank{rank}_inv.npy"),
                     cpu_world.input_block(c, dev.cpu().numpy().view(np.complex128)))
         api.offt_3d_fin(po)
-        json.dump({"comm": c, "v": v, "exchange": exchange}, open(os.path.join(outdir, f"case{ci}_rank{rank}.json"), "w"))
+        json.dump({"comm": c, "v": v, "exchange": exchange, "consistent": consistent}, open(os.path.join(outdir, f"case{ci}_rank{rank}.json"), "w"))
         dist.barrier()
     L.offt_hip_test_set_transport(None, 0, 1)
     dist.destroy_process_group()

@@ -20,6 +20,12 @@ flag kernels order the streams.  hipIpc cannot open a handle inside the process 
 test seam that hands the threads' pointers round; the hook seam is a barrier among the rank threads before every wait is
 enqueued (offt_backend.h).
 
+The life cycle of that exchange (tests/test_p2p_lifecycle.py): "max_loop": n goes to the plan's init (the static sweep);
+"fail_map": {"rank": r, "call": k} makes rank r's k-th peer_open return non-zero after it has offered its pointer;
+"fail_pass": {"rank": r, "execute": e, "pass": i} (cpu) makes pass i of rank r's execute e fail and notes per execute the
+failure marker, the error text and the backend's launch count.  Every record of summary.json carries "ranks": per rank
+offt_hip_test_p2p_consistent and offt_hip_get_exchange after init and after every execute, the final mesh and tiling.
+
 usage: _thread_world.py <size> <cases.json> <outdir> [gpu|cpu]
 """
 import collections
@@ -33,6 +39,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+# Every rendezvous among the rank threads (a message on the wire, its acknowledgement, the pointers of a peer_open, the hook
+# barrier) waits at most "s" seconds (a case's "rendezvous_s", default 120).  One that runs out of time is a HARD failure of the
+# world -- it is noted here and the process exits 1 --, never a way for ranks that have lost step with each other to meet again.
+RENDEZVOUS = {"s": 120.0, "timed_out": []}
 
 
 class Wire:
@@ -50,9 +62,11 @@ class Wire:
             self.cv.notify_all()
         return ack
 
-    def take(self, key, timeout=120.0):
+    def take(self, key):
         with self.cv:
-            ok = self.cv.wait_for(lambda: self.q[key] or self.failed, timeout)
+            ok = self.cv.wait_for(lambda: self.q[key] or self.failed, RENDEZVOUS["s"])
+            if not ok and not self.failed:
+                RENDEZVOUS["timed_out"].append(("take", key))
             if not ok or self.failed:
                 raise RuntimeError(f"no message on {key}")
             return self.q[key].popleft()
@@ -77,10 +91,13 @@ def main():
     L.offt_hip_test_set_p2p.argtypes = [C.c_void_p, C.c_void_p]
     L.offt_hip_test_set_p2p.restype = None
     L.offt_hip_get_exchange.argtypes = [C.c_void_p]
+    L.offt_hip_test_p2p_consistent.argtypes = [C.c_void_p]
     if cpu:
         torch = None
         CB = cpu_world._cb_lib()
         CB.cpu_backend_set_peer_open.argtypes = [C.c_void_p]
+        CB.cpu_backend_thread_launch_count.restype = C.c_long
+        CB.cpu_backend_thread_fail_pass_at.argtypes = [C.c_long]
     else:
         import torch
         torch.cuda.set_device(0)
@@ -109,7 +126,7 @@ def main():
             L.offt_hip_device_synchronize()  # the plan's streams are non-blocking: finish the copy before releasing
 
     # ---- direct-store exchange seams ----
-    peer_book = {"cv": threading.Condition(), "posted": {}, "count": collections.defaultdict(int)}
+    peer_book = {"cv": threading.Condition(), "posted": {}, "count": collections.defaultdict(int), "calls": collections.defaultdict(int)}
 
     def peer_open(which, npeers, self_idx, local, nbytes, peers):
         """rendezvous of one group's members: everybody posts its pointer, everybody reads the others'"""
@@ -118,13 +135,23 @@ def main():
             p1 = L.offt_hip_test_current_p1()
             members = [cpu_world.group_peer(which, g, rank, size, p1) for g in range(npeers)]
             assert members[self_idx] == rank
-            gid = (which, members[0])
+            gid = (p1, which, members[0])  # (p1: the sweep changes the mesh, and with it who is in which group)
             with peer_book["cv"]:
                 seq = peer_book["count"][(gid, rank)]
                 peer_book["count"][(gid, rank)] += 1
                 peer_book["posted"][(gid, seq, rank)] = (local, nbytes)
                 peer_book["cv"].notify_all()
-                ok = peer_book["cv"].wait_for(lambda: all((gid, seq, m) in peer_book["posted"] for m in members) or wire.failed, 120.0)
+                # "fail_map": this rank's k-th call fails AFTER it has offered its pointer (a handle that arrives and cannot
+                # be opened): the other members get theirs and return 0, this one maps nothing
+                nth = peer_book["calls"][rank]
+                peer_book["calls"][rank] += 1
+                fm = tls.case.get("fail_map")
+                if fm and fm["rank"] == rank and fm["call"] == nth:
+                    return -1
+                ok = peer_book["cv"].wait_for(lambda: all((gid, seq, m) in peer_book["posted"] for m in members) or wire.failed, RENDEZVOUS["s"])
+                if not ok and not wire.failed:
+                    RENDEZVOUS["timed_out"].append(("peer_open", gid, seq, rank))
+                    wire.fail()
                 if not ok or wire.failed:
                     return -1
                 for g, m in enumerate(members):
@@ -139,8 +166,10 @@ def main():
 
     def hook():
         try:
-            hook_bar["b"].wait(120.0)
+            hook_bar["b"].wait(RENDEZVOUS["s"])
         except threading.BrokenBarrierError:
+            if not wire.failed:
+                RENDEZVOUS["timed_out"].append(("hook", tls.rank))
             wire.fail()
 
     peer_cb, hook_cb = PEER_CB(peer_open), HOOK_CB(hook)
@@ -162,7 +191,8 @@ def main():
                         copy(recvp[a], ptr, nb)
                         ack.set()
                 for ack in acks:
-                    if not ack.wait(120.0):
+                    if not ack.wait(RENDEZVOUS["s"]):
+                        RENDEZVOUS["timed_out"].append(("ack", rank))
                         raise RuntimeError("send not consumed")
                 return 0
             except Exception as e:
@@ -211,7 +241,8 @@ def main():
                         box["done"] = new_event(stream)  # the sender's buffer has been read once this event has passed
                         ack.set()
                 for ack, box in acks:
-                    if not ack.wait(120.0):
+                    if not ack.wait(RENDEZVOUS["s"]):
+                        RENDEZVOUS["timed_out"].append(("ack", rank))
                         raise RuntimeError("send not consumed")
                     if hip.hipStreamWaitEvent(stream, box["done"], 0) != 0:  # my send is complete when the receiver has copied
                         raise RuntimeError("wait")
@@ -226,6 +257,16 @@ def main():
     async_cbs = {}
     cpu_a2a = cpu_world.A2A_CB(lambda *a: transports[tls.rank](*a))  # CPU backend: ONE process-wide callback
 
+    lifecycle = {}  # (case, rank) -> what rank_thread notes after init and after every execute
+
+    def execute(po, inp, out):
+        api.offt_3d_execute(po, inp, out)
+        tls.note()
+
+    def execute_dir(po, inp, out, direction):
+        api.offt_3d_execute_dir(po, inp, out, direction)
+        tls.note()
+
     def unseam():
         L.offt_hip_test_set_p2p(None, None)
         if cpu:
@@ -237,6 +278,7 @@ def main():
     def rank_thread(rank, ci, case, bar):
         try:
             tls.rank = rank
+            tls.case = case
             if cpu:
                 L.offt_hip_test_set_backend(CB.cpu_backend_table(), rank, size)
             else:
@@ -247,16 +289,31 @@ def main():
                     async_cbs[rank] = ASYNC_CB(make_async_transport(rank))
                     L.offt_hip_test_set_transport_async(C.cast(async_cbs[rank], C.c_void_p))
             if case.get("p2p"):
-                L.offt_hip_test_set_p2p(C.cast(peer_cb, C.c_void_p), C.cast(hook_cb, C.c_void_p))
+                # ("fail_pass": a rank that fails leaves its schedule early and never reaches the hooks of the waits it skips;
+                # the CPU backend's waits spin on the host and need no such barrier)
+                L.offt_hip_test_set_p2p(C.cast(peer_cb, C.c_void_p), None if case.get("fail_pass") else C.cast(hook_cb, C.c_void_p))
             prec = api.F32 if case.get("f32") else api.F64
             r2c = case.get("r2c", 0)
             po = api.offt_3d_init(*case["N"], custom_params=api.make_params(**case["params"]), is_equalxy=case.get("eq", 0),
-                                  is_r2c=r2c, precision=prec)
+                                  is_r2c=r2c, precision=prec, max_loop=case.get("max_loop", 0))
             c = api.comm_dict(po)
             v = list(po.contents.params.contents.v)
-            if case.get("p2p") and L.offt_hip_get_exchange(po) != 1:
+            # the life cycle of the direct-store exchange, for the tests to assert on: after init and after every execute whether
+            # its state describes the plan's buffers (offt_backend.h) and which exchange is in use; the final mesh and tiling
+            life = lifecycle[(ci, rank)] = {"consistent": [], "exchange": [], "mesh": [c["p1"], c["p2"]], "tiling": [v[api.T1], v[api.W1], v[api.T2]]}
+
+            def note():
+                life["consistent"].append(int(L.offt_hip_test_p2p_consistent(po)))
+                life["exchange"].append(int(L.offt_hip_get_exchange(po)))
+                if life["consistent"][-1] != 1:  # nothing more runs on mappings of buffers that are gone
+                    raise RuntimeError("rank %d: %s" % (rank, L.offt_hip_last_error().decode()))
+            tls.note = note
+            note()
+            if case.get("p2p") and not case.get("fail_map") and L.offt_hip_get_exchange(po) != 1:
                 raise RuntimeError("the plan fell back to the staged exchange")
             ct = np.complex128 if prec == api.F64 else np.complex64
+            if cpu and case.get("fail_pass"):
+                return cpu_fail_pass_rank(rank, ci, case, bar, po, c, v, ct, life)
             if cpu:
                 return cpu_rank(rank, ci, case, bar, po, c, v, ct)
             dev = torch.zeros(api.local_elems(po) * 2, dtype=torch.float64 if prec == api.F64 else torch.float32, device="cuda")
@@ -269,7 +326,7 @@ def main():
                 torch.cuda.synchronize()
                 e_in = float(dev.double().square().sum())
                 bar.wait()
-                api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+                execute(po, dev.data_ptr(), dev.data_ptr())
                 e_out = float(dev.double().square().sum())
                 cv = torch.view_as_complex(dev.view(-1, 2))
                 spots = {}
@@ -285,7 +342,7 @@ def main():
                 results[(ci, rank)] = {"comm": c, "v": v, "e_in": e_in, "e_out": e_out, "spots": spots}
                 return
             bar.wait()
-            api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+            execute(po, dev.data_ptr(), dev.data_ptr())
             res = {"comm": c, "v": v, "out": dev.cpu().numpy().view(ct).copy()}
             for rep_i in range(case.get("repeat", 0)):
                 # the same plan again on OTHER input (buffer reuse between transforms: the FREE flags of the direct-store
@@ -295,13 +352,13 @@ def main():
                     raise RuntimeError("fill failed")
                 dev.mul_(2.0 ** (rep_i + 1))
                 torch.cuda.current_stream().synchronize()  # (this thread's stream only: a device-wide wait would line the ranks up)
-                api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+                execute(po, dev.data_ptr(), dev.data_ptr())
                 again = dev.cpu().numpy().view(ct)
                 if not np.array_equal(again, res["out"] * ct(2.0 ** (rep_i + 1))):
                     raise RuntimeError(f"repeat {rep_i}: result differs from the first transform (times {2 ** (rep_i + 1)})")
             if case.get("inv"):
                 bar.wait()
-                api.offt_3d_execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
+                execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
                 # (dev holds the LAST forward result: the field times 2^repeat)
                 res["inv"] = cpu_world.input_block(c, dev.cpu().numpy().view(ct)) / ct(2.0 ** case.get("repeat", 0))
                 if case.get("repeat"):
@@ -309,11 +366,11 @@ def main():
                         raise RuntimeError("fill failed")
                     dev.mul_(0.5)
                     torch.cuda.current_stream().synchronize()
-                    api.offt_3d_execute(po, dev.data_ptr(), dev.data_ptr())
+                    execute(po, dev.data_ptr(), dev.data_ptr())
                     if not np.array_equal(dev.cpu().numpy().view(ct), res["out"] * ct(0.5)):
                         raise RuntimeError("forward after inverse differs from the first transform (times 1/2)")
                     if case.get("inv") == 2:  # the inverse again, on the same array: the schedule kept from the first one, other data
-                        api.offt_3d_execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
+                        execute_dir(po, dev.data_ptr(), dev.data_ptr(), +1)
                         if not np.array_equal(cpu_world.input_block(c, dev.cpu().numpy().view(ct)), res["inv"] * ct(0.5)):
                             raise RuntimeError("second inverse (kept schedule) differs from the first (times 1/2)")
             bar.wait()
@@ -350,34 +407,59 @@ def main():
         buf = fill()
         ptr = buf.ctypes.data_as(C.c_void_p)
         bar.wait()
-        api.offt_3d_execute(po, ptr, ptr)
+        execute(po, ptr, ptr)
         res = {"comm": c, "v": v, "out": buf.copy()}
         for rep_i in range(case.get("repeat", 0)):
             b2 = fill() * ct(2.0 ** (rep_i + 1))  # other data every time: see the GPU path
             p2 = b2.ctypes.data_as(C.c_void_p)
-            api.offt_3d_execute(po, p2, p2)
+            execute(po, p2, p2)
             if not np.array_equal(b2, res["out"] * ct(2.0 ** (rep_i + 1))):
                 raise RuntimeError(f"repeat {rep_i}: result differs from the first transform (times {2 ** (rep_i + 1)})")
         if case.get("inv"):
             back = buf.copy()
             bp = back.ctypes.data_as(C.c_void_p)
-            api.offt_3d_execute_dir(po, bp, bp, +1)
+            execute_dir(po, bp, bp, +1)
             res["inv"] = cpu_world.input_block(c, back)
             if case.get("inv") == 2:  # once more on the SAME array: the plan replays the schedule it kept from the first inverse
                 back[:] = buf
-                api.offt_3d_execute_dir(po, bp, bp, +1)
+                execute_dir(po, bp, bp, +1)
                 if not np.array_equal(cpu_world.input_block(c, back), res["inv"]):
                     raise RuntimeError("second inverse (kept schedule) differs from the first")
             if case.get("repeat"):
                 b2 = fill()
                 p2 = b2.ctypes.data_as(C.c_void_p)
-                api.offt_3d_execute(po, p2, p2)
+                execute(po, p2, p2)
                 if not np.array_equal(b2, res["out"]):
                     raise RuntimeError("forward after inverse differs from the first transform")
         bar.wait()
         api.offt_3d_fin(po)
         unseam()
         results[(ci, rank)] = res
+
+    def cpu_fail_pass_rank(rank, ci, case, bar, po, c, v, ct, life):
+        """"fail_pass": {"rank": r, "execute": e, "pass": i} -- pass i of rank r's execute e returns -1.  Every rank executes
+        e + 2 times; per execute the failure marker t[ALL], the error text and how many launches (passes, flag operations,
+        exchanges, copies) the backend saw from this rank are noted.  The results are not compared: there are none."""
+        fp = case["fail_pass"]
+        buf = np.zeros(api.local_elems(po), dtype=ct)
+        ptr = buf.ctypes.data_as(C.c_void_p)
+        life["executes"] = []
+        for e in range(fp["execute"] + 2):
+            bar.wait()
+            if rank == fp["rank"] and e == fp["execute"]:
+                CB.cpu_backend_thread_fail_pass_at(fp["pass"] + 1)
+            before, err = CB.cpu_backend_thread_launch_count(), ""
+            try:
+                api.offt_3d_execute(po, ptr, ptr)
+            except RuntimeError as ex:
+                err = str(ex)
+            life["executes"].append({"t_all": float(po.contents.t[api.ALL]), "error": err,
+                                     "launches": CB.cpu_backend_thread_launch_count() - before})
+            tls.note()
+        bar.wait()
+        api.offt_3d_fin(po)
+        unseam()
+        results[(ci, rank)] = {"comm": c, "v": v}
 
     if cpu:
         CB.cpu_backend_set_a2a(cpu_a2a)
@@ -392,6 +474,11 @@ def main():
         hook_bar["b"] = threading.Barrier(size)
         peer_book["posted"].clear()
         peer_book["count"].clear()
+        peer_book["calls"].clear()
+        RENDEZVOUS["s"] = float(case.get("rendezvous_s", 120.0))
+        own_db = bool(case.get("max_loop")) and "OFFT_SWEEP_DB" not in os.environ
+        if own_db:  # the sweep's point database: one per case, and not in the working directory
+            os.environ["OFFT_SWEEP_DB"] = os.path.join(outdir, "sweep-db-%d" % ci)
         th = [threading.Thread(target=rank_thread, args=(r, ci, case, bar)) for r in range(size)]
         for t in th:
             t.start()
@@ -400,6 +487,11 @@ def main():
         for k in case.get("env", {}):
             os.environ.pop(k, None)
         os.environ.pop("OFFT_EXCHANGE", None)
+        if own_db:
+            os.environ.pop("OFFT_SWEEP_DB", None)
+        if RENDEZVOUS["timed_out"]:  # ranks that waited for each other in vain: whatever they computed afterwards
+            print("FAILED rendezvous timed out", RENDEZVOUS["timed_out"], errors, flush=True)
+            sys.exit(1)
         if not cpu:
             torch.cuda.synchronize()
             for ev in garbage:
@@ -411,6 +503,12 @@ def main():
         shape = tuple(case["N"])
         r2c = case.get("r2c", 0)
         f32 = bool(case.get("f32"))
+        ranks = [lifecycle[(ci, r)] for r in range(size)]
+        if case.get("fail_pass"):
+            rec = {"case": case, "mesh": ranks[0]["mesh"], "ranks": ranks}
+            summary.append(rec)
+            print(json.dumps(rec), flush=True)
+            continue
         if case.get("check") == "ramp":
             E = float(np.prod(shape))
             e_in = sum(results[(ci, r)]["e_in"] for r in range(size))
@@ -434,7 +532,7 @@ def main():
                 scale = abs(want) if want else n ** 3 * 111 * (n - 1) / 2
                 worst = max(worst, abs(complex(re, im) - want) / scale)
             rec = {"case": case, "mesh": [results[(ci, 0)]["comm"]["p1"], results[(ci, 0)]["comm"]["p2"]], "rel_numpy": worst,
-                   "v": results[(ci, 0)]["v"], "tol": 5e-6 if f32 else 1e-12}
+                   "v": results[(ci, 0)]["v"], "tol": 5e-6 if f32 else 1e-12, "ranks": ranks}
             summary.append(rec)
             print(json.dumps({k: rec[k] for k in rec if k != "v"}), flush=True)
             continue
@@ -447,7 +545,7 @@ def main():
         want = np.fft.rfftn(field.real, axes=(0, 1, 2)) if r2c else np.fft.fftn(field)
         e_np = float(np.linalg.norm(G - want) / np.linalg.norm(want))
         rec = {"case": case, "mesh": [results[(ci, 0)]["comm"]["p1"], results[(ci, 0)]["comm"]["p2"]], "rel_numpy": e_np,
-               "v": results[(ci, 0)]["v"]}
+               "v": results[(ci, 0)]["v"], "ranks": ranks}
         if np.prod(shape) <= 1 << 22:  # the oracle finishes these in seconds
             og, _, _ = O.world_fft(*shape, size, kind=1, is_equalxy=case.get("eq", 0), is_r2c=r2c, **case["params"])
             rec["rel_oracle"] = float(np.linalg.norm(G - og) / np.linalg.norm(og))

@@ -18,6 +18,9 @@ typedef int (*a2a_cb_t)(int which, int npeers, const int *peer, const void *cons
                         void *const *recvp, const size_t *recvbytes);
 static a2a_cb_t g_a2a_cb = NULL;
 static long g_pass_count = 0;
+/* per THREAD (ranks as threads, tests/_thread_world.py): what this rank has launched -- passes, flag operations, exchanges,
+ * copies -- and failure injection: the n-th pass from now returns -1 once (tests/test_p2p_lifecycle.py) */
+static _Thread_local long g_thread_launches = 0, g_thread_passes = 0, g_fail_pass_at = -1;
 
 /* failure injection: the n-th allocation from now fails once (an out-of-memory on ONE rank, tests/test_host_logic.py) */
 static long g_alloc_count = 0, g_fail_alloc_at = -1;
@@ -39,6 +42,8 @@ static long long split_off(int k, int split, int nfloor, long long blk, long lon
 static int cb_pass(const offt_pass_desc *d, const void *in, void *out, void *stream) {
   (void)stream;
   g_pass_count++;
+  g_thread_launches++;
+  if (++g_thread_passes == g_fail_pass_at) { g_fail_pass_at = -1; return -1; }
   if (d->n < 1 || d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
   const int n = d->n, f32 = d->precision == OFFT_PREC_F32;
   orc_fft_plan *pl = orc_fft_plan_create(n);
@@ -84,10 +89,11 @@ static double cb_event_ms(void *a, void *b) { return (a && b) ? *(double *)b - *
 static int cb_a2a(void *ctx, int which, int npeers, const int *peer, const void *const *sendp, const size_t *sendbytes,
                   void *const *recvp, const size_t *recvbytes, void *stream) {
   (void)ctx; (void)stream;
+  g_thread_launches++;
   if (!g_a2a_cb) return -1;
   return g_a2a_cb(which, npeers, peer, sendp, sendbytes, recvp, recvbytes);
 }
-static int cb_memcpy_dd(void *dst, const void *src, size_t bytes, void *s) { (void)s; memmove(dst, src, bytes); return 0; }
+static int cb_memcpy_dd(void *dst, const void *src, size_t bytes, void *s) { (void)s; g_thread_launches++; memmove(dst, src, bytes); return 0; }
 
 static int cb_upload(void *dst, const void *src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
 
@@ -107,11 +113,13 @@ static void *cb_flag_alloc(size_t bytes, int host_visible) { (void)host_visible;
 static void cb_flag_free(void *p, int host_visible) { (void)host_visible; free(p); }
 static int cb_flag_signal(int n, unsigned long long *const *addr, unsigned long long value, void *stream) {
   (void)stream;
+  g_thread_launches++;
   for (int i = 0; i < n; i++) __atomic_store_n(addr[i], value, __ATOMIC_RELEASE);
   return 0;
 }
 static int cb_flag_wait(int n, unsigned long long *const *addr, unsigned long long value, unsigned long long *status, double timeout_s, void *stream) {
   (void)stream;
+  g_thread_launches++;
   struct timespec t0, t;
   clock_gettime(CLOCK_MONOTONIC, &t0);
   for (int i = 0; i < n; i++)
@@ -136,4 +144,6 @@ void cpu_backend_set_a2a(a2a_cb_t cb) { g_a2a_cb = cb; }
 void cpu_backend_set_peer_open(peer_cb_t cb) { g_peer_cb = cb; }
 long cpu_backend_pass_count(void) { return g_pass_count; }
 long cpu_backend_alloc_count(void) { return g_alloc_count; }
+long cpu_backend_thread_launch_count(void) { return g_thread_launches; }
+void cpu_backend_thread_fail_pass_at(long n_from_now) { g_fail_pass_at = n_from_now > 0 ? g_thread_passes + n_from_now : -1; }
 void cpu_backend_fail_alloc_at(long n_from_now) { g_fail_alloc_at = n_from_now > 0 ? g_alloc_count + n_from_now : -1; }

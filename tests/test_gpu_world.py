@@ -49,6 +49,10 @@ def run_world(size, cases, tmp_path):
                 assert np.linalg.norm(back / np.prod(shape) - blk) / np.linalg.norm(blk) < 1e-13, (case, r)
         if case.get("p2p"):  # the direct-store exchange was really in use (no silent fall-back to the staged one)
             assert all(json.load(open(tmp_path / f"case{ci}_rank{r}.json"))["exchange"] == 1 for r in range(size)), case
+            # ... and its state described the plan's buffers after init and after every execute (offt_hip_test_p2p_consistent)
+            for r in range(size):
+                seen = json.load(open(tmp_path / f"case{ci}_rank{r}.json"))["consistent"]
+                assert len(seen) >= 2 and all(x == 1 for x in seen), (case, r, seen)
 
 
 def run_thread_world(size, cases, tmp_path, env=None):
@@ -195,6 +199,22 @@ def test_direct_store_exchange_between_processes_hipipc(built, tmp_path):
              dict(N=[64, 32, 16], params=dict(P1=2, T1=8), p2p=1, inv=1, repeat=1)]
     run_world(2, cases, tmp_path)
     run_world(4, [dict(N=[64, 64, 64], params=dict(P1=2), p2p=1, repeat=1), dict(N=[128, 128, 128], params=dict(P1=1), p2p=1)], tmp_path)
+
+
+def test_direct_store_exchange_through_the_sweep(built, tmp_path):
+    """the static sweep (max_loop > 0) under the direct-store exchange on device memory: every point frees and reallocates
+    the receive volumes, and the peers' mappings, tables, flags and slot counters are rebuilt with them (slab and pencil; the
+    same cases run on the CPU in tests/test_p2p_lifecycle.py)"""
+    cases = [dict(N=[16, 16, 16], params=dict(P1=1), p2p=1, max_loop=6), dict(N=[16, 16, 16], params=dict(P1=2), p2p=1, max_loop=6)]
+    for rec in run_thread_world(2, cases, tmp_path):
+        for r in rec["ranks"]:
+            assert r["consistent"] == [1, 1] and r["exchange"] == [1, 1], rec
+
+
+def test_direct_store_exchange_between_processes_hipipc_through_the_sweep(built, tmp_path):
+    """... and between processes: every rebuild closes the hipIpc mappings of the volumes it frees and opens the new ones"""
+    cases = [dict(N=[64, 64, 64], params=dict(P1=1), p2p=1, repeat=2, max_loop=4), dict(N=[64, 64, 64], params=dict(P1=2), p2p=1, repeat=1, max_loop=4)]
+    run_world(2, cases, tmp_path)
 
 
 def test_long_lines_in_worlds(built, tmp_path):

@@ -381,6 +381,26 @@ def test_gloo_world4_one_rank_out_of_memory_during_the_sweep(built, tmp_path):
     assert vs[0][0] != int(lines[1][1])                                           # ... and was not chosen
 
 
+def test_gloo_world2_out_of_memory_in_the_sweeps_last_rebuild(built, tmp_path):
+    """the sweep ends by rebuilding the buffers of the point it chose, and the plan keeps what that rebuild makes: when it
+    fails on ONE rank (its last allocation, a receive volume) offt_3d_init fails on EVERY rank -- no rank is left holding a
+    plan whose peer has none"""
+    cases = [dict(N=[8, 8, 8], params=dict(P1=1), max_loop=4, fail_alloc=dict(rank=1, final=1),
+                  env=dict(OFFT_SWEEP_DB="{outdir}/sweep_last.db", OFFT_SELF_BYPASS=0))]
+    port = _free_port()
+    procs = []
+    for r in range(2):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="1")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gloo_worker.py"), json.dumps(cases), str(tmp_path)],
+                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
+    outs = [p.communicate(timeout=300)[0].decode() for p in procs]
+    for r, p in enumerate(procs):
+        assert p.returncode == 0, f"rank {r} failed:\n{outs[r]}"
+    for r in range(2):
+        msg = json.load(open(tmp_path / f"case0_rank{r}.json"))["init_failed"]
+        assert "the sweep could not rebuild the buffers of the point it chose" in msg, (r, msg)
+
+
 def test_gloo_world8(built, tmp_path):
     """the 8-rank shapes the multi-GPU bench uses (1x8 slab, 2x4 pencil, 8x1), incl. r2c and ragged sizes"""
     cases = [dict(N=[16, 16, 16], params=dict(P1=1)), dict(N=[16, 16, 16], params=dict()),

@@ -11,9 +11,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_cpu_thread_world(size, cases, tmp_path):
+def run_cpu_thread_world(size, cases, tmp_path, env=None, output=None):
+    """`env`: further environment of the world; `output`: a list that gets the world's output (stdout and stderr) appended"""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_thread_world.py"), str(size), json.dumps(cases), str(tmp_path), "cpu"],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=dict(os.environ, OMP_NUM_THREADS="1", OFFT_P2P_TIMEOUT="20"))
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300,
+                       env=dict(dict(os.environ, OMP_NUM_THREADS="1", OFFT_P2P_TIMEOUT="20"), **(env or {})))
+    if output is not None:
+        output.append(p.stdout.decode())
     assert p.returncode == 0, p.stdout.decode()[-4000:]
     summary = json.load(open(tmp_path / "summary.json"))
     assert len(summary) == len(cases)
