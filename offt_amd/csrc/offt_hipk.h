@@ -116,6 +116,19 @@ int offt_hipk_fft_pass_pair(const offt_pass_desc *dy, const void *iny, void *out
 int offt_hipk_has_pass_pair(const offt_pass_desc *dy, const offt_pass_desc *dx);
 /* "fft_pair_yx_k", or "no paired kernel" */
 const char *offt_hipk_pair_kernel_name(const offt_pass_desc *dy, const offt_pass_desc *dx);
+/* The grid offt_hipk_fft_pass_pair would launch, asked without launching (needs no device): the workgroups of either role
+ * (*ny_blocks, *nx_blocks: column panels of the role's shape times nb1 times nb2) and how many blocks of EACH role are
+ * dispatched in alternating runs (*both, a multiple of the run length; the rest of x, then the rest of y follow).  Any
+ * pointer may be NULL.  Returns the run length in blocks (one period of the x role's XCD-aware order, or OFFT_PAIR_RUN), or
+ * -1 where offt_hipk_has_pass_pair says 0. */
+int offt_hipk_pass_pair_grid(const offt_pass_desc *dy, const offt_pass_desc *dx, long long *ny_blocks, long long *nx_blocks, long long *both);
+/* The XCD-aware panel order every launch gives a grid of nblk workgroups (OFFT_XCD_REMAP): returns the run length G in
+ * panels (a power of two; 0 = launch order) and in *lim (may be NULL) the number of leading blocks that are renumbered, a
+ * multiple of 8 G -- the blocks behind it keep their index.  Needs no device. */
+int offt_hipk_panel_order(long long nblk, long long *lim);
+/* Workgroup size the any-length kernel (fft_mixed_k) runs lines of n points with (from its LDS footprint, or
+ * OFFT_MIX_THREADS); 0: the line is too long for that kernel.  Needs no device. */
+int offt_hipk_any_length_threads(int n, int precision);
 /* 1 if the pass, with out_keep set, runs on a kernel whose stores stay cached (otherwise out_keep is ignored)          */
 int offt_hipk_keeps_output(const offt_pass_desc *d);
 /* 1 if a register/LDS Stockham panel kernel exists for (n, precision): powers of two up to 4096

@@ -1633,6 +1633,23 @@ int launch_blue_panel(const offt_pass_desc *d, const void *in, void *out, hipStr
                 &a.xcd_lim, &a.xcd_gshift, args, st);
 }
 
+// the any-length kernel's panel for lines of n points: columns per workgroup, twiddles in LDS or not, LDS bytes, workgroup size
+struct MixShape { int cols; bool tw_in_lds; size_t lds; unsigned threads; };
+MixShape mix_shape(int n, int prec) {
+  MixShape s;
+  const size_t line = n * elem_size(prec);
+  s.cols = 8;
+  while (s.cols > 1 && (2 * (size_t)s.cols + 1) * line > LDS_BYTES) s.cols >>= 1;
+  s.tw_in_lds = (2 * (size_t)s.cols + 1) * line <= LDS_BYTES;
+  s.lds = (2 * (size_t)s.cols + (s.tw_in_lds ? 1 : 0)) * line;
+  // the panel's LDS footprint allows one or two workgroups per CU: size the workgroup so that the CU still
+  // holds 8-16 waves to cover the LDS round trips between stages
+  s.threads = s.lds > 80 * 1024 ? 1024 : s.lds > 40 * 1024 ? 512 : 256;
+  while (s.threads > 64 && (long long)s.threads * 2 > (long long)s.cols * n) s.threads >>= 1;  // at least two elements per thread
+  if (env().mix_threads >= 64 && env().mix_threads <= 1024) s.threads = (unsigned)env().mix_threads;
+  return s;
+}
+
 int launch_any_length(const offt_pass_desc *d, const void *in, void *out, const Tables &tb, hipStream_t st) {
   GenArgs g = gen_args(d);
   g.in_contig = d->in_contig; g.out_contig = d->out_contig;
@@ -1650,23 +1667,15 @@ int launch_any_length(const offt_pass_desc *d, const void *in, void *out, const 
   if (d->n == 1) { g.nfac = 0; }
   if (g.nfac > OFFT_MIX_MAXFAC) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d has too many factors", d->n); return -1; }
   if (!fits_any_length(d->n, d->precision)) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass: n=%d too long for the any-length kernel", d->n); return -1; }
-  const size_t line = d->n * elem_size(d->precision);
-  int cols = 8;
-  while (cols > 1 && (2 * (size_t)cols + 1) * line > LDS_BYTES) cols >>= 1;
-  g.tw_in_lds = (2 * (size_t)cols + 1) * line <= LDS_BYTES;
-  g.cols = cols;
-  g.ncp = (d->ncols + cols - 1) / cols;
-  const size_t lds = (2 * (size_t)cols + (g.tw_in_lds ? 1 : 0)) * line;
-  // the panel's LDS footprint allows one or two workgroups per CU: size the workgroup so that the CU still
-  // holds 8-16 waves to cover the LDS round trips between stages
-  unsigned nt = lds > 80 * 1024 ? 1024 : lds > 40 * 1024 ? 512 : 256;
-  while (nt > 64 && (long long)nt * 2 > (long long)cols * d->n) nt >>= 1;  // at least two elements per thread
-  if (env().mix_threads >= 64 && env().mix_threads <= 1024) nt = (unsigned)env().mix_threads;
+  const MixShape ms = mix_shape(d->n, d->precision);
+  g.tw_in_lds = ms.tw_in_lds;
+  g.cols = ms.cols;
+  g.ncp = (d->ncols + ms.cols - 1) / ms.cols;
   static bool attr_set[2] = {false, false};
   const bool f64 = d->precision == OFFT_PREC_F64;
   void *args[] = {(void *)&g, (void *)&in, (void *)&out, (void *)&tb.full};
   return launch("offt_hipk_fft_pass", f64 ? (const void *)fft_mixed_k<double> : (const void *)fft_mixed_k<float>, nullptr, &attr_set[f64 ? 0 : 1],
-                LDS_BYTES, lds, nt, (long long)g.ncp * d->nb1 * d->nb2, &g.xcd_lim, &g.xcd_gshift, args, st);
+                LDS_BYTES, ms.lds, ms.threads, (long long)g.ncp * d->nb1 * d->nb2, &g.xcd_lim, &g.xcd_gshift, args, st);
 }
 
 int four_pass(const offt_pass_desc *d, const void *in, void *out, void *stream, const FourStep &fs, const Tables &tb) {
@@ -2069,6 +2078,23 @@ Variant *pick_pair(const offt_pass_desc *dy, const void *iny, const void *outy, 
   *vy = ry.v; *vx = rx.v;
   return p;
 }
+
+// the grid of a paired launch: workgroups per role, each role's XCD-aware order (that of a launch of its own), and the
+// dispatch order of fft_pair_yx_k -- runs of 2^run_shift blocks alternate while both roles have a whole run left (blocks
+// below 2 * both).  A run is a whole period of the x role's order (8 XCDs times G panels) unless OFFT_PAIR_RUN says otherwise
+struct PairGrid { long long nyb, nxb; unsigned run_shift, both; };
+PairGrid pair_grid(const offt_pass_desc *dy, const offt_pass_desc *dx, PassArgs *ay, PassArgs *ax) {
+  PairGrid g;
+  g.nyb = (long long)ay->ncp * dy->nb1 * dy->nb2;
+  g.nxb = (long long)ax->ncp * dx->nb1 * dx->nb2;
+  xcd_order(g.nyb, &ay->xcd_lim, &ay->xcd_gshift);
+  xcd_order(g.nxb, &ax->xcd_lim, &ax->xcd_gshift);
+  g.run_shift = 3u + (env().xcd_remap > 0 ? ax->xcd_gshift : 0u);
+  if (env().pair_run >= 8 && is_pow2(env().pair_run)) g.run_shift = (unsigned)log2i(env().pair_run);
+  const long long least = g.nxb < g.nyb ? g.nxb : g.nyb;
+  g.both = (unsigned)((least >> g.run_shift) << g.run_shift);
+  return g;
+}
 }  // namespace
 
 int offt_hipk_has_pass_pair(const offt_pass_desc *dy, const offt_pass_desc *dx) {
@@ -2093,21 +2119,37 @@ int offt_hipk_fft_pass_pair(const offt_pass_desc *dy, const void *iny, void *out
   Tables ty, tx;
   if (get_tables(dy->n, dy->precision, ty, false) || get_tables(dx->n, dx->precision, tx, false)) return -1;
   PassArgs ay = pass_args(dy, p->cols), ax = pass_args(dx, p->pair_x_cols);
-  const long long nyb = (long long)ay.ncp * dy->nb1 * dy->nb2, nxb = (long long)ax.ncp * dx->nb1 * dx->nb2;
-  if (nyb + nxb > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass_pair: grid too large"); return -1; }
-  // each role keeps the XCD-aware order of a launch of its own; a run of one role is a whole period of that order (8 XCDs
-  // times G panels) unless OFFT_PAIR_RUN says otherwise
-  xcd_order(nyb, &ay.xcd_lim, &ay.xcd_gshift);
-  xcd_order(nxb, &ax.xcd_lim, &ax.xcd_gshift);
-  unsigned run_shift = 3u + (env().xcd_remap > 0 ? ax.xcd_gshift : 0u);
-  if (env().pair_run >= 8 && is_pow2(env().pair_run)) run_shift = (unsigned)log2i(env().pair_run);
-  const long long least = nxb < nyb ? nxb : nyb;
-  unsigned nx = (unsigned)nxb, both = (unsigned)((least >> run_shift) << run_shift);
+  PairGrid g = pair_grid(dy, dx, &ay, &ax);
+  if (g.nyb + g.nxb > 0x7fffffffLL) { snprintf(g_err, sizeof g_err, "offt_hipk_fft_pass_pair: grid too large"); return -1; }
+  unsigned nx = (unsigned)g.nxb;
   unsigned total_lim = 0, total_gshift = 0;  // (launch() works out the order of the whole grid: no role uses it)
   void *args[] = {(void *)&ay, (void *)&iny, (void *)&outy, (void *)&ty.full, (void *)&ax, (void *)&inx, (void *)&outx, (void *)&tx.full,
-                  (void *)&nx, (void *)&both, (void *)&run_shift};
-  return launch("offt_hipk_fft_pass_pair", p->fn, nullptr, &p->attr_set, p->lds, p->lds, p->threads, nyb + nxb, &total_lim, &total_gshift, args,
+                  (void *)&nx, (void *)&g.both, (void *)&g.run_shift};
+  return launch("offt_hipk_fft_pass_pair", p->fn, nullptr, &p->attr_set, p->lds, p->lds, p->threads, g.nyb + g.nxb, &total_lim, &total_gshift, args,
                 (hipStream_t)stream);
+}
+
+int offt_hipk_pass_pair_grid(const offt_pass_desc *dy, const offt_pass_desc *dx, long long *ny_blocks, long long *nx_blocks, long long *both) {
+  Variant *vy, *vx;
+  const Variant *p = pick_pair(dy, nullptr, nullptr, dx, nullptr, nullptr, &vy, &vx);
+  if (!p) return -1;
+  PassArgs ay = pass_args(dy, p->cols), ax = pass_args(dx, p->pair_x_cols);
+  const PairGrid g = pair_grid(dy, dx, &ay, &ax);
+  if (ny_blocks) *ny_blocks = g.nyb;
+  if (nx_blocks) *nx_blocks = g.nxb;
+  if (both) *both = g.both;
+  return 1 << g.run_shift;
+}
+
+int offt_hipk_panel_order(long long nblk, long long *lim) {
+  unsigned l = 0, gshift = 0;
+  xcd_order(nblk, &l, &gshift);
+  if (lim) *lim = l;
+  return env().xcd_remap > 0 ? 1 << gshift : 0;
+}
+
+int offt_hipk_any_length_threads(int n, int precision) {
+  return n >= 1 && fits_any_length(n, precision) ? (int)mix_shape(n, precision).threads : 0;
 }
 
 }  // extern "C"

@@ -74,10 +74,17 @@ __device__ __forceinline__ void gstore(V2 *p, V2 v) {
   __builtin_nontemporal_store(r, reinterpret_cast<vt *>(p));
 }
 
+// KEEP: the same vector store with the default cache policy.  The two forms differ in the store's cache hint and in nothing
+// else the optimiser sees, so a KEEP instantiation rounds exactly like its plain twin (a struct store here once gave the
+// single-precision 256- and 1024-point twins other packed-math and contraction choices: last-place differences)
 template <bool KEEP, typename V2>
 __device__ __forceinline__ void gstore_p(V2 *p, V2 v) {
-  if constexpr (KEEP) *p = v;
-  else gstore(p, v);
+  if constexpr (KEEP) {
+    using E = decltype(p->x);
+    typedef E vt __attribute__((ext_vector_type(2)));
+    vt r; r.x = v.x; r.y = v.y;
+    *reinterpret_cast<vt *>(p) = r;
+  } else gstore(p, v);
 }
 
 // v with its sign bit XORed by m (m = 0 or 0x80000000, uniform): conjugation and half-wave twiddle signs cost one
