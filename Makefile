@@ -105,6 +105,11 @@ tests/libcpubackend_streams.so: tests/cpu_backend_streams.c tests/cpu_backend_sp
 tests/libcpubackend_pipeline.so: tests/cpu_backend_pipeline.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
 	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_pipeline.c tests/cpu_backend.c oracle/oracle_fft.c -lm
 
+# ... and the plain interpreter with pass_pair, every launch and stream operation logged with its stream, and a replay that
+# runs the queued operations in the orders the event edges allow (tests/test_zgroup_chains.py)
+tests/libcpubackend_chains.so: tests/cpu_backend_chains.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
+	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_chains.c tests/cpu_backend.c oracle/oracle_fft.c -lm
+
 # run-fft-compatible C harness.  MPI=1 builds the multi-rank variant
 # against an MPI found at MPI_PREFIX (e.g. /opt/conda; linked by file name, not -L: a conda lib directory also holds an
 # older libstdc++ that must not shadow the system one the HIP runtime needs).

@@ -267,6 +267,16 @@ int offt_hip_wait(struct _offt_plan *po);
                                           box), 0 (default) = such a plan transforms and multiplies in separate launches.  Alone it
                                           changes nothing.  Read by every filtered call; the results agree to rounding
                                           (OFFT_SPEC_MIXED) */
+/* (22 is not assigned, like 15 and 17) */
+#define OFFT_HIP_OPT_ZGROUP_CHAINS 23  /* the pipelined plane groups of OFFT_HIP_OPT_ZGROUP_PIPELINE (same plans, and only with it): 2 = two
+                                          independent chains, the even groups on the plan's stream and the odd groups on a second
+                                          stream of the library's (y(0) | {x(0), y(2)} | ... | x(G-2)  next to  y(1) | {x(1), y(3)} |
+                                          ... | x(G-1)), forked behind the z pass and joined before the call returns or enqueues anything
+                                          else; the groups are then half the usual size unless OFFT_HIP_OPT_ZGROUP_PLANES /
+                                          OFFT_HIP_OPT_ZGROUP_MIB fix it, and a transform of fewer than 4 groups runs as one chain;
+                                          1 = one chain.  The default is 2 where the library sizes the groups itself; a plan whose
+                                          group size is fixed takes two chains only once this option (or OFFT_ZGROUP_CHAINS) is set.
+                                          Equal bits either way; any other value is refused (OFFT_ZGROUP_CHAINS) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds
@@ -301,6 +311,9 @@ int offt_hip_last_passes_paired(const struct _offt_plan *po);
 /* how many launches of the last single-rank execute carried two passes in one grid (OFFT_HIP_OPT_ZGROUP_PIPELINE): 0 = the
  * plan did not take that route */
 int offt_hip_last_pipelined_launches(const struct _offt_plan *po);
+/* ... and in how many chains they ran (OFFT_HIP_OPT_ZGROUP_CHAINS): 2 = on two streams, 1 = on the plan's stream alone, 0 = the
+ * last execute did not take the pipelined route.  The count above is over both chains */
+int offt_hip_last_pipelined_chains(const struct _offt_plan *po);
 /* last error text ("" if none); errors also go to stderr, like the reference's
  * printf-only error handling (offt-compute.c:702-704)                           */
 const char *offt_hip_last_error(void);

@@ -22,6 +22,7 @@ PARAM_NAMES = ["P1", "T1", "W1", "Px1", "Py1", "Fz", "FP1", "Ux1", "Uz1", "FU1",
 FFTW_ESTIMATE = 1 << 6
 F64, F32 = 0, 1
 FILTER_REAL, FILTER_COMPLEX = 0, 1  # offt_hip.h OFFT_HIP_FILTER_REAL / OFFT_HIP_FILTER_COMPLEX
+OPT_ZGROUP_CHAINS = 23  # (22 is unassigned) offt_hip.h OFFT_HIP_OPT_ZGROUP_CHAINS: 2 = the pipelined plane groups as two chains on two streams (even / odd groups; the default where the library sizes the groups), 1 = one chain
 OPT_SPEC_MIXED = 21  # offt_hip.h OFFT_HIP_OPT_SPEC_MIXED: with OPT_SPEC_FUSED, the filtered forward / inverse of a plan whose x extent is no power of two may run the fused route
 OPT_ZGROUP_PLANES = 20  # offt_hip.h OFFT_HIP_OPT_ZGROUP_PLANES: planes per plane group (> 0: instead of OPT_ZGROUP_MIB)
 OPT_ZGROUP_PIPELINE = 19  # offt_hip.h OFFT_HIP_OPT_ZGROUP_PIPELINE: x(group g-1) and y(group g) of the forward z-y-x plane groups as one launch
@@ -151,6 +152,8 @@ def bind(L):
     L.offt_hip_last_passes_paired.argtypes = [PP]
     L.offt_hip_last_pipelined_launches.restype = i
     L.offt_hip_last_pipelined_launches.argtypes = [PP]
+    L.offt_hip_last_pipelined_chains.restype = i
+    L.offt_hip_last_pipelined_chains.argtypes = [PP]
     L.offt_hip_last_error.restype = C.c_char_p
     L.offt_hip_malloc.restype = C.c_void_p
     L.offt_hip_malloc.argtypes = [C.c_longlong]

@@ -377,6 +377,8 @@ static struct _offt_comm *comm_build(const struct _offt_plan *po) {
 /* pipelined plane groups (execute_single, OFFT_HIP_OPT_ZGROUP_PIPELINE): whether a plan starts with them
  * (profiles/zgroup_pipeline.txt) */
 #define ZGROUP_PIPELINE_DEFAULT 1
+/* ... and in how many chains (OFFT_HIP_OPT_ZGROUP_CHAINS; profiles/zgroup_chains.txt) */
+#define ZGROUP_CHAINS_DEFAULT 2
 typedef struct hip_state {
   int prec;
   size_t esz;           /* bytes per complex element */
@@ -439,7 +441,9 @@ typedef struct hip_state {
   double out_scale;
   int yx_fused;        /* the last single-rank execute alternated launches i and i+1 over groups of planes: i + 1 (0: none) */
   int yx_pipelined;    /* ... and this many of its launches carried x(group g-1) and y(group g) in one grid (0: plain alternation) */
-  void *s_aux, *ev_aux[4]; /* ... with the x launches on this second stream, ordered behind their y launch by these events */
+  int yx_chains;       /* ... in this many chains (2: even groups on the compute stream, odd ones on s_aux; 0: not pipelined) */
+  void *s_aux, *ev_aux[4]; /* ... with the x launches on this second stream, ordered behind their y launch by these events
+                              (OFFT_ZGROUP_STREAMS = 2); or the odd groups' chain on it, [0] the fork and [1] the join (yx_chains = 2) */
   /* plan-level options (offt_hip_set_option).  The environment variables of the same meaning are read ONCE, in
    * offt_3d_init, as defaults: nothing below depends on the process environment after the plan exists */
   struct {
@@ -448,6 +452,8 @@ typedef struct hip_state {
     int zgroup_planes;   /* ... the forward y / x pair of execute_single only: planes per group where it runs in groups at all (> 0) */
     int zgroup_pipeline; /* ... 1 = x(group g-1) and y(group g) in one grid where the pair has such a kernel (execute_single) */
     int zgroup_pipeline_set; /* ... and somebody said so (option or environment), see execute_single */
+    int zgroup_chains;   /* ... 2 = the pipelined groups as two paired chains, even groups on the compute stream and odd ones on a second */
+    int zgroup_chains_set; /* ... and somebody said so, as above */
     int slab_chunk_mib;  /* slab schedule: largest z-chunk of the y-transformed volume (Infinity-Cache reuse K2 -> K3) */
     int comm_streams;    /* pencil schedule: 2 = row and column exchanges on separate streams */
     long long min_msg;   /* tiles are merged upwards until a per-peer message has this many bytes */
@@ -1343,6 +1349,8 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.zgroup_planes = getenv("OFFT_ZGROUP_PLANES") ? atoi(getenv("OFFT_ZGROUP_PLANES")) : 0;
   st->opt.zgroup_pipeline = getenv("OFFT_ZGROUP_PIPELINE") ? atoi(getenv("OFFT_ZGROUP_PIPELINE")) != 0 : ZGROUP_PIPELINE_DEFAULT;
   st->opt.zgroup_pipeline_set = getenv("OFFT_ZGROUP_PIPELINE") != NULL;
+  st->opt.zgroup_chains = getenv("OFFT_ZGROUP_CHAINS") ? (atoi(getenv("OFFT_ZGROUP_CHAINS")) >= 2 ? 2 : 1) : ZGROUP_CHAINS_DEFAULT;
+  st->opt.zgroup_chains_set = getenv("OFFT_ZGROUP_CHAINS") != NULL;
   st->opt.slab_chunk_mib = getenv("OFFT_SLAB_CHUNK_MIB") ? atoi(getenv("OFFT_SLAB_CHUNK_MIB")) : 256;
   st->opt.comm_streams = getenv("OFFT_COMM_STREAMS") ? atoi(getenv("OFFT_COMM_STREAMS")) : 1;
   st->opt.min_msg = getenv("OFFT_MIN_MSG") ? atoll(getenv("OFFT_MIN_MSG")) : 4LL << 20;
@@ -1844,6 +1852,10 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_PIPELINE: st->opt.zgroup_pipeline = value != 0; st->opt.zgroup_pipeline_set = 1; break;
     case OFFT_HIP_OPT_ZGROUP_PLANES: st->opt.zgroup_planes = (int)value; break;
+    case OFFT_HIP_OPT_ZGROUP_CHAINS:
+      if (value != 1 && value != 2) { SET_ERR("offt_hip_set_option: OFFT_HIP_OPT_ZGROUP_CHAINS is 1 or 2, not %lld", value); return -1; }
+      st->opt.zgroup_chains = (int)value; st->opt.zgroup_chains_set = 1;
+      break;
     case OFFT_HIP_OPT_F32_PAIRS: st->opt.f32_pairs = value != 0; break;
     case OFFT_HIP_OPT_K1_STREAMS: st->k1_streams = (int)value; break;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: st->opt.exec_timeout_s = (double)value; break;
@@ -1877,6 +1889,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_ZGROUP_STREAMS: return st->opt.zgroup_streams;
     case OFFT_HIP_OPT_ZGROUP_PIPELINE: return st->opt.zgroup_pipeline;
     case OFFT_HIP_OPT_ZGROUP_PLANES: return st->opt.zgroup_planes;
+    case OFFT_HIP_OPT_ZGROUP_CHAINS: return st->opt.zgroup_chains;
     case OFFT_HIP_OPT_F32_PAIRS: return st->opt.f32_pairs;
     case OFFT_HIP_OPT_HALF_R2C: return st->opt.half_r2c;
     case OFFT_HIP_OPT_HALF_MIXED: return st->opt.half_mixed;
@@ -1917,6 +1930,8 @@ int offt_hip_last_passes_paired(const struct _offt_plan *po) {
 }
 /* how many launches of the last single-rank execute carried two passes (0: none, the pair alternated or ran as plain launches) */
 int offt_hip_last_pipelined_launches(const struct _offt_plan *po) { return ((const hip_state *)po->hip_state)->yx_pipelined; }
+/* ... and in how many chains those launches ran (2: two streams; 1: one; 0: the last execute was not pipelined) */
+int offt_hip_last_pipelined_chains(const struct _offt_plan *po) { return ((const hip_state *)po->hip_state)->yx_chains; }
 void offt_hip_last_pass_seconds(const struct _offt_plan *po, double t[3]) {
   const hip_state *st = (const hip_state *)po->hip_state;
   t[0] = st->pass_s[0]; t[1] = st->pass_s[1]; t[2] = st->pass_s[2];
@@ -2208,6 +2223,73 @@ static int execute_single(struct _offt_plan *po, void *data, int dir) {
   /* OFFT_HIP_OPT_ZGROUP_PLANES: the size of this pair's groups in planes, where the rule above has groups at all (it turns
    * nothing on: OFFT_HIP_OPT_ZGROUP_MIB = 0 stays off), for groups finer than a MiB count can say; no other call reads it */
   if (ng >= 1 && st->opt.zgroup_planes > 0 && ia == 1 && ss.zyx && dir <= 0) ng = st->opt.zgroup_planes > cnt ? cnt : st->opt.zgroup_planes;
+  /* The pipelined pair as TWO chains (OFFT_HIP_OPT_ZGROUP_CHAINS = 2).  The only dependence among the groups is x(g) on y(g),
+   * so the even and the odd groups are two independent paired sequences, each on an in-order stream of its own:
+   *   s      y(0) | {x(0), y(2)} | {x(2), y(4)} | ... | x(last even group)
+   *   s_aux  y(1) | {x(1), y(3)} | {x(3), y(5)} | ... | x(last odd group)
+   * No event orders anything inside the phase: s_aux waits once for the launch ahead of the pair (fork) and s waits once for
+   * the end of s_aux (join), so while one chain's launch drains the other chain's workgroups fill the chip.  Four groups are
+   * live at a time instead of two, hence groups of half the size unless somebody fixed it; with fewer than 4 groups (a chain
+   * would have no paired launch at all) the one chain above runs at its own group size.  The same kernels on the same planes:
+   * equal bits.  A test table is asked only once the option has been set, as for pass_pair above.  Nor does the DEFAULT reach
+   * a plan whose group size somebody fixed: that size was chosen for two live groups, the library cannot halve it, and two
+   * chains at the one chain's size lose (1024^3 f64, 16 planes: 18.49 against 16.89 ms, profiles/zgroup_chains.txt); there
+   * the option has to be set as well. */
+  int chains = pipelined && ng >= 1 ? 1 : 0;
+  const int fixed = st->opt.zgroup_planes > 0 || st->opt.zgroup_mib >= 0;
+  if (pipelined && ng >= 1 && st->opt.zgroup_chains >= 2 && (st->opt.zgroup_chains_set || (be->pass == hb_pass && !fixed))) {
+    const int ng2 = fixed || ng < 2 ? ng : ng / 2;
+    if ((cnt + ng2 - 1) / ng2 >= 4) {
+      if (!st->s_aux) {
+        st->s_aux = be->stream_create();
+        for (int i = 0; i < 4; i++) st->ev_aux[i] = be->event_create();
+      }
+      if (st->s_aux && st->ev_aux[0] && st->ev_aux[1]) { chains = 2; ng = ng2; }
+    }
+  }
+  st->yx_chains = chains;
+  if (chains == 2) {
+    void *sx = st->s_aux;
+    const int ngroups = (cnt + ng - 1) / ng;
+    int rc = 0;
+    for (int i = 0; i < ia; i++) { /* the launch ahead of the pair */
+      if (st->timed) be->event_record(st->evp[i], s);
+      if (be->pass(&ss.d[i], ss.src[i], ss.dst[i], s)) return -1;
+    }
+    if (st->timed) be->event_record(st->evp[ia], s);
+    be->event_record(st->ev_aux[0], s); /* fork */
+    be->stream_wait(sx, st->ev_aux[0]);
+    /* step k issues y(k) and x(k-2) on chain k & 1: together where both exist, so the two chains are fed in turn */
+    for (int k = 0; k < ngroups + 2 && !rc; k++) {
+      void *sk = (k & 1) ? sx : s;
+      offt_pass_desc da = ss.d[ia], db = ss.d[ib];
+      const int zy = k * ng, zx = (k - 2) * ng;
+      const int have_y = k < ngroups, have_x = k >= 2;
+      da.nb1 = have_y ? (cnt - zy < ng ? cnt - zy : ng) : 0;
+      db.nb1 = have_x ? (cnt - zx < ng ? cnt - zx : ng) : 0;
+      da.out_keep = 1;
+      const char *sa = (const char *)ss.src[ia] + (size_t)(have_y ? zy : 0) * (size_t)da.in_b1_stride * st->esz;
+      char *oa = (char *)ss.dst[ia] + (size_t)(have_y ? zy : 0) * (size_t)da.out_b1_stride * st->esz;
+      const char *sb = (const char *)ss.src[ib] + (size_t)(have_x ? zx : 0) * (size_t)db.in_b1_stride * st->esz;
+      char *ob = (char *)ss.dst[ib] + (size_t)(have_x ? zx : 0) * (size_t)db.out_b1_stride * st->esz;
+      if (have_y && have_x) {
+        rc = be->pass_pair(&da, sa, oa, &db, sb, ob, sk);
+        if (!rc) st->yx_pipelined++;
+      } else if (have_y) rc = be->pass(&da, sa, oa, sk);
+      else rc = be->pass(&db, sb, ob, sk);
+    }
+    /* join, also behind a launch that failed: nothing of s_aux may still run when the caller's stream goes on */
+    be->event_record(st->ev_aux[1], sx);
+    be->stream_wait(s, st->ev_aux[1]);
+    if (rc) return -1;
+    if (st->timed) { be->event_record(st->evp[ib], s); be->event_record(st->evp[ib + 1], s); }
+    for (int i = ib + 1; i < 3; i++) { /* the launch behind the pair */
+      if (be->pass(&ss.d[i], ss.src[i], ss.dst[i], s)) return -1;
+      if (st->timed) be->event_record(st->evp[i + 1], s);
+    }
+    st->yx_fused = ia + 1;
+    return 0;
+  }
   if (ng >= 1) {
     /* OFFT_ZGROUP_STREAMS=2: consumer launches on a second stream (then 128 MiB groups do as well as 256 MiB on one stream).
      * The consumer of a group runs on a second stream behind its producer, so that the next group's producer fills the
