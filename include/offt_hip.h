@@ -170,6 +170,31 @@ int offt_hip_spectral_fused(const struct _offt_plan *po);
 #define OFFT_HIP_SHELLS_MAX_BINS 4096
 int offt_hip_spectrum_shells(struct _offt_plan *po, const void *a, const void *b, const int kmul[3], int nbins, double *sums,
                              long long *counts);
+/* Pseudo-spectral product: two stored spectra to physical space, multiplied point by point, the product back -- the
+ * nonlinear term (u . grad u, phi^2) of a solver that keeps its state as a spectrum.  a and b (device memory) each hold this
+ * rank's block of a spectrum in the forward's OUTPUT layout (ostart/osize/ostride; the Nz/2+1 half spectrum of an r2c plan);
+ * `out` receives, in the same layout,
+ *   scale * F( Finv(A) (.) Finv(B) )
+ * with Finv the library's UNNORMALISED inverse and F its unnormalised forward: with N = Nx*Ny*Nz, in numpy terms
+ *   scale * N^2 * fftn(ifftn(A) * ifftn(B))                  (complex plan: the complex product)
+ *   scale * N^2 * rfftn(irfftn(A, s) * irfftn(B, s))         (r2c plan: the product of the real fields)
+ * scale = offt_hip_set_output_scale, applied once, on the final store; every inner pass runs with scale 1.  The intermediate
+ * fields are the unnormalised inverses: N times larger than normalised ones, which in single precision is that much closer
+ * to the largest float -- scale the spectra down before the call where N * max|field| could approach 3e38.
+ * b == NULL or b == a squares the field (one inverse).  `out` may be a, b, or a device buffer of its own of
+ * offt_hip_local_bytes(po) bytes that overlaps neither input.  a and b are consumed: their contents are undefined afterwards
+ * unless they are `out`.  On an r2c plan the imaginary parts of the plane z = 0 (and z = Nz/2, Nz even) have no effect, as with
+ * any c2r inverse.  On a half-box plan the product is formed inside the box and its zero-padded spectrum is returned.
+ * Stream, async, offt_hip_wait and offt_hip_last_device_seconds (the whole call) as in offt_hip_execute_convolve_sum;
+ * offt_hip_last_pass_seconds reports zeros.  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and
+ * offt_hip_last_error(), and nothing launched, for a NULL or host-memory a or out, a host-memory b, a backend without the
+ * multiply, a failed communicator. */
+int offt_hip_execute_product(struct _offt_plan *po, void *a, void *b, void *out);
+/* 1 if the call runs the fused route: the inverse's x and y passes per input, ONE launch that runs the inverse z pass of
+ * both, multiplies in registers and runs the forward z pass (the physical field is never written), the forward's y and x
+ * passes -- one rank, the default z-y-x layout, a complex plan, no half box, a z extent that is a power of two from 64 to
+ * 1024, OFFT_HIP_OPT_PROD_FUSED set; 0: the generic route (an inverse per input, one multiply sweep, one forward) */
+int offt_hip_product_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
  *   full spectrum of the zero-padded field, in the usual output layout.
@@ -277,6 +302,10 @@ int offt_hip_wait(struct _offt_plan *po);
                                           1 = one chain.  The default is 2 where the library sizes the groups itself; a plan whose
                                           group size is fixed takes two chains only once this option (or OFFT_ZGROUP_CHAINS) is set.
                                           Equal bits either way; any other value is refused (OFFT_ZGROUP_CHAINS) */
+#define OFFT_HIP_OPT_PROD_FUSED 24     /* pseudo-spectral product: 1 = the z passes of both inverses, the multiply and the forward's z
+                                          pass are one launch where the plan has that route (offt_hip_product_fused), 0 (default) =
+                                          an inverse per input, a multiply sweep, a forward.  Any non-zero value reads back as 1.  Read
+                                          by every product call; the results agree to rounding (OFFT_PROD_FUSED) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -22,6 +22,7 @@ PARAM_NAMES = ["P1", "T1", "W1", "Px1", "Py1", "Fz", "FP1", "Ux1", "Uz1", "FU1",
 FFTW_ESTIMATE = 1 << 6
 F64, F32 = 0, 1
 FILTER_REAL, FILTER_COMPLEX = 0, 1  # offt_hip.h OFFT_HIP_FILTER_REAL / OFFT_HIP_FILTER_COMPLEX
+OPT_PROD_FUSED = 24  # offt_hip.h OFFT_HIP_OPT_PROD_FUSED: the pseudo-spectral product may run the route whose one launch carries both inverse z passes, the multiply and the forward z pass
 OPT_ZGROUP_CHAINS = 23  # (22 is unassigned) offt_hip.h OFFT_HIP_OPT_ZGROUP_CHAINS: 2 = the pipelined plane groups as two chains on two streams (even / odd groups; the default where the library sizes the groups), 1 = one chain
 OPT_SPEC_MIXED = 21  # offt_hip.h OFFT_HIP_OPT_SPEC_MIXED: with OPT_SPEC_FUSED, the filtered forward / inverse of a plan whose x extent is no power of two may run the fused route
 OPT_ZGROUP_PLANES = 20  # offt_hip.h OFFT_HIP_OPT_ZGROUP_PLANES: planes per plane group (> 0: instead of OPT_ZGROUP_MIB)
@@ -124,6 +125,10 @@ def bind(L):
     L.offt_hip_spectral_fused.argtypes = [PP]
     L.offt_hip_spectrum_shells.restype = i
     L.offt_hip_spectrum_shells.argtypes = [PP, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), i, C.c_void_p, C.c_void_p]
+    L.offt_hip_execute_product.restype = i
+    L.offt_hip_execute_product.argtypes = [PP, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.offt_hip_product_fused.restype = i
+    L.offt_hip_product_fused.argtypes = [PP]
     L.offt_hip_set_half_box.restype = i
     L.offt_hip_set_half_box.argtypes = [PP, i]
     L.offt_hip_half_box_pruned.restype = i
@@ -312,6 +317,21 @@ def offt_hip_spectrum_shells(po, a, b, nbins, sums, counts=None, kmul=None):
     km = (C.c_int * 3)(*kmul) if kmul is not None else None
     if L.offt_hip_spectrum_shells(po, a, b, km, nbins, sums, counts) != 0:
         raise RuntimeError("offt_hip_spectrum_shells failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_execute_product(po, a, b, out):
+    """out = scale * N^2 * fftn(ifftn(A) * ifftn(B)) (rfftn / irfftn for r2c plans): two stored spectra (device pointers, the
+    forward's output layout) to physical space, multiplied point by point, the product back in the same layout.  b None or
+    equal to a squares the field; `out` may be a, b or a buffer of its own of offt_hip_local_bytes bytes; a and b are consumed
+    unless they are `out` (include/offt_hip.h)"""
+    L = lib()
+    if L.offt_hip_execute_product(po, a, b, out) != 0:
+        raise RuntimeError("offt_hip_execute_product failed: " + L.offt_hip_last_error().decode())
+
+
+def offt_hip_product_fused(po):
+    """True if the product runs the fused route (one launch for both inverse z passes, the multiply and the forward z pass)"""
+    return lib().offt_hip_product_fused(po) == 1
 
 
 def offt_hip_set_half_box(po, on=True):

@@ -95,6 +95,13 @@ typedef struct offt_backend {
    * pass_pair: offt_hipk_fft_pass_pair -- two independent passes as one launch: `dy` from iny to outy and `dx` from inx to
    * outx.  A backend without workgroups runs the two one after the other. */
   int (*pass_pair)(const offt_pass_desc *dy, const void *iny, void *outy, const offt_pass_desc *dx, const void *inx, void *outx, void *stream);
+  /* ---- pseudo-spectral product (offt_hip_execute_product); appended at the end, so that every older table leaves both NULL ----
+   * prod_pass: offt_hipk_prod_pass -- the fused launch: inverse pass of src0 and src1 (NULL: src0 squared), their product,
+   * forward pass, into `dst`; NULL: no fused route.
+   * pointwise_prod: offt_hipk_pointwise_prod -- out = x * y; NULL: the call is refused. */
+  int (*prod_pass)(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream);
+  int (*pointwise_prod)(const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0, long long s1, long long s2,
+                        void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);
@@ -103,6 +110,8 @@ void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);
 const offt_backend *offt_hip_test_hip_backend_no_conv_sum(void);
 /* ... and with filt_pass_fwd and filt_pass_inv withheld: the generic route of the two filtered calls on the device */
 const offt_backend *offt_hip_test_hip_backend_no_filt(void);
+/* ... and with prod_pass withheld: the generic route of the pseudo-spectral product on the device */
+const offt_backend *offt_hip_test_hip_backend_no_prod(void);
 
 /* keep the HIP backend but route the exchange through `fn` (called with the comm stream
  * drained; device pointers): several test ranks can then share one GPU */

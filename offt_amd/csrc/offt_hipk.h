@@ -299,6 +299,27 @@ int offt_hipk_spectrum_shells(const void *a, const void *b, int precision, int r
 /* bytes of `partials` a call with these arguments needs at most (whatever the strides and the arrays' alignment); 0 for an
  * empty box and for arguments the call refuses.  Host arithmetic only. */
 long long offt_hipk_spectrum_shells_partials(int precision, const int n[3], const int N[3], const int kmul[3], int nbins);
+/* ---- pseudo-spectral product (offt_hip_execute_product): two stored spectra to physical space, multiplied point by point, the
+ * product back -- along ONE axis in one launch ----
+ * `d` is the last pass of an inverse transform over strided lines (the z pass of the z-y-x schedule: !in_contig, complex, no
+ * split, no half lines, no four-step twiddles), addressed through its in_* side for loads and stores alike.  Per line:
+ * the unnormalised inverse (exp(+i...), whatever d->direction says) of the line of src0 and of the line of src1, their complex
+ * product (src1 NULL or == src0: the square of the one, from one load and one inverse), the forward transform (exp(-i...)),
+ * times d->scale, stored to `dst` at the load offsets.  `dst` may be either source: a workgroup owns whole lines and has loaded
+ * them from both sources before its only stores; a source that is not `dst` is not written.  d->out_keep is ignored (no
+ * cache-keeping twin).  Power-of-two lines of 64 ... 1024 points.  -1, nothing launched: no such kernel, a NULL src0 or dst. */
+int offt_hipk_prod_pass(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream);
+/* 1 if offt_hipk_prod_pass has a kernel for d; the registry lookup needs no device */
+int offt_hipk_prod_has_fused(const offt_pass_desc *d);
+/* "fft_prod_panel_k", or "no fused kernel" */
+const char *offt_hipk_prod_kernel_name(const offt_pass_desc *d);
+/* out[i0 s0 + i1 s1 + i2 s2] = x[same] * y[same] over the box n0 x n1 x n2: complex elements of `precision`, or, with
+ * OFFT_HIPK_PROD_REAL or-ed into it, real scalars (the rows of an r2c plan; strides and extents then count scalars).  y NULL
+ * or == x: the square, from one load.  `out` may be either operand: a lane loads both before its only store.  ONE sweep,
+ * non-temporal, 16 B per lane along a unit stride where the rows allow. */
+#define OFFT_HIPK_PROD_REAL 0x100
+int offt_hipk_pointwise_prod(const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0, long long s1,
+                             long long s2, void *stream);
 /* zero a strided 3-D block n0 x n1 x n2 OUTSIDE the kept sub-box [0,k0) x [0,k1) x [0,k2) (0 <= k <= n); the kept part is
  * not touched.  Elements are complex values of `precision`, or, with OFFT_HIPK_ZERO_REAL or-ed into it, real scalars (the
  * rows of an r2c plan; strides and extents then count scalars).  Vector stores, 16 B per lane along a unit stride s2. */

@@ -44,6 +44,9 @@ const char *offt_hip_last_error(void) { return g_err; }
 /* default of OFFT_HIP_OPT_SPEC_FUSED: 0, because the single-precision filtered forward lost to the generic route on every
  * measured line (profiles/spec_filtered.txt) */
 #define OFFT_SPEC_FUSED_DEFAULT 0
+/* default of OFFT_HIP_OPT_PROD_FUSED: 0 until the fused route is ahead of the generic one by more than the run-to-run spread
+ * at every measured size in both precisions (profiles/product.txt) */
+#define OFFT_PROD_FUSED_DEFAULT 0
 #define SET_ERR(...)                                 \
   do {                                               \
     snprintf(g_err, sizeof g_err, __VA_ARGS__);      \
@@ -389,6 +392,8 @@ typedef struct hip_state {
   void *ev0, *ev1, *evp[4];
   void *work; size_t work_elems; /* single path: transposed-output scratch */
   void *work2;                   /* ... x-y-z output (S = 1): the second rotation's scratch */
+  void *prod_w2; int prod_w2_failed; /* offt_hip_execute_product, fused route: a second volume like `work` for the second input, made by
+                                      * the first call that needs it; failed: it could not be made, the plan's products run generic */
   /* pipeline */
   int T, ntiles, ring;
   int slab_zyx;          /* p1 == 1 and z-y-x output: single-exchange slab schedule, see execute_slab() */
@@ -473,7 +478,10 @@ typedef struct hip_state {
                           * (spec_fused_route), 0 = transform and multiply as separate launches (OFFT_HIP_OPT_SPEC_FUSED) */
     int spec_mixed;      /* filtered forward / inverse: 1 = together with spec_fused the fused route may run on the mixed-radix
                           * kernels (bit 4 of offt_filter_desc::mixed), 0 = such an x extent takes the generic route */
-    int block_pad;       /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
+    int prod_fused;      /* pseudo-spectral product: 1 = the fused route (one launch for both inverse z passes, the multiply and the
+                          * forward z pass) where the plan has one (prod_fused_route), 0 = inverses, a multiply sweep, a forward
+                          * (OFFT_HIP_OPT_PROD_FUSED) */
+    int block_pad;      /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
   double *agree_d, *agree_h; /* world_max(): 2 p doubles on the device and on the host, made once at plan time so that the
@@ -769,12 +777,32 @@ static int hb_spectrum_shells(const void *a, const void *b, int precision, int r
   if (rc) SET_ERR("shell-binned spectrum failed: %s", offt_hipk_last_error());
   return rc;
 }
+static int hb_prod_pass(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream) {
+  const int rc = offt_hipk_prod_pass(d, src0, src1, dst, stream);
+  if (rc) SET_ERR("fused product pass failed: %s", offt_hipk_last_error());
+  return rc;
+}
+static int hb_pointwise_prod(const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0, long long s1,
+                             long long s2, void *stream) {
+  const int rc = offt_hipk_pointwise_prod(x, y, out, precision, n0, n1, n2, s0, s1, s2, stream);
+  if (rc) SET_ERR("pointwise product failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static const offt_backend k_hip_backend = {
     hb_malloc, hb_free, hb_prepare, hb_pass, hb_stream_create, hb_stream_destroy, hb_event_create,
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
     hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside,
-    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv, hb_spectrum_shells, hb_pass_pair};
+    hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv, hb_spectrum_shells, hb_pass_pair,
+    hb_prod_pass, hb_pointwise_prod};
 #ifdef OFFT_TEST_SEAMS
+/* the HIP backend without the fused product launch: the generic route of offt_hip_execute_product on the device (tests compare
+ * the two routes, tools/conv_probe.py times them) */
+const offt_backend *offt_hip_test_hip_backend_no_prod(void) {
+  static offt_backend b;
+  b = k_hip_backend;
+  b.prod_pass = NULL;
+  return &b;
+}
 /* the HIP backend without its fused multi-input launch, for offt_hip_test_set_backend: a plan made under it takes the generic
  * route of offt_hip_execute_convolve_sum on the device (tools/conv_probe.py times that route with it) */
 const offt_backend *offt_hip_test_hip_backend_no_conv_sum(void) {
@@ -1288,6 +1316,7 @@ static void state_free(hip_state *st) {
   const offt_backend *be = st->be;
   be->dfree(st->work);
   be->dfree(st->work2);
+  be->dfree(st->prod_w2);
   be->dfree(st->agree_d); free(st->agree_h);
   mesh_teardown(st);
   be->dfree(st->stage);
@@ -1362,6 +1391,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.conv_multi_mixed = getenv("OFFT_CONV_MULTI_MIXED") && atoi(getenv("OFFT_CONV_MULTI_MIXED")) != 0;
   st->opt.conv_sum_mixed = getenv("OFFT_CONV_SUM_MIXED") && atoi(getenv("OFFT_CONV_SUM_MIXED")) != 0;
   st->opt.spec_fused = getenv("OFFT_SPEC_FUSED") ? atoi(getenv("OFFT_SPEC_FUSED")) != 0 : OFFT_SPEC_FUSED_DEFAULT;
+  st->opt.prod_fused = getenv("OFFT_PROD_FUSED") ? atoi(getenv("OFFT_PROD_FUSED")) != 0 : OFFT_PROD_FUSED_DEFAULT;
   st->opt.spec_mixed = getenv("OFFT_SPEC_MIXED") && atoi(getenv("OFFT_SPEC_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
@@ -1848,6 +1878,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
     case OFFT_HIP_OPT_CONV_SUM_MIXED: st->opt.conv_sum_mixed = value != 0; break; /* read by every multi-input convolve (conv_fused_route, CONV_SUM) */
     case OFFT_HIP_OPT_SPEC_FUSED: st->opt.spec_fused = value != 0; break; /* read by every filtered forward / inverse (spec_fused_route) */
     case OFFT_HIP_OPT_SPEC_MIXED: st->opt.spec_mixed = value != 0; break; /* likewise */
+    case OFFT_HIP_OPT_PROD_FUSED: st->opt.prod_fused = value != 0; break; /* read by every product call (prod_fused_route) */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_PIPELINE: st->opt.zgroup_pipeline = value != 0; st->opt.zgroup_pipeline_set = 1; break;
@@ -1898,6 +1929,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_CONV_MULTI_MIXED: return st->opt.conv_multi_mixed;
     case OFFT_HIP_OPT_CONV_SUM_MIXED: return st->opt.conv_sum_mixed;
     case OFFT_HIP_OPT_SPEC_FUSED: return st->opt.spec_fused;
+    case OFFT_HIP_OPT_PROD_FUSED: return st->opt.prod_fused;
     case OFFT_HIP_OPT_SPEC_MIXED: return st->opt.spec_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
@@ -2719,6 +2751,9 @@ static int execute_slab(struct _offt_plan *po, void *data) {
   if (p2p && run_wait(st, &st->g1, 1, ep - 1, s, EDGE_P2P_WAIT_FREE)) return -1;
 
   /* ---- K1: FFTz + pack (offt-compute.c:905-1206), all x-tiles ---- */
+  /* (recorded under the K1 tag.  A fresh plan's rec_tag is 0, chunk 0: an inverse that was the plan's FIRST transform replayed
+   *  its mirrored K1 passes with chunk 0's, ahead of the exchanges they read -- until a run had left the tag at -1 below) */
+  st->rec_tag = -1;
   be->event_record(st->evp[0], s);
   int two = st->k1_streams >= 2 && nt > 1 && !st->rec;
   if (two && !st->s_k1b) {
@@ -3821,6 +3856,126 @@ int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, i
       rc = conv_multiply(po, spec, out, filters[order[i]], filter_kind);
       if (!rc) rc = conv_inverse(po, out);
     }
+  }
+  return conv_leave(po, t0, rc);
+}
+
+/* ---- pseudo-spectral product: the dual of a convolve (two inverses, a multiply in physical space, a forward), with the
+ * convolve calls' entry, exit and refusals ---- */
+/* The fused route: one rank, the z-y-x layout, a complex plan, no half box, OFFT_HIP_OPT_PROD_FUSED, the backend entry and a
+ * kernel for the z extent (powers of two from 64 to 1024).  The inverse's last pass and the forward's first are both the z
+ * pass over the lines of the scratch volume W[x][z][y]: the forward must store where the inverse loads, with the same
+ * addressing (it does where the inverse is the forward mirrored, single_schedule).  *fd: the fused launch's descriptor, the
+ * inverse's z pass -- loads and stores through its input side, scale 1.  0: the generic route. */
+static int prod_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, offt_pass_desc *fd) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_pass_desc *z = &iv->d[2], *f0 = &fw->d[0];
+  if (st->use_pipeline || !fw->zyx || po->is_r2c || st->half_box || !st->opt.prod_fused || !st->be->prod_pass) return 0;
+  if (fw->dst[0] != iv->src[2] || f0->n != z->n || f0->ncols != z->ncols || f0->nb1 != z->nb1 || f0->nb2 != z->nb2 ||
+      f0->out_axis_stride != z->in_axis_stride || f0->out_col_stride != z->in_col_stride || f0->out_b1_stride != z->in_b1_stride ||
+      f0->out_b2_stride != z->in_b2_stride || f0->out_contig != z->in_contig || f0->out_split != z->in_split)
+    return 0;
+  *fd = *z;
+  fd->scale = 1.0;
+  fd->out_keep = 0;
+  return offt_hipk_prod_has_fused(fd);
+}
+
+int offt_hip_product_fused(const struct _offt_plan *po) {
+  if (!po || !po->hip_state || ((hip_state *)po->hip_state)->use_pipeline) return 0;
+  single_sched fw, iv;
+  offt_pass_desc fd;
+  struct _offt_plan *p = (struct _offt_plan *)po;
+  single_schedule(p, NULL, -1, &fw);
+  single_schedule(p, NULL, +1, &iv);
+  return prod_fused_route(p, &fw, &iv, &fd);
+}
+
+/* the two launches of `ss` that work through the same z-planes (ss->pair and the one behind it: x then y of an inverse, y then
+ * x of a forward), alternating over plane groups by execute_single's rule (plane_group; the producer keeps its stores), or as
+ * they are where the rule has no groups.  The consumer stores to `cdst`. */
+static int prod_plane_pair(struct _offt_plan *po, const single_sched *ss, void *cdst) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const int ia = ss->pair, ib = ia + 1, cnt = ss->planes;
+  int ng = 0;
+  if (ss->d[ia].nb1 == cnt && ss->d[ib].nb1 == cnt) ng = plane_group(st, ss->plane_elems, cnt, ss->d[ia].n, ss->d[ib].n, &ss->d[ia]);
+  const int step = ng >= 1 ? ng : cnt;
+  for (int z0 = 0; z0 < cnt; z0 += step) {
+    offt_pass_desc da = ss->d[ia], db = ss->d[ib];
+    if (ng >= 1) {
+      da.nb1 = db.nb1 = cnt - z0 < ng ? cnt - z0 : ng;
+      da.out_keep = 1;
+    }
+    if (be->pass(&da, (const char *)ss->src[ia] + (size_t)z0 * (size_t)da.in_b1_stride * st->esz,
+                 (char *)ss->dst[ia] + (size_t)z0 * (size_t)da.out_b1_stride * st->esz, st->s_compute) ||
+        be->pass(&db, (const char *)ss->src[ib] + (size_t)z0 * (size_t)db.in_b1_stride * st->esz,
+                 (char *)cdst + (size_t)z0 * (size_t)db.out_b1_stride * st->esz, st->s_compute))
+      return -1;
+  }
+  return 0;
+}
+
+/* The fused route on one rank.  1: no such route (the caller takes the generic one).  z-y-x: the inverse of a spectrum is
+ * x in place, y: buf -> W, z: W -> buf, and the forward z: buf -> W, y: W -> out, x in place on out.  The two z passes and the
+ * multiply between them are ONE launch over the lines of W, so the physical fields are never written:
+ *   inverse x in place on a, inverse y  a -> W;    inverse x in place on b, inverse y  b -> W2;
+ *   the fused launch  (W, W2) -> W;
+ *   forward y  W -> out, forward x in place on out with the output scale.
+ * W2 is a second scratch volume like W, made by the first call that has two inputs; without it (no memory) this call and
+ * every later one on the plan run generic.  Squaring needs none.  `out` may be a or b: both are in W and W2 before out is
+ * written. */
+static int execute_product_single(struct _offt_plan *po, void *a, void *b, void *out) {
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  single_sched fw, iv;
+  offt_pass_desc fd;
+  single_schedule(po, out, -1, &fw);
+  single_schedule(po, a, +1, &iv);
+  if (st->prod_w2_failed || !prod_fused_route(po, &fw, &iv, &fd) || iv.pair != 0 || fw.pair != 1) return 1;
+  if (b && !st->prod_w2) {
+    st->prod_w2 = be->dmalloc(st->work_elems * st->esz);
+    if (!st->prod_w2) { st->prod_w2_failed = 1; return 1; }
+  }
+  if (prod_plane_pair(po, &iv, iv.dst[1])) return -1;
+  if (b) {
+    single_schedule(po, b, +1, &iv);
+    if (prod_plane_pair(po, &iv, st->prod_w2)) return -1;
+  }
+  if (be->prod_pass(&fd, st->work, b ? st->prod_w2 : NULL, st->work, st->s_compute)) return -1;
+  return prod_plane_pair(po, &fw, fw.dst[2]);
+}
+
+int offt_hip_execute_product(struct _offt_plan *po, void *a, void *b, void *out) {
+  static const char who[] = "offt_hip_execute_product";
+  hip_state *st = (hip_state *)po->hip_state;
+  const offt_backend *be = st->be;
+  const struct _offt_comm *c = po->comm;
+  conv_begin(po);
+  if (conv_need_device(po, who, a, "the first spectrum", -1, "", 1) || (b && conv_need_device(po, who, b, "the second spectrum", -1, "", 0)) ||
+      conv_need_device(po, who, out, "the output", -1, "", 1) || conv_ready(po, who, be->pointwise_prod != NULL, "pointwise product"))
+    return -1;
+  if (b == a) b = NULL; /* the square: one inverse */
+  const double t0 = conv_enter(po);
+  int rc = st->use_pipeline ? 1 : execute_product_single(po, a, b, out);
+  if (rc > 0) {
+    /* generic: the inverse on every input, unscaled; ONE multiply sweep over the input-layout block into out; the forward on
+     * out, the output scale on its last store.  A half box: the product outside the box is cleared (or not loaded) */
+    const double scale = st->out_scale;
+    st->out_scale = 1.0;
+    rc = conv_inverse(po, a);
+    if (!rc && b) rc = conv_inverse(po, b);
+    st->out_scale = scale;
+    if (!rc) {
+      if (po->is_r2c) /* real rows: scalar strides (offt_hip_fill_input) */
+        rc = be->pointwise_prod(a, b ? b : a, out, st->prec | OFFT_HIPK_PROD_REAL, c->isize[0], c->isize[1], c->isize[2], 2LL * c->istride[0],
+                                2LL * c->istride[1], 1, st->s_compute) ? -1 : 0;
+      else
+        rc = be->pointwise_prod(a, b ? b : a, out, st->prec, c->isize[0], c->isize[1], c->isize[2], c->istride[0], c->istride[1], c->istride[2],
+                                st->s_compute) ? -1 : 0;
+    }
+    if (!rc) rc = half_box_clear(po, out);
+    if (!rc) rc = conv_forward_scaled(po, out);
   }
   return conv_leave(po, t0, rc);
 }

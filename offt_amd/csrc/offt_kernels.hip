@@ -425,6 +425,38 @@ pointwise_sum_k(SumArgs sa, typename vec2<T>::type *out, int n1, int n2, long lo
   }
 }
 
+// out = x * y over a strided box (offt_hipk_pointwise_prod): ONE sweep, non-temporal.  A lane works on W scalars that are
+// contiguous in memory -- EPL complex elements (REAL = false: W = 2 EPL, a complex product per pair) or W real scalars of
+// an r2c plan's rows (REAL = true: offsets and extents count scalars) -- 16 B where the rows allow.  It has loaded both
+// operands before its only store and no other lane touches its scalars: out may be either operand.  y == x (uniform):
+// the square from one load.
+template <typename T, int W>
+struct prod_vec { typedef T type __attribute__((ext_vector_type(W))); };
+template <typename T>
+struct prod_vec<T, 1> { typedef T type; };
+template <typename T, bool REAL, int W>
+__global__ void __launch_bounds__(256)
+pointwise_prod_k(const T *x, const T *y, T *out, int n1, int n2, long long s0, long long s1, long long s2, long long rows) {
+  using VT = typename prod_vec<T, W>::type;
+  constexpr int U = REAL ? 1 : 2;    // scalars per element
+  constexpr int EPL = W / U;         // elements per lane
+  static_assert(W % U == 0 && EPL >= 1, "whole elements per lane");
+  const int i2 = (blockIdx.x * 256 + threadIdx.x) * EPL;
+  if (i2 >= n2) return;
+  const bool square = y == x;
+  for (long long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const long long i1 = r % n1, i0 = r / n1;
+    const long long o = (i0 * s0 + i1 * s1 + (long long)i2 * s2) * U;
+    const VT a = __builtin_nontemporal_load(reinterpret_cast<const VT *>(x + o));
+    const VT b = square ? a : __builtin_nontemporal_load(reinterpret_cast<const VT *>(y + o));
+    VT p;
+    if constexpr (REAL) p = a * b;
+    else if constexpr (W == 2) p = VT{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
+    else p = VT{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x, a.z * b.z - a.w * b.w, a.z * b.w + a.w * b.z};
+    __builtin_nontemporal_store(p, reinterpret_cast<VT *>(out + o));
+  }
+}
+
 // ---------------------------------------------------------------------------
 // shell-binned power / cross spectrum of a strided box (offt_hipk_spectrum_shells): a read-only sweep that ends in a keyed
 // reduction, every floating-point addition in an order fixed by the geometry alone.
@@ -753,6 +785,8 @@ void build_registry() {
   reg_half_mixed_f32();
   reg_half_real_mixed_f64();
   reg_half_real_mixed_f32();
+  reg_prod_f64();
+  reg_prod_f32();
   reg_bluestein_all();
 #endif
 }
@@ -2403,6 +2437,50 @@ int pointwise_sum_launch(const char *who, int nin, const void *const *ins, const
   return 0;
 }
 
+// the product instance for d, or nullptr: strided complex lines without a split, half lines or four-step twiddles, loads
+// and stores through the in_* side; the power-of-two lengths that have a spill-free instance
+Variant *pick_prod(const offt_pass_desc *d) {
+  if (!d || (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32)) return nullptr;
+  if (d->in_contig || d->in_split || d->in_split_nfloor || d->real_input || d->half || d->tw4) return nullptr;
+  return find_variant(VariantKey{d->n, d->precision, false, false, Role::Prod, false, 0});
+}
+
+int pointwise_prod_launch(const char *who, const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0,
+                          long long s1, long long s2, void *stream) {
+  const bool real = (precision & OFFT_HIPK_PROD_REAL) != 0;
+  const int prec = precision & ~OFFT_HIPK_PROD_REAL;
+  if (prec != OFFT_PREC_F64 && prec != OFFT_PREC_F32) { snprintf(g_err, sizeof g_err, "%s: bad precision %d", who, precision); return -1; }
+  if (!x || !out) { snprintf(g_err, sizeof g_err, "%s: a NULL array", who); return -1; }
+  if (!y) y = x;
+  if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
+  const PointRows r(n0, n1, n2, s0, s1, s2);
+  const bool aligned = !((uintptr_t)x & 15) && !((uintptr_t)y & 15) && !((uintptr_t)out & 15);
+  // scalars per lane: 16 B where the rows are unit-stride runs of whole 16-B words on the 16-B grid, else one element
+  int w = real ? 1 : 2;
+  if (real) {
+    const int full = prec == OFFT_PREC_F64 ? 2 : 4;
+    if (aligned && r.st[2] == 1 && !(r.n[2] % full) && !(r.st[1] % full) && !(r.st[0] % full)) w = full;
+  } else if (aligned && r.pair_rows(prec)) w = 4;
+  const int epl = real ? w : w / 2;
+  const dim3 grid((unsigned)((r.n[2] / epl + 255) / 256), (unsigned)(r.rows < 65535 ? r.rows : 65535));
+  hipStream_t sm = (hipStream_t)stream;
+  (void)hipGetLastError();
+#define PROD(T, REAL, W) \
+  hipLaunchKernelGGL((pointwise_prod_k<T, REAL, W>), grid, dim3(256), 0, sm, (const T *)x, (const T *)y, (T *)out, r.n[1], r.n[2], r.st[0], r.st[1], r.st[2], r.rows)
+  if (prec == OFFT_PREC_F64) {
+    if (!real) PROD(double, false, 2);
+    else if (w == 2) PROD(double, true, 2);
+    else PROD(double, true, 1);
+  } else {
+    if (!real) { if (w == 4) PROD(float, false, 4); else PROD(float, false, 2); }
+    else if (w == 4) PROD(float, true, 4);
+    else PROD(float, true, 1);
+  }
+#undef PROD
+  HIPK_CHECK(hipGetLastError());
+  return 0;
+}
+
 // ---- offt_hipk_spectrum_shells: the geometry of a call, worked out on the host ----
 struct ShellGeom {
   ShellArgs sa;      // all but n2l and step, which depend on the elements per lane (shells_grid)
@@ -2589,6 +2667,29 @@ int offt_hipk_conv_pass_sum(const offt_pass_desc *d, const offt_filter_desc *f, 
 int offt_hipk_pointwise_sum(int nin, const void *const *ins, const void *const *filters, void *out, int precision, int kind, int n0, int n1,
                             int n2, long long s0, long long s1, long long s2, void *stream) {
   return pointwise_sum_launch("offt_hipk_pointwise_sum", nin, ins, filters, out, precision, kind, n0, n1, n2, s0, s1, s2, stream);
+}
+
+// ---- pseudo-spectral product (offt_hipk.h) ----
+int offt_hipk_prod_has_fused(const offt_pass_desc *d) { return pick_prod(d) != nullptr; }
+const char *offt_hipk_prod_kernel_name(const offt_pass_desc *d) { return conv_kernel_name(pick_prod(d)); }
+int offt_hipk_prod_pass(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream) {
+  const char *who = "offt_hipk_prod_pass";
+  if (!src0 || !dst) { snprintf(g_err, sizeof g_err, "%s: a NULL array", who); return -1; }
+  Variant *v = pick_prod(d);
+  if (!v) { snprintf(g_err, sizeof g_err, "%s: no fused product kernel for this descriptor (n=%d)", who, d ? d->n : 0); return -1; }
+  if (src1 == src0) src1 = nullptr;  // the square: one load, one inverse
+  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  PassArgs a = pass_args(d, v->cols, true);  // loads and stores through the in_* side, no split
+  void *args[] = {(void *)&a, (void *)&src0, (void *)&src1, (void *)&dst, (void *)&tb.full};
+  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
+                args, (hipStream_t)stream);
+}
+
+int offt_hipk_pointwise_prod(const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0, long long s1,
+                             long long s2, void *stream) {
+  return pointwise_prod_launch("offt_hipk_pointwise_prod", x, y, out, precision, n0, n1, n2, s0, s1, s2, stream);
 }
 
 int offt_hipk_zero_outside(void *buf, int precision, int n0, int n1, int n2, int k0, int k1, int k2, long long s0, long long s1,

@@ -2624,6 +2624,235 @@ fft_conv_sum_half_panelx_k(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>:
 }
 
 // ---------------------------------------------------------------------------
+// Pseudo-spectral product of whole lines (offt_hipk_prod_pass): out = fft( ifft(a) . ifft(b) ), the last pass of two inverse
+// transforms, the pointwise product and the first pass of the forward transform in one launch -- the dual of
+// conv_sum_body.  In the z-y-x layout all three are the z pass over the lines of the scratch volume W[x][z][y], so the lines
+// are STRIDED: a panel is COLS consecutive columns (128-B segments at a pitch of one W line), panel_body's strided / strided
+// addressing and thread mappings:
+//   A  lanes across columns (c = tid % COLS, j = tid / COLS): the loads, the first and the last stage, the stores
+//   B  lanes along the line  (j = tid % TPL,  c = tid / TPL): the middle stage of a three-stage shape
+// Per workgroup, for source 0 and, if there is one, source 1: load the panel conjugated (the inverse as conj(F(conj(.)))), the
+// stages; acc[E] = the first result, then acc[i] *= v[i] -- both in the last stage's register order, and the product is
+// pointwise, so nothing is reordered.  One source: acc[i] *= acc[i], a uniform branch (the two-source form's registers).
+// Then back to the load order.  The last stage leaves a thread the line indices j + m TPL, m < E, of its column, which are
+// the indices it loaded: going back is a renaming of registers at compile time (conj(acc) read in another order), no trip
+// through LDS.  The stages again (forward), scale, store at the load offsets of `dst`.
+// `dst` may be either source: a workgroup owns whole lines and has loaded them from both before its only stores.
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+__device__ __forceinline__ void prod_body(PassArgs a, const typename vec2<T>::type *src0, const typename vec2<T>::type *src1,
+                                          typename vec2<T>::type *dst, const typename vec2<T>::type *twq) {
+  using V2 = typename vec2<T>::type;
+  using Cfg = PanelCfg<N, E, R0, R1, R2, COLS, SPLIT, T>;
+  constexpr int TPL = Cfg::TPL, NT = Cfg::NT, NSTAGE = Cfg::NSTAGE;
+  constexpr int LSTRIDE = Cfg::LSTRIDE;
+  constexpr bool SWZ = Cfg::SWZ;
+  constexpr int PS = SWZ ? Cfg::SWZSHIFT : Cfg::PADSHIFT;
+  static_assert(lanes<T>::n == 1, "one column per lane");
+  static_assert(R0 * R1 * R2 == N, "radices must multiply to N");
+  static_assert(E % R0 == 0 && E % R1 == 0 && E % R2 == 0 && N % E == 0, "bad E");
+  static_assert(NSTAGE > 1, "at least one exchange");
+  constexpr int RL = NSTAGE == 3 ? R2 : R1;  // radix of the last stage
+  constexpr int LRL = ilog2(RL);
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T *exs = reinterpret_cast<T *>(smem);
+  V2 *exv = reinterpret_cast<V2 *>(smem);
+  V2 *tw = reinterpret_cast<V2 *>(smem + Cfg::TW_OFF);
+  V2 *tw1 = reinterpret_cast<V2 *>(smem + Cfg::T1_OFF);
+
+  const int tid = threadIdx.x;
+  for (int i = tid; i < Cfg::QT; i += NT) tw[i] = twq[i];
+  if constexpr (Cfg::USE_T1) {
+    constexpr int M1 = N / (R0 * R1);
+    for (int i = tid; i < Cfg::T1N; i += NT) {
+      const int t = i / R0 + 1, k = i - (t - 1) * R0;
+      tw1[i] = twq[k * M1 * t];
+    }
+  }
+  __syncthreads();  // the twiddle tables are visible (once, ahead of the three runs of the stages)
+
+  const unsigned bid = panel_of_block(blockIdx.x, a.xcd_lim, a.xcd_gshift);
+  const int cp = bid % (unsigned)a.ncp;
+  const unsigned rest = bid / (unsigned)a.ncp;
+  const int b1 = rest % (unsigned)a.nb1;
+  const int b2 = rest / (unsigned)a.nb1;
+  const int c0 = cp * COLS;
+  const int cA = tid % COLS, jA = tid / COLS, jB = tid % TPL, cB = tid / TPL;
+  const bool valid = (c0 + cA) < a.ncols;  // a ragged last column group: lanes past the last column load and store nothing
+  const long long lo = (long long)b1 * a.in_b1 + (long long)b2 * a.in_b2 + (long long)(c0 + cA) * a.in_col + (long long)jA * a.in_axis;
+
+  // a wave owns whole columns in mapping B when TPL divides 64 (see panel_body)
+  constexpr bool WAVE_COLS = (64 % TPL == 0) && (NT % 64 == 0);
+
+  cx<T> v[E];
+
+  // panel_body's stages, strided / strided: from the load distribution in mapping A to the last stage's register order in
+  // mapping A -- v[u RL + bitrev(t)] holds line index jA + u TPL + t N/RL of column cA.  Every exchange has mapping A on one
+  // side at least, so its writes and reads are a workgroup barrier apart.
+  auto stages = [&]() {
+    int c = cA, j = jA;
+    static_for<0, NSTAGE>([&](auto sidx) {
+      constexpr int s = decltype(sidx)::value;
+      constexpr int R = (s == 0) ? R0 : ((s == 1) ? R1 : R2);
+      constexpr int Ns = (s == 0) ? 1 : ((s == 1) ? R0 : R0 * R1);
+      constexpr int NB = E / R;
+      constexpr int LR = ilog2(R);
+      if constexpr (s > 0) {
+        constexpr int M = N / (Ns * R);
+        static_for<0, NB>([&](auto uu) {
+          constexpr int u = decltype(uu)::value;
+          const int q = j + u * TPL;
+          const int km = (q & (Ns - 1)) * M;
+          static_for<1, R>([&](auto tt) {
+            constexpr int t = decltype(tt)::value;
+            T cr, ci;
+            if constexpr (s == 1 && Cfg::USE_T1) {
+              const V2 w = tw1[(t - 1) * R0 + (q & (R0 - 1))];
+              cr = w.x; ci = w.y;
+            } else if constexpr (Cfg::USE_HALF) {
+              const int e = km * t;
+              const V2 w = tw[e & (N / 2 - 1)];
+              const unsigned sm = ((unsigned)e << (32 - ilog2(N))) & 0x80000000u;
+              cr = xor_sign(w.x, sm); ci = xor_sign(w.y, sm);
+            } else {
+              const int e = km * t;
+              const int qd = e / (N / 4);
+              const V2 w = tw[e & (N / 4 - 1)];
+              cr = (qd & 1) ? w.y : w.x;
+              ci = (qd & 1) ? -w.x : w.y;
+              if (qd & 2) { cr = -cr; ci = -ci; }
+            }
+            const cx<T> x = v[u * R + t];
+            v[u * R + t] = cx<T>{x.x * cr - x.y * ci, x.x * ci + x.y * cr};
+          });
+        });
+      }
+      static_for<0, NB>([&](auto uu) { dft_reg<T, R>(&v[decltype(uu)::value * R]); });
+      if constexpr (s < NSTAGE - 1) {
+        constexpr int Rn = (s == 0) ? R1 : R2;
+        constexpr bool next_last = (s + 1 == NSTAGE - 1);
+        const int cn = next_last ? cA : cB, jn = next_last ? jA : jB;  // the reader's mapping
+        auto wr_idx = [&](int u, int t) {
+          const int q = j + u * TPL;
+          const int k = q & (Ns - 1);
+          return c * LSTRIDE + padidx<SWZ, PS>((q - k) * R + k + t * Ns);
+        };
+        auto rd_idx = [&](int u, int t) { return cn * LSTRIDE + padidx<SWZ, PS>(jn + u * TPL + t * (N / Rn)); };
+        if constexpr (s > 0) {
+          // the previous exchange's reads are done: they ran in mapping B, as these writes do
+          if constexpr (WAVE_COLS) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+          } else {
+            __syncthreads();
+          }
+        }
+        if constexpr (SPLIT) {
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].x;
+          });
+          __syncthreads();
+          T re[E];
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            re[decltype(ii)::value] = exs[rd_idx(u, t)];
+          });
+          __syncthreads();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            exs[wr_idx(u, t)] = v[u * R + bitrev(t, LR)].y;
+          });
+          __syncthreads();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            v[decltype(ii)::value] = cx<T>{re[decltype(ii)::value], exs[rd_idx(u, t)]};
+          });
+        } else {
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / R, t = decltype(ii)::value % R;
+            const cx<T> x = v[u * R + bitrev(t, LR)];
+            V2 w; w.x = x.x; w.y = x.y;
+            exv[wr_idx(u, t)] = w;
+          });
+          __syncthreads();
+          static_for<0, E>([&](auto ii) {
+            constexpr int u = decltype(ii)::value / Rn, t = decltype(ii)::value % Rn;
+            const V2 w = exv[rd_idx(u, t)];
+            v[decltype(ii)::value] = cx<T>{w.x, w.y};
+          });
+        }
+        c = cn; j = jn;
+      }
+    });
+  };
+
+  // acc = conj(ifft(src0)) . conj(ifft(src1)) = conj of the product, in the last stage's register order
+  cx<T> acc[E];
+  const int nsrc = src1 ? 2 : 1;
+#pragma nounroll
+  for (int k = 0; k < nsrc; k++) {
+    const V2 *line = (k ? src1 : src0) + lo;
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      constexpr int cn = u * TPL + t * (N / R0);
+      V2 val;
+      val.x = 0; val.y = 0;
+      if (valid) val = gload(line + (long long)cn * a.in_axis);
+      v[decltype(ii)::value] = cx<T>{val.x, -val.y};
+    });
+    stages();
+    if (k == 0) {
+      static_for<0, E>([&](auto ii) { acc[decltype(ii)::value] = v[decltype(ii)::value]; });
+    } else {
+      static_for<0, E>([&](auto ii) {
+        const cx<T> p = acc[decltype(ii)::value], q = v[decltype(ii)::value];
+        acc[decltype(ii)::value] = cx<T>{p.x * q.x - p.y * q.y, p.x * q.y + p.y * q.x};
+      });
+    }
+    __syncthreads();  // this source's last exchange reads done: before the next run of the stages writes its first exchange
+  }
+  if (nsrc == 1) {
+    static_for<0, E>([&](auto ii) {
+      const cx<T> p = acc[decltype(ii)::value];
+      acc[decltype(ii)::value] = cx<T>{p.x * p.x - p.y * p.y, (p.x + p.x) * p.y};
+    });
+  }
+
+  // the product itself, conj(acc), back in the load order: load register u R0 + t holds line index jA + (u + t E/R0) TPL,
+  // and the last stage left that index in register u' RL + bitrev(t') with u' + t' E/RL = u + t E/R0
+  static_for<0, E>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+    constexpr int m = u + t * (E / R0);
+    constexpr int ul = m % (E / RL), tl = m / (E / RL);
+    const cx<T> x = acc[ul * RL + bitrev(tl, LRL)];
+    v[decltype(ii)::value] = cx<T>{x.x, -x.y};
+  });
+
+  stages();
+
+  V2 *sline = dst + lo;
+  const T sc = (T)a.scale;
+  static_for<0, E>([&](auto ii) {
+    constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+    constexpr int cn = u * TPL + t * (N / RL);
+    const cx<T> x = v[u * RL + bitrev(t, LRL)];
+    V2 w;
+    w.x = x.x * sc;
+    w.y = x.y * sc;
+    if (valid) gstore(sline + (long long)cn * a.in_axis, w);
+  });
+}
+
+// (v[E] and acc[E] live together as in conv_sum_body: the same bound on the waves per SIMD)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+__global__ void __launch_bounds__((N / E) * COLS, (conv_sum_wps<T, N, E, R0, R1, R2, COLS, SPLIT>()))
+fft_prod_panel_k(PassArgs a, const typename vec2<T>::type *src0, const typename vec2<T>::type *src1, typename vec2<T>::type *dst,
+                 const typename vec2<T>::type *twq) {
+  prod_body<T, N, E, R0, R1, R2, COLS, SPLIT>(a, src0, src1, dst, twq);
+}
+
+// ---------------------------------------------------------------------------
 // variant registry: every instantiation registers itself under a VariantKey (which kernel it is) and an id
 // ---------------------------------------------------------------------------
 // what an instance does to a line
@@ -2640,6 +2869,8 @@ enum class Role {
   FiltInv,  // inverse x pass with the filter on its loads, src -> dst (offt_hipk_filt_pass_inv): fft_filt_inv_panel_k, fft_filt_inv_panelx_k
   PairYX,   // two passes in one grid (offt_hipk_fft_pass_pair): fft_pair_yx_k, the x pass of one group of planes next to the y pass
             // of the next.  key.n is the y length, the entry's id the x length.
+  Prod,     // pseudo-spectral product (offt_hipk_prod_pass): fft_prod_panel_k, two inverse passes, their product and a forward pass
+            // over strided lines, stored at the load offsets
 };
 // column-pair instances (T = f32x2) are kept under their own precision so that the one-column variants and their ids stay
 // what they were
@@ -2856,6 +3087,14 @@ void reg_variant_conv_sum() {
   add(true, 3, (const void *)fft_conv_sum_half_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, true>);
 }
 
+// pseudo-spectral product (fft_prod_panel_k; offt_reg_prod_*.hip): strided lines on both sides, full lines, no cache-keeping
+// twin; shapes of their own (the accumulator doubles the data registers, as in reg_variant_conv_sum)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+void reg_variant_prod() {
+  add_variant(VariantKey{N, prec_of<T>(), false, false, Role::Prod, false, 0}, panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>(),
+              (const void *)fft_prod_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>, "fft_prod_panel_k", " product");
+}
+
 // filtered forward and filtered inverse (fft_filt_fwd_panel_k, fft_filt_inv_panel_k; offt_reg_spec_*.hip): the shapes of
 // reg_variant_conv, each plain and with cache-keeping stores
 template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
@@ -3012,6 +3251,8 @@ void reg_spec_f64();
 void reg_spec_f32();
 void reg_spec_mixed_f64();
 void reg_spec_mixed_f32();
+void reg_prod_f64();
+void reg_prod_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();
