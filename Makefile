@@ -19,7 +19,8 @@ $(BUILD):
 HIPSRC    := offt_reg_pow2_f32_big offt_kernels offt_reg_pow2_f64 offt_reg_pow2_f64_1024 offt_reg_pair_yx_f64 offt_reg_pow2_f64_anysplit offt_reg_pow2_f32 offt_reg_pow2_f32_anysplit offt_reg_pow2_f32_pair offt_reg_pow2_tw4 offt_reg_mixed_f64_a offt_reg_mixed_f64_b \
              offt_reg_mixed_f64_c offt_reg_mixed_f64_d offt_reg_mixed_f64_e offt_reg_mixed_f32_a offt_reg_mixed_f32_b offt_reg_bluestein offt_reg_bluestein_f32 \
              offt_reg_conv_f64 offt_reg_conv_f32 offt_reg_conv_oop_f64 offt_reg_conv_oop_f32 offt_reg_conv_mixed_f64 offt_reg_conv_mixed_f32 offt_reg_conv_oop_mixed_f64 offt_reg_conv_oop_mixed_f32 offt_reg_conv_sum_f64 offt_reg_conv_sum_f32 offt_reg_conv_sum_mixed_f64 offt_reg_conv_sum_mixed_f32 offt_reg_spec_f64 offt_reg_spec_f32 offt_reg_spec_mixed_f64 offt_reg_spec_mixed_f32 offt_reg_half_f64 offt_reg_half_f32 offt_reg_half_real_f64 offt_reg_half_real_f32 \
-             offt_reg_half_mixed_f64 offt_reg_half_mixed_f32 offt_reg_half_real_mixed_f64 offt_reg_half_real_mixed_f32 offt_reg_prod_f64 offt_reg_prod_f32
+             offt_reg_half_mixed_f64 offt_reg_half_mixed_f32 offt_reg_half_real_mixed_f64 offt_reg_half_real_mixed_f32 offt_reg_prod_f64 offt_reg_prod_f32 \
+             offt_reg_prod_real_f64 offt_reg_prod_real_f32
 HIPOBJ    := $(HIPSRC:%=$(BUILD)/%.o)
 $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/offt_panel.hpp $(CSRC)/offt_bluestein.hpp $(CSRC)/offt_hipk.h $(CSRC)/offt_w32_consts.h $(CSRC)/offt_wr_consts.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.resource_usage.txt || (cat $(BUILD)/$*.resource_usage.txt; false)
@@ -100,6 +101,10 @@ tests/libcpubackend_shells.so: tests/cpu_backend_shells.c tests/cpu_backend_spec
 # ... and with the two entries of the pseudo-spectral product filled and every launch logged (tests/test_product.py)
 tests/libcpubackend_prod.so: tests/cpu_backend_prod.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
 	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_prod.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c -lm
+
+# ... and with the real-row fused launch of the product (prod_pass_real) interpreted from its definition and logged (tests/test_product_real.py)
+tests/libcpubackend_prod_real.so: tests/cpu_backend_prod_real.c tests/cpu_backend_prod.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h
+	$(CC) -std=gnu11 -O2 -fPIC -shared -Ioracle -I$(CSRC) -o $@ tests/cpu_backend_prod_real.c tests/cpu_backend_prod.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c -lm
 
 # ... and with every launch, event and stream operation logged with its stream, and the memory each launch touches (tests/test_streams.py)
 tests/libcpubackend_streams.so: tests/cpu_backend_streams.c tests/cpu_backend_spec.c tests/cpu_backend_sum.c tests/cpu_backend_multi.c tests/cpu_backend_padreal.c tests/cpu_backend_pad.c tests/cpu_backend_conv.c tests/cpu_backend.c oracle/oracle_fft.c oracle/oracle.h offt_amd/csrc/offt_backend.h offt_amd/csrc/offt_hipk.h

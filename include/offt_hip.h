@@ -184,7 +184,8 @@ int offt_hip_spectrum_shells(struct _offt_plan *po, const void *a, const void *b
  * b == NULL or b == a squares the field (one inverse).  `out` may be a, b, or a device buffer of its own of
  * offt_hip_local_bytes(po) bytes that overlaps neither input.  a and b are consumed: their contents are undefined afterwards
  * unless they are `out`.  On an r2c plan the imaginary parts of the plane z = 0 (and z = Nz/2, Nz even) have no effect, as with
- * any c2r inverse.  On a half-box plan the product is formed inside the box and its zero-padded spectrum is returned.
+ * any c2r inverse -- on the fused route too (OFFT_HIP_OPT_PROD_REAL), which drops them before it packs the two spectra into
+ * one transform.  On a half-box plan the product is formed inside the box and its zero-padded spectrum is returned.
  * Stream, async, offt_hip_wait and offt_hip_last_device_seconds (the whole call) as in offt_hip_execute_convolve_sum;
  * offt_hip_last_pass_seconds reports zeros.  Collective on several ranks.  0 on success; -1 with t[ALL] = 99999999 and
  * offt_hip_last_error(), and nothing launched, for a NULL or host-memory a or out, a host-memory b, a backend without the
@@ -192,8 +193,10 @@ int offt_hip_spectrum_shells(struct _offt_plan *po, const void *a, const void *b
 int offt_hip_execute_product(struct _offt_plan *po, void *a, void *b, void *out);
 /* 1 if the call runs the fused route: the inverse's x and y passes per input, ONE launch that runs the inverse z pass of
  * both, multiplies in registers and runs the forward z pass (the physical field is never written), the forward's y and x
- * passes -- one rank, the default z-y-x layout, a complex plan, no half box, a z extent that is a power of two from 64 to
- * 1024, OFFT_HIP_OPT_PROD_FUSED set; 0: the generic route (an inverse per input, one multiply sweep, one forward) */
+ * passes -- one rank, the default z-y-x layout, no half box, a z extent that is a power of two from 64 to 1024,
+ * OFFT_HIP_OPT_PROD_FUSED set, and on a real-input (r2c) plan OFFT_HIP_OPT_PROD_REAL as well (the launch then works on the
+ * half-spectrum lines and yields both real fields from one complex inverse); 0: the generic route (an inverse per input, one
+ * multiply sweep, one forward) */
 int offt_hip_product_fused(const struct _offt_plan *po);
 /* Zero-padded input: the data lives in the box [0,Nx/2) x [0,Ny/2) x [0,Nz/2) (global indices) of the INPUT layout.
  * Forward: whatever else the input block holds is ignored (treated as zero, need not be initialised); the output is the
@@ -306,6 +309,12 @@ int offt_hip_wait(struct _offt_plan *po);
                                           pass are one launch where the plan has that route (offt_hip_product_fused), 0 (default) =
                                           an inverse per input, a multiply sweep, a forward.  Any non-zero value reads back as 1.  Read
                                           by every product call; the results agree to rounding (OFFT_PROD_FUSED) */
+#define OFFT_HIP_OPT_PROD_REAL 25      /* pseudo-spectral product on a real-input (r2c) plan: 1 = together with OFFT_HIP_OPT_PROD_FUSED
+                                          the fused route may run there too -- its one launch works on half-spectrum lines and takes
+                                          both real inverses from one packed complex transform; 0 (default) = an r2c plan keeps the
+                                          generic route whatever OFFT_HIP_OPT_PROD_FUSED says.  Without OFFT_HIP_OPT_PROD_FUSED it has
+                                          no effect; a complex plan does not read it.  Any non-zero value reads back as 1.  Read by
+                                          every product call; the results agree to rounding (OFFT_PROD_REAL) */
 int offt_hip_set_option(struct _offt_plan *po, int option, long long value);
 /* (Launchers that want an exchange-only / compute-only split of a multi-rank execute link the DIAGNOSTICS build,
  *  tools/liboffthip_diag.so = the product compiled with -DOFFT_BENCH_DIAGNOSTICS, which adds

@@ -22,6 +22,7 @@ PARAM_NAMES = ["P1", "T1", "W1", "Px1", "Py1", "Fz", "FP1", "Ux1", "Uz1", "FU1",
 FFTW_ESTIMATE = 1 << 6
 F64, F32 = 0, 1
 FILTER_REAL, FILTER_COMPLEX = 0, 1  # offt_hip.h OFFT_HIP_FILTER_REAL / OFFT_HIP_FILTER_COMPLEX
+OPT_PROD_REAL = 25  # offt_hip.h OFFT_HIP_OPT_PROD_REAL: with OPT_PROD_FUSED, the pseudo-spectral product of a real-input (r2c) plan may run the fused route (half-spectrum lines, both real inverses from one packed complex transform)
 OPT_PROD_FUSED = 24  # offt_hip.h OFFT_HIP_OPT_PROD_FUSED: the pseudo-spectral product may run the route whose one launch carries both inverse z passes, the multiply and the forward z pass
 OPT_ZGROUP_CHAINS = 23  # (22 is unassigned) offt_hip.h OFFT_HIP_OPT_ZGROUP_CHAINS: 2 = the pipelined plane groups as two chains on two streams (even / odd groups; the default where the library sizes the groups), 1 = one chain
 OPT_SPEC_MIXED = 21  # offt_hip.h OFFT_HIP_OPT_SPEC_MIXED: with OPT_SPEC_FUSED, the filtered forward / inverse of a plan whose x extent is no power of two may run the fused route

@@ -102,6 +102,11 @@ typedef struct offt_backend {
   int (*prod_pass)(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream);
   int (*pointwise_prod)(const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0, long long s1, long long s2,
                         void *stream);
+  /* ---- ... of real fields on a real-input plan (OFFT_HIP_OPT_PROD_REAL); appended at the end, so that every older table
+   * leaves it NULL and its r2c plans keep the generic route ----
+   * prod_pass_real: offt_hipk_prod_real_pass -- the fused launch over lines that are half spectra: `d` is the real-output z
+   * pass of the inverse (real_input = 2, n the real length, n/2+1 complex values a line through the in_* side). */
+  int (*prod_pass_real)(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream);
 } offt_backend;
 
 void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);
@@ -110,7 +115,7 @@ void offt_hip_test_set_backend(const offt_backend *b, int rank, int size);
 const offt_backend *offt_hip_test_hip_backend_no_conv_sum(void);
 /* ... and with filt_pass_fwd and filt_pass_inv withheld: the generic route of the two filtered calls on the device */
 const offt_backend *offt_hip_test_hip_backend_no_filt(void);
-/* ... and with prod_pass withheld: the generic route of the pseudo-spectral product on the device */
+/* ... and with prod_pass and prod_pass_real withheld: the generic route of the pseudo-spectral product on the device */
 const offt_backend *offt_hip_test_hip_backend_no_prod(void);
 
 /* keep the HIP backend but route the exchange through `fn` (called with the comm stream

@@ -313,6 +313,20 @@ int offt_hipk_prod_pass(const offt_pass_desc *d, const void *src0, const void *s
 int offt_hipk_prod_has_fused(const offt_pass_desc *d);
 /* "fft_prod_panel_k", or "no fused kernel" */
 const char *offt_hipk_prod_kernel_name(const offt_pass_desc *d);
+/* ... of REAL fields held as half spectra, the z pass of a real-input (r2c) plan.  `d` is the real-output z pass of the
+ * complex-to-real inverse as the schedule states it: real_input = 2, n the REAL length, a line the n/2+1 complex values of a
+ * half spectrum at a pitch of in_axis_stride, !in_contig, no split, no half lines, no four-step twiddles; loads and stores
+ * through the in_* side.  Per line: the Hermitian extension of the line of src0 and of src1 (X~[k] = X[k] for k <= n/2,
+ * conj(X[n - k]) above; the imaginary parts of X[0] and X[n/2] have no effect), the two unnormalised real inverses -- from ONE
+ * complex transform of A~ + i B~ --, their product (src1 NULL or == src0: the square), the forward transform, times
+ * d->scale; the elements k <= n/2 stored to `dst` at the load offsets, nothing else of the line's pitch written.  `dst` may be
+ * either source; a source that is not `dst` is not written.  Power-of-two real lengths of 64 ... 1024.  -1, nothing launched:
+ * no such kernel, a NULL src0 or dst. */
+int offt_hipk_prod_real_pass(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream);
+/* 1 if offt_hipk_prod_real_pass has a kernel for d; the registry lookup needs no device */
+int offt_hipk_prod_real_has_fused(const offt_pass_desc *d);
+/* "fft_prod_real_panel_k", or "no fused kernel" */
+const char *offt_hipk_prod_real_kernel_name(const offt_pass_desc *d);
 /* out[i0 s0 + i1 s1 + i2 s2] = x[same] * y[same] over the box n0 x n1 x n2: complex elements of `precision`, or, with
  * OFFT_HIPK_PROD_REAL or-ed into it, real scalars (the rows of an r2c plan; strides and extents then count scalars).  y NULL
  * or == x: the square, from one load.  `out` may be either operand: a lane loads both before its only store.  ONE sweep,

@@ -47,6 +47,8 @@ const char *offt_hip_last_error(void) { return g_err; }
 /* default of OFFT_HIP_OPT_PROD_FUSED: 0 until the fused route is ahead of the generic one by more than the run-to-run spread
  * at every measured size in both precisions (profiles/product.txt) */
 #define OFFT_PROD_FUSED_DEFAULT 0
+/* default of OFFT_HIP_OPT_PROD_REAL (the fused route on real-input plans, on top of the option above): 0 by the same rule */
+#define OFFT_PROD_REAL_DEFAULT 0
 #define SET_ERR(...)                                 \
   do {                                               \
     snprintf(g_err, sizeof g_err, __VA_ARGS__);      \
@@ -481,6 +483,8 @@ typedef struct hip_state {
     int prod_fused;      /* pseudo-spectral product: 1 = the fused route (one launch for both inverse z passes, the multiply and the
                           * forward z pass) where the plan has one (prod_fused_route), 0 = inverses, a multiply sweep, a forward
                           * (OFFT_HIP_OPT_PROD_FUSED) */
+    int prod_real;       /* pseudo-spectral product: 1 = together with prod_fused the fused route may run on a real-input plan, its
+                          * launch working on half-spectrum lines (OFFT_HIP_OPT_PROD_REAL) */
     int block_pad;      /* exchange volumes: per-peer / per-chunk blocks padded against HBM channel aliasing */
     double exec_timeout_s, p2p_timeout_s;
   } opt;
@@ -782,6 +786,11 @@ static int hb_prod_pass(const offt_pass_desc *d, const void *src0, const void *s
   if (rc) SET_ERR("fused product pass failed: %s", offt_hipk_last_error());
   return rc;
 }
+static int hb_prod_pass_real(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream) {
+  const int rc = offt_hipk_prod_real_pass(d, src0, src1, dst, stream);
+  if (rc) SET_ERR("fused real product pass failed: %s", offt_hipk_last_error());
+  return rc;
+}
 static int hb_pointwise_prod(const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0, long long s1,
                              long long s2, void *stream) {
   const int rc = offt_hipk_pointwise_prod(x, y, out, precision, n0, n1, n2, s0, s1, s2, stream);
@@ -793,14 +802,15 @@ static const offt_backend k_hip_backend = {
     hb_event_destroy, hb_event_record, hb_stream_wait, hb_stream_sync, hb_event_ms, hb_a2a, hb_memcpy_dd, hb_upload,
     hb_peer_open, hb_peer_close, hb_flag_alloc, hb_flag_free, hb_flag_signal, hb_flag_wait, hb_conv_pass, hb_pointwise, hb_zero_outside,
     hb_conv_pass_oop, hb_pointwise_oop, hb_conv_pass_sum, hb_pointwise_sum, hb_filt_pass_fwd, hb_filt_pass_inv, hb_spectrum_shells, hb_pass_pair,
-    hb_prod_pass, hb_pointwise_prod};
+    hb_prod_pass, hb_pointwise_prod, hb_prod_pass_real};
 #ifdef OFFT_TEST_SEAMS
-/* the HIP backend without the fused product launch: the generic route of offt_hip_execute_product on the device (tests compare
+/* the HIP backend without the fused product launches: the generic route of offt_hip_execute_product on the device (tests compare
  * the two routes, tools/conv_probe.py times them) */
 const offt_backend *offt_hip_test_hip_backend_no_prod(void) {
   static offt_backend b;
   b = k_hip_backend;
   b.prod_pass = NULL;
+  b.prod_pass_real = NULL;
   return &b;
 }
 /* the HIP backend without its fused multi-input launch, for offt_hip_test_set_backend: a plan made under it takes the generic
@@ -1392,6 +1402,7 @@ struct _offt_plan *offt_3d_init_ex(int Nx, int Ny, int Nz, void *in, void *out, 
   st->opt.conv_sum_mixed = getenv("OFFT_CONV_SUM_MIXED") && atoi(getenv("OFFT_CONV_SUM_MIXED")) != 0;
   st->opt.spec_fused = getenv("OFFT_SPEC_FUSED") ? atoi(getenv("OFFT_SPEC_FUSED")) != 0 : OFFT_SPEC_FUSED_DEFAULT;
   st->opt.prod_fused = getenv("OFFT_PROD_FUSED") ? atoi(getenv("OFFT_PROD_FUSED")) != 0 : OFFT_PROD_FUSED_DEFAULT;
+  st->opt.prod_real = getenv("OFFT_PROD_REAL") ? atoi(getenv("OFFT_PROD_REAL")) != 0 : OFFT_PROD_REAL_DEFAULT;
   st->opt.spec_mixed = getenv("OFFT_SPEC_MIXED") && atoi(getenv("OFFT_SPEC_MIXED")) != 0;
   /* (off by default: measured, it buys nothing -- the power-of-two block pitches are NOT what holds K1 / K2 back,
    * profiles/r03_rehearse_block_pad_ab.txt; OFFT_BLOCK_PAD=1 turns it on) */
@@ -1879,6 +1890,7 @@ int offt_hip_set_option(struct _offt_plan *po, int option, long long value) {
     case OFFT_HIP_OPT_SPEC_FUSED: st->opt.spec_fused = value != 0; break; /* read by every filtered forward / inverse (spec_fused_route) */
     case OFFT_HIP_OPT_SPEC_MIXED: st->opt.spec_mixed = value != 0; break; /* likewise */
     case OFFT_HIP_OPT_PROD_FUSED: st->opt.prod_fused = value != 0; break; /* read by every product call (prod_fused_route) */
+    case OFFT_HIP_OPT_PROD_REAL: st->opt.prod_real = value != 0; break;   /* likewise */
     case OFFT_HIP_OPT_ZGROUP_MIB: st->opt.zgroup_mib = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_STREAMS: st->opt.zgroup_streams = (int)value; break;
     case OFFT_HIP_OPT_ZGROUP_PIPELINE: st->opt.zgroup_pipeline = value != 0; st->opt.zgroup_pipeline_set = 1; break;
@@ -1930,6 +1942,7 @@ long long offt_hip_get_option(const struct _offt_plan *po, int option) {
     case OFFT_HIP_OPT_CONV_SUM_MIXED: return st->opt.conv_sum_mixed;
     case OFFT_HIP_OPT_SPEC_FUSED: return st->opt.spec_fused;
     case OFFT_HIP_OPT_PROD_FUSED: return st->opt.prod_fused;
+    case OFFT_HIP_OPT_PROD_REAL: return st->opt.prod_real;
     case OFFT_HIP_OPT_SPEC_MIXED: return st->opt.spec_mixed;
     case OFFT_HIP_OPT_K1_STREAMS: return st->k1_streams;
     case OFFT_HIP_OPT_EXEC_TIMEOUT_S: return (long long)st->opt.exec_timeout_s;
@@ -3862,15 +3875,19 @@ int offt_hip_execute_inverse_filtered(struct _offt_plan *po, const void *spec, i
 
 /* ---- pseudo-spectral product: the dual of a convolve (two inverses, a multiply in physical space, a forward), with the
  * convolve calls' entry, exit and refusals ---- */
-/* The fused route: one rank, the z-y-x layout, a complex plan, no half box, OFFT_HIP_OPT_PROD_FUSED, the backend entry and a
- * kernel for the z extent (powers of two from 64 to 1024).  The inverse's last pass and the forward's first are both the z
- * pass over the lines of the scratch volume W[x][z][y]: the forward must store where the inverse loads, with the same
- * addressing (it does where the inverse is the forward mirrored, single_schedule).  *fd: the fused launch's descriptor, the
- * inverse's z pass -- loads and stores through its input side, scale 1.  0: the generic route. */
+/* The fused route: one rank, the z-y-x layout, no half box, OFFT_HIP_OPT_PROD_FUSED, the backend entry and a kernel for the z
+ * extent (powers of two from 64 to 1024).  A real-input plan needs OFFT_HIP_OPT_PROD_REAL as well and the backend's
+ * prod_pass_real: its launch works on the half-spectrum lines the real-output z pass loads.  The inverse's last pass and the
+ * forward's first are both the z pass over the lines of the scratch volume W[x][z][y]: the forward must store where the
+ * inverse loads, with the same addressing (it does where the inverse is the forward mirrored, single_schedule; on a
+ * real-input plan the real-input z pass stores the Nz/2+1 values of a line exactly where the real-output one loads them).
+ * *fd: the fused launch's descriptor, the inverse's z pass -- loads and stores through its input side, scale 1.  0: the
+ * generic route. */
 static int prod_fused_route(struct _offt_plan *po, const single_sched *fw, const single_sched *iv, offt_pass_desc *fd) {
   hip_state *st = (hip_state *)po->hip_state;
   const offt_pass_desc *z = &iv->d[2], *f0 = &fw->d[0];
-  if (st->use_pipeline || !fw->zyx || po->is_r2c || st->half_box || !st->opt.prod_fused || !st->be->prod_pass) return 0;
+  if (st->use_pipeline || !fw->zyx || st->half_box || !st->opt.prod_fused) return 0;
+  if (po->is_r2c ? !(st->opt.prod_real && st->be->prod_pass_real) : !st->be->prod_pass) return 0;
   if (fw->dst[0] != iv->src[2] || f0->n != z->n || f0->ncols != z->ncols || f0->nb1 != z->nb1 || f0->nb2 != z->nb2 ||
       f0->out_axis_stride != z->in_axis_stride || f0->out_col_stride != z->in_col_stride || f0->out_b1_stride != z->in_b1_stride ||
       f0->out_b2_stride != z->in_b2_stride || f0->out_contig != z->in_contig || f0->out_split != z->in_split)
@@ -3878,7 +3895,7 @@ static int prod_fused_route(struct _offt_plan *po, const single_sched *fw, const
   *fd = *z;
   fd->scale = 1.0;
   fd->out_keep = 0;
-  return offt_hipk_prod_has_fused(fd);
+  return po->is_r2c ? offt_hipk_prod_real_has_fused(fd) : offt_hipk_prod_has_fused(fd);
 }
 
 int offt_hip_product_fused(const struct _offt_plan *po) {
@@ -3922,6 +3939,8 @@ static int prod_plane_pair(struct _offt_plan *po, const single_sched *ss, void *
  *   inverse x in place on a, inverse y  a -> W;    inverse x in place on b, inverse y  b -> W2;
  *   the fused launch  (W, W2) -> W;
  *   forward y  W -> out, forward x in place on out with the output scale.
+ * A real-input plan (OFFT_HIP_OPT_PROD_REAL) runs the same launches: its x and y passes work on the Nz/2+1 planes of the half
+ * spectrum, and the fused launch is prod_pass_real over lines of Nz/2+1 values.
  * W2 is a second scratch volume like W, made by the first call that has two inputs; without it (no memory) this call and
  * every later one on the plan run generic.  Squaring needs none.  `out` may be a or b: both are in W and W2 before out is
  * written. */
@@ -3942,7 +3961,7 @@ static int execute_product_single(struct _offt_plan *po, void *a, void *b, void 
     single_schedule(po, b, +1, &iv);
     if (prod_plane_pair(po, &iv, st->prod_w2)) return -1;
   }
-  if (be->prod_pass(&fd, st->work, b ? st->prod_w2 : NULL, st->work, st->s_compute)) return -1;
+  if ((po->is_r2c ? be->prod_pass_real : be->prod_pass)(&fd, st->work, b ? st->prod_w2 : NULL, st->work, st->s_compute)) return -1;
   return prod_plane_pair(po, &fw, fw.dst[2]);
 }
 

@@ -787,6 +787,8 @@ void build_registry() {
   reg_half_real_mixed_f32();
   reg_prod_f64();
   reg_prod_f32();
+  reg_prod_real_f64();
+  reg_prod_real_f32();
   reg_bluestein_all();
 #endif
 }
@@ -2445,6 +2447,14 @@ Variant *pick_prod(const offt_pass_desc *d) {
   return find_variant(VariantKey{d->n, d->precision, false, false, Role::Prod, false, 0});
 }
 
+// ... and the one for real fields held as half spectra: d is the real-output z pass of a complex-to-real inverse as it is
+// (real_input = 2, n the real length, lines of n/2+1 complex values through the in_* side), strided, no split, no half box
+Variant *pick_prod_real(const offt_pass_desc *d) {
+  if (!d || (d->precision != OFFT_PREC_F64 && d->precision != OFFT_PREC_F32)) return nullptr;
+  if (d->in_contig || d->in_split || d->in_split_nfloor || d->real_input != 2 || d->half || d->tw4) return nullptr;
+  return find_variant(VariantKey{d->n, d->precision, false, false, Role::ProdReal, false, 0});
+}
+
 int pointwise_prod_launch(const char *who, const void *x, const void *y, void *out, int precision, int n0, int n1, int n2, long long s0,
                           long long s1, long long s2, void *stream) {
   const bool real = (precision & OFFT_HIPK_PROD_REAL) != 0;
@@ -2677,6 +2687,23 @@ int offt_hipk_prod_pass(const offt_pass_desc *d, const void *src0, const void *s
   if (!src0 || !dst) { snprintf(g_err, sizeof g_err, "%s: a NULL array", who); return -1; }
   Variant *v = pick_prod(d);
   if (!v) { snprintf(g_err, sizeof g_err, "%s: no fused product kernel for this descriptor (n=%d)", who, d ? d->n : 0); return -1; }
+  if (src1 == src0) src1 = nullptr;  // the square: one load, one inverse
+  if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
+  Tables tb;
+  if (get_tables(d->n, d->precision, tb, false)) return -1;
+  PassArgs a = pass_args(d, v->cols, true);  // loads and stores through the in_* side, no split
+  void *args[] = {(void *)&a, (void *)&src0, (void *)&src1, (void *)&dst, (void *)&tb.full};
+  return launch(who, v->fn, nullptr, &v->attr_set, v->lds, v->lds, v->threads, (long long)a.ncp * d->nb1 * d->nb2, &a.xcd_lim, &a.xcd_gshift,
+                args, (hipStream_t)stream);
+}
+
+int offt_hipk_prod_real_has_fused(const offt_pass_desc *d) { return pick_prod_real(d) != nullptr; }
+const char *offt_hipk_prod_real_kernel_name(const offt_pass_desc *d) { return conv_kernel_name(pick_prod_real(d)); }
+int offt_hipk_prod_real_pass(const offt_pass_desc *d, const void *src0, const void *src1, void *dst, void *stream) {
+  const char *who = "offt_hipk_prod_real_pass";
+  if (!src0 || !dst) { snprintf(g_err, sizeof g_err, "%s: a NULL array", who); return -1; }
+  Variant *v = pick_prod_real(d);
+  if (!v) { snprintf(g_err, sizeof g_err, "%s: no fused real product kernel for this descriptor (n=%d)", who, d ? d->n : 0); return -1; }
   if (src1 == src0) src1 = nullptr;  // the square: one load, one inverse
   if (d->ncols < 1 || d->nb1 < 1 || d->nb2 < 1) return 0;
   Tables tb;

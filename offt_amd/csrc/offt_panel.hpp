@@ -2638,7 +2638,18 @@ fft_conv_sum_half_panelx_k(PassArgs a, ConvArgs f, SumArgs sa, typename vec2<T>:
 // the indices it loaded: going back is a renaming of registers at compile time (conj(acc) read in another order), no trip
 // through LDS.  The stages again (forward), scale, store at the load offsets of `dst`.
 // `dst` may be either source: a workgroup owns whole lines and has loaded them from both before its only stores.
-template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT>
+//
+// REAL (offt_hipk_prod_real_pass, fft_prod_real_panel_k): the lines are HALF SPECTRA of real fields -- N is the real length, a
+// line in memory the N/2+1 complex values at a pitch of in_axis.  Both inverses ride on ONE complex FFT: with A~, B~ the
+// Hermitian extensions (X~[n] = X[n] for n <= N/2, conj(X[N - n]) above), Z = A~ + i B~ has the unnormalised inverse a + i b,
+// a and b the two real fields.  The stages get conj(Z) and leave v = a - i b, so the product is p = -v.x v.y: no accumulator
+// array and no barrier between sources.  One source: Z = A~, v = (a, 0), p = v.x^2.  The imaginary parts of X[0] and X[N/2]
+// are DROPPED before packing: the separate real-output passes discard them with their imaginary output, here Im A[0] would
+// end up in field b and Im B[0] in field a.  The mirrored half re-reads what the workgroup loads for its own half anyway
+// (panel_body's C2R load: a per-lane base plus a uniform offset for either half, default cache policy so that the second
+// read is an L2 hit).  (p, 0) goes back to the load order by the same renaming, the stages run again, and only the indices
+// n <= N/2 are stored.
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, bool REAL = false>
 __device__ __forceinline__ void prod_body(PassArgs a, const typename vec2<T>::type *src0, const typename vec2<T>::type *src1,
                                           typename vec2<T>::type *dst, const typename vec2<T>::type *twq) {
   using V2 = typename vec2<T>::type;
@@ -2787,6 +2798,70 @@ __device__ __forceinline__ void prod_body(PassArgs a, const typename vec2<T>::ty
     });
   };
 
+  if constexpr (REAL) {
+    static_assert(TPL <= N / 2 && (N / 2) % TPL == 0, "the line's halves are whole rows of registers");
+    // element (u, t) is line index n = jA + cn: the stored value at n for n <= N/2, the conjugate of the one at N - n above
+    // -- N - n = -jA + a uniform N - cn, so the mirrored half has a per-lane base of its own
+    const long long lm = lo - 2LL * jA * a.in_axis;
+    auto load_packed = [&](auto two_) {
+      constexpr bool TWO = decltype(two_)::value;
+      static_for<0, E>([&](auto ii) {
+        constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+        constexpr int cn = u * TPL + t * (N / R0);
+        const bool low = (jA + cn) <= N / 2;
+        const bool end = (cn == 0 || cn == N / 2) && jA == 0;  // n = 0 or N/2: real by symmetry, the stored imaginary part dropped
+        const long long off = low ? lo + (long long)cn * a.in_axis : lm + (long long)(N - cn) * a.in_axis;
+        V2 x, y;
+        x.x = 0; x.y = 0; y.x = 0; y.y = 0;
+        if (valid) {
+          x = src0[off];
+          if constexpr (TWO) y = src1[off];
+        }
+        const T ai = end ? (T)0 : (low ? x.y : -x.y);
+        if constexpr (TWO) {
+          const T bi = end ? (T)0 : (low ? y.y : -y.y);
+          v[decltype(ii)::value] = cx<T>{x.x - bi, -(ai + y.x)};  // conj(A~ + i B~)
+        } else {
+          v[decltype(ii)::value] = cx<T>{x.x, -ai};
+        }
+      });
+    };
+    const bool two = src1 != nullptr;
+    if (two) load_packed(std::true_type{});
+    else load_packed(std::false_type{});
+
+    stages();
+
+    // v = a - i b (one source: (a, 0)); the product (p, 0) back in the load order, by prod_body's renaming of registers
+    T p[E];
+    if (two) static_for<0, E>([&](auto ii) { p[decltype(ii)::value] = -(v[decltype(ii)::value].x * v[decltype(ii)::value].y); });
+    else static_for<0, E>([&](auto ii) { p[decltype(ii)::value] = v[decltype(ii)::value].x * v[decltype(ii)::value].x; });
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / R0, t = decltype(ii)::value % R0;
+      constexpr int m = u + t * (E / R0);
+      constexpr int ul = m % (E / RL), tl = m / (E / RL);
+      v[decltype(ii)::value] = cx<T>{p[ul * RL + bitrev(tl, LRL)], (T)0};
+    });
+    __syncthreads();  // the inverse's last exchange reads done: before the forward's first exchange writes
+
+    stages();
+
+    // the half spectrum of the product: indices n <= N/2 only (n = N/2 is row cn = N/2 of the lanes with jA = 0)
+    V2 *sline = dst + lo;
+    const T sc = (T)a.scale;
+    static_for<0, E>([&](auto ii) {
+      constexpr int u = decltype(ii)::value / RL, t = decltype(ii)::value % RL;
+      constexpr int cn = u * TPL + t * (N / RL);
+      if constexpr (cn > N / 2) return;
+      const cx<T> x = v[u * RL + bitrev(t, LRL)];
+      V2 w;
+      w.x = x.x * sc;
+      w.y = x.y * sc;
+      if (valid && (cn < N / 2 || jA == 0)) gstore(sline + (long long)cn * a.in_axis, w);
+    });
+    return;
+  }
+
   // acc = conj(ifft(src0)) . conj(ifft(src1)) = conj of the product, in the last stage's register order
   cx<T> acc[E];
   const int nsrc = src1 ? 2 : 1;
@@ -2852,6 +2927,18 @@ fft_prod_panel_k(PassArgs a, const typename vec2<T>::type *src0, const typename 
   prod_body<T, N, E, R0, R1, R2, COLS, SPLIT>(a, src0, src1, dst, twq);
 }
 
+// (one v[E] and no accumulator: bounded like the fused convolution, which runs its stages twice over one array as well;
+//  WPS = 0 asks for that bound, anything else states the waves per SIMD of an instance -- offt_reg_prod_real_*.hip)
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, int WPS>
+constexpr int prod_real_wps() { return WPS > 0 ? WPS : conv_wps<T, N, E, R0, R1, R2, COLS, SPLIT>(); }
+
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, int WPS = 0>
+__global__ void __launch_bounds__((N / E) * COLS, (prod_real_wps<T, N, E, R0, R1, R2, COLS, SPLIT, WPS>()))
+fft_prod_real_panel_k(PassArgs a, const typename vec2<T>::type *src0, const typename vec2<T>::type *src1, typename vec2<T>::type *dst,
+                      const typename vec2<T>::type *twq) {
+  prod_body<T, N, E, R0, R1, R2, COLS, SPLIT, true>(a, src0, src1, dst, twq);
+}
+
 // ---------------------------------------------------------------------------
 // variant registry: every instantiation registers itself under a VariantKey (which kernel it is) and an id
 // ---------------------------------------------------------------------------
@@ -2871,6 +2958,8 @@ enum class Role {
             // of the next.  key.n is the y length, the entry's id the x length.
   Prod,     // pseudo-spectral product (offt_hipk_prod_pass): fft_prod_panel_k, two inverse passes, their product and a forward pass
             // over strided lines, stored at the load offsets
+  ProdReal, // ... of real fields held as half spectra (offt_hipk_prod_real_pass): fft_prod_real_panel_k, key.n the REAL length, lines
+            // of n/2+1 complex values, both inverses from one packed complex FFT
 };
 // column-pair instances (T = f32x2) are kept under their own precision so that the one-column variants and their ids stay
 // what they were
@@ -3094,6 +3183,12 @@ void reg_variant_prod() {
   add_variant(VariantKey{N, prec_of<T>(), false, false, Role::Prod, false, 0}, panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>(),
               (const void *)fft_prod_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT>, "fft_prod_panel_k", " product");
 }
+// ... of real fields (fft_prod_real_panel_k; offt_reg_prod_real_*.hip): N the real length.  WPS: prod_real_wps
+template <typename T, int N, int E, int R0, int R1, int R2, int COLS, bool SPLIT, int WPS = 0>
+void reg_variant_prod_real() {
+  add_variant(VariantKey{N, prec_of<T>(), false, false, Role::ProdReal, false, 0}, panel_shape<T, N, E, R0, R1, R2, COLS, SPLIT>(),
+              (const void *)fft_prod_real_panel_k<T, N, E, R0, R1, R2, COLS, SPLIT, WPS>, "fft_prod_real_panel_k", " real product");
+}
 
 // filtered forward and filtered inverse (fft_filt_fwd_panel_k, fft_filt_inv_panel_k; offt_reg_spec_*.hip): the shapes of
 // reg_variant_conv, each plain and with cache-keeping stores
@@ -3253,6 +3348,8 @@ void reg_spec_mixed_f64();
 void reg_spec_mixed_f32();
 void reg_prod_f64();
 void reg_prod_f32();
+void reg_prod_real_f64();
+void reg_prod_real_f32();
 void reg_half_f64();
 void reg_half_f32();
 void reg_half_real_f64();

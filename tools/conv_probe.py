@@ -49,7 +49,14 @@ output block filled with random numbers, next to the in-place REAL offt_hipk_poi
 point in double precision against the call's 16 B).  The two ALTERNATE after a warm-up, MIXED_REPS times each, device time by
 events on one stream; the line reports min and median of both, their ratio (the condition: below 1; the byte model: 0.4) and
 the call's rate over the bytes it reads.
-usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:|shells:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
+A spec with the prefix prod: measures offt_hip_execute_product (two spectra, out = the first) on one plan and the same buffers:
+the fused route (OFFT_HIP_OPT_PROD_FUSED and, for prod:r2c:, OFFT_HIP_OPT_PROD_REAL set), the call's own generic route (a
+second plan made under the HIP backend with prod_pass / prod_pass_real withheld, a seam of tests/liboffthip_test.so) and the
+caller's route (two offt_3d_execute_dir(+1), a torch multiply, one offt_3d_execute).  The call consumes its inputs, so every
+run starts from copies made outside the timed region.  The three ALTERNATE after a warm-up, MIXED_REPS times each, and the line
+reports min and median of all three, the ratios against both, each baseline's own spread (median / min - 1) and the byte
+model of DESIGN.md 4.5 (240 / 336 per point in f64, per half-spectrum point on an r2c plan: a model, not a measurement).
+usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:|shells:|prod:][half:][f64|f32|r2c:]N ... [--zgroup-mib M]
        (default: 1024 f32:1024 r2c:512 mixed:768 mixed:f32:768 mixed:1000 mixed:f32:1000 mixed:half:768;
         the multi: set of profiles/conv_multi.txt: multi:512 multi:1024 multi:f32:1024 multi:r2c:512 multi:half:512;
         the multi:mixed: set of profiles/conv_multi_mixed.txt: multi:mixed:768 multi:mixed:f32:768 multi:mixed:1000
@@ -61,7 +68,9 @@ usage: conv_probe.py [mixed:|multi:|multi:mixed:|sum:|sum:mixed:|spec:|shells:][
         the spec: set of profiles/spec_filtered.txt: spec:512 spec:f32:512 spec:1024 spec:f32:1024 spec:r2c:512 spec:r2c:f32:512;
         the spec: set of profiles/spec_filtered_mixed.txt: spec:768 spec:f32:768 spec:1000 spec:f32:1000 spec:r2c:768;
         the shells: set of profiles/spectrum_shells.txt: shells:512 shells:f32:512 shells:r2c:512 shells:r2c:f32:512 shells:1024
-        shells:f32:1024 shells:r2c:1024 shells:r2c:f32:1024)"""
+        shells:f32:1024 shells:r2c:1024 shells:r2c:f32:1024;
+        the prod: set of profiles/product.txt: prod:64 prod:128 prod:256 prod:512 prod:1024 prod:f32:1024 and the same with
+        prod:r2c: (prod:r2c:64 ... prod:r2c:1024 prod:r2c:f32:1024))"""
 import ctypes as C
 import os
 import sys
@@ -72,8 +81,8 @@ import torch  # noqa: E402
 
 from offt_amd import api  # noqa: E402
 
-if any((a.startswith("sum:") and not a.startswith("sum:mixed:")) or a.startswith("spec:") for a in sys.argv[1:]):
-    # the sum: and spec: specs time the generic route as well, which needs the build with the test seams (the same kernel objects)
+if any((a.startswith("sum:") and not a.startswith("sum:mixed:")) or a.startswith("spec:") or a.startswith("prod:") for a in sys.argv[1:]):
+    # the sum:, spec: and prod: specs time the generic route as well, which needs the build with the test seams (the same kernel objects)
     api.use_library(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "liboffthip_test.so"))
 L = api.lib()
 REPS = int(os.environ.get("CONV_PROBE_REPS", "5"))
@@ -265,6 +274,87 @@ def probe_spec(rest, zg):
     torch.cuda.empty_cache()
 
 
+def probe_prod(rest, zg):
+    """prod:[r2c:][f64|f32:]N -- offt_hip_execute_product (two spectra, out = the first), three routes on the same buffers"""
+    r2c = rest.startswith("r2c:")
+    kind, _, n_s = rest[(4 if r2c else 0):].rpartition(":")
+    n = int(n_s)
+    prec = api.F32 if kind == "f32" else api.F64
+    T = api.lib()
+    T.offt_hip_test_hip_backend_no_prod.restype = C.c_void_p
+    T.offt_hip_test_set_backend.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    plans = {}
+    for name in ("generic", "fused"):  # the plan made under the table without the fused launches first, then the product's own
+        T.offt_hip_test_set_backend(T.offt_hip_test_hip_backend_no_prod() if name == "generic" else None, 0, 1)
+        po = plans[name] = api.offt_3d_init(n, n, n, precision=prec, is_r2c=int(r2c))
+        if zg is not None:
+            T.offt_hip_set_option(po, OPT_ZGROUP_MIB, zg)
+        T.offt_hip_set_option(po, api.OPT_PROD_FUSED, 1)
+        T.offt_hip_set_option(po, api.OPT_PROD_REAL, 1)  # (a complex plan does not read it)
+    po = plans["fused"]
+    stream = torch.cuda.Stream()  # one stream for both plans, the caller's multiply, the copies and the timing events
+    for p in plans.values():
+        T.offt_hip_set_stream(p, stream.cuda_stream)
+    td = torch.float32 if prec == api.F32 else torch.float64
+    ne = api.local_elems(po)
+    with torch.cuda.stream(stream):
+        # the spectra of two random fields, kept aside: the call consumes its inputs, so every timed run starts from a copy
+        # (made outside the timed region)
+        a0 = torch.zeros(ne * 2, dtype=td, device="cuda")
+        T.offt_hip_fill_input(po, a0.data_ptr(), 1)
+        api.offt_3d_execute(po, a0.data_ptr(), a0.data_ptr())
+        b0 = a0 * 0.5
+        a, b = a0.clone(), b0.clone()
+    pa, pb = a.data_ptr(), b.data_ptr()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def run(fn):
+        with torch.cuda.stream(stream):
+            a.copy_(a0)
+            b.copy_(b0)
+            ev[0].record(stream)
+            fn()
+            ev[1].record(stream)
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) * 1e-3
+
+    def caller():  # without the call: two inverses, a multiply of the caller's own, one forward
+        api.offt_3d_execute_dir(po, pa, pa, +1)
+        api.offt_3d_execute_dir(po, pb, pb, +1)
+        if r2c:  # real rows (with their two padding scalars a row: (n + 2) / n of the field)
+            a.mul_(b)
+        else:
+            torch.view_as_complex(a.view(-1, 2)).mul_(torch.view_as_complex(b.view(-1, 2)))
+        api.offt_3d_execute(po, pa, pa)
+
+    rs = (("fused", lambda: api.offt_hip_execute_product(po, pa, pb, pa)),
+          ("generic", lambda: api.offt_hip_execute_product(plans["generic"], pa, pb, pa)),
+          ("caller", caller))
+    fusedp, fusedg = api.offt_hip_product_fused(po), api.offt_hip_product_fused(plans["generic"])
+    t = {k: [] for k, _ in rs}
+    for rep_i in range(2 + MIXED_REPS):
+        for name, fn in rs:
+            dt = run(fn)
+            if rep_i >= 2:
+                t[name].append(dt)
+    mn, md = {k: min(v) for k, v in t.items()}, {k: float(np.median(v)) for k, v in t.items()}
+    tag = f"{'r2c ' if r2c else ''}{'f32' if prec == api.F32 else 'f64'} {n}^3"
+    # bytes per point (per half-spectrum point on an r2c plan), f64 (DESIGN.md 4.5): a MODEL, not a measurement
+    print(f"prod: {tag}: call [{'fused' if fusedp else 'generic'}] min {mn['fused'] * 1e3:.3f} ms median {md['fused'] * 1e3:.3f} ms  "
+          f"call without prod_pass [{'fused' if fusedg else 'generic'}] min {mn['generic'] * 1e3:.3f} ms median {md['generic'] * 1e3:.3f} ms  "
+          f"caller's route min {mn['caller'] * 1e3:.3f} ms median {md['caller'] * 1e3:.3f} ms  "
+          f"fused/generic min {mn['fused'] / mn['generic']:.3f} median {md['fused'] / md['generic']:.3f}  "
+          f"fused/caller min {mn['fused'] / mn['caller']:.3f} median {md['fused'] / md['caller']:.3f}  "
+          f"generic spread {md['generic'] / mn['generic'] - 1:.3f}  caller spread {md['caller'] / mn['caller'] - 1:.3f}  "
+          f"byte model (f64, 240 / 336 B per point) {240 / 336:.3f}  n {MIXED_REPS}  zgroup_mib {T.offt_hip_get_option(po, OPT_ZGROUP_MIB)}",
+          flush=True)
+    for p in plans.values():
+        api.offt_3d_fin(p)
+    del a, b, a0, b0
+    torch.cuda.empty_cache()
+
+
 def probe_shells(rest):
     """shells:[r2c:][f64|f32:]N -- offt_hip_spectrum_shells next to the in-place real pointwise sweep over the same block"""
     r2c = rest.startswith("r2c:")
@@ -405,6 +495,9 @@ def main():
             continue
         if spec.startswith("shells:"):
             probe_shells(spec[7:])
+            continue
+        if spec.startswith("prod:"):
+            probe_prod(spec[5:], zg)
             continue
         if spec.startswith("sum:mixed:"):
             probe_sum_mixed(spec[10:], zg)
